@@ -6,7 +6,7 @@ A "step" = one complete circular-order computation (initial row sums, the whole
 agglomeration loop, expansion) on a synthetic random symmetric matrix that is already
 resident in HBM when the step starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--taxa 32768] [--seed 1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--taxa 32768] [--seed 1] [--full] [--dump-outputs DIR]
 
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU) and orders the SAME
 matrix on all N GPUs (BASELINE.json's metric: one problem, strong scaling): every rank holds the matrix
@@ -19,11 +19,19 @@ created the ranks agree to let rank 0 compute alone (reported in config.parallel
 FNN_BENCH_REPLICAS=1 instead runs N independent orders (seed + rank), one per GPU: that is NOT the
 BASELINE metric and is reported under its own metric name (orders per second).
 
-Outside the timed region the line also carries: `roofline` (the streaming kernel that is left, with its share
-of the GPU time), `chain` (per-kernel averages of the latency-bound event chain from an extra run with HIP events
-around every launch), `cpu_baseline` (the oracle on the host cores: the first events of the same matrix,
-extrapolated, plus a fully measured run at n = 4096 on one thread and on all cores next to the engine's own
-time at that size), and the comparison of the order with the oracle's golden (tests/golden/oracle_big.json).
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given and
+prints the line.  Besides the headline it carries only what the timed run's own statistics give: `roofline` (the
+streaming kernel that is left, with its share of the GPU time), the phases and counters of the run.
+
+--full adds, outside the timed region: `chain` (per-kernel averages of the latency-bound event chain from an extra
+run with HIP events around every launch, and the Amdahl estimate and k_track figures built on it), the measured
+stream-read rate, `config5_e2e_s` (BASELINE config 5), `cpu_baseline` (the oracle on the host cores: the first
+events of the same matrix, extrapolated, plus a fully measured run at n = 4096 on one thread and on all cores next
+to the engine's own time at that size), the comparison of the order with the oracle's golden
+(tests/golden/oracle_big.json) and, with several ranks, the comparison of every rank's order.
+
+--dump-outputs DIR writes what the last timed step returned to its caller: DIR/order.npy, the circular order
+(n + 1 entries) as float64.  The inputs depend only on --taxa and --seed.
 
 Prints ONE JSON line on rank 0.
 """
@@ -210,6 +218,13 @@ def golden_check(n, seed, order):
     return None
 
 
+def dump_outputs(out_dir, order):
+    """What one step returns to its caller (Handle.run): the circular order, as float64 (exact for every taxon index)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "order.npy"), np.asarray(order, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -217,10 +232,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--taxa", "--n", dest="n", type=int, default=32768)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-chain", action="store_true", help="skip the extra run that times every kernel of the event chain")
-    ap.add_argument("--no-config5", action="store_true", help="skip BASELINE config 5 (order + split weights + Nexus document, ~100 s, outside the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements and checks outside the timed region: chain run, stream probe, config 5, "
+                         "CPU baseline, golden comparison, every rank's order")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's circular order to DIR/order.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-chain", action="store_true", help="with --full: skip the extra run that times every kernel of the event chain")
+    ap.add_argument("--no-config5", action="store_true", help="with --full: skip BASELINE config 5 (order + split weights + Nexus document, ~100 s, outside the timed region)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -307,11 +329,13 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if same_gpu else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, last[0])
 
     # ---- outside the timed region: every kernel of the event chain between HIP events (all ranks of a sharded run
     # take part: the exchange is collective)
     chain = None
-    if worker and not args.no_chain:
+    if worker and args.full and not args.no_chain:
         api.set_scan_timing(h._h, 2)
         _, st2 = one_step()
         ms = (C.c_double * 8)()
@@ -336,7 +360,7 @@ def main():
         }
     # ---- several ranks: every rank's order, not only rank 0's (the replicated event chain rests on identical decisions)
     ranks_orders = None
-    if dist is not None and not replicas:
+    if dist is not None and not replicas and args.full:
         mine = hashlib.sha256(last[0].tobytes()).hexdigest() if (worker and last is not None) else None
         ranks_orders = [None] * world
         dist.all_gather_object(ranks_orders, mine)
@@ -348,7 +372,7 @@ def main():
         sec = elapsed / args.steps
         fp64_equiv = 8.0 * float(st.sum_entries)     # BASELINE.md's 8 * sum E_t, for reference
         assert sorted(order[1:].tolist()) == list(range(1, n + 1)) and order[0] == 0 and order[1] == 1
-        gold = golden_check(n, seed, order) if not replicas else None
+        gold = golden_check(n, seed, order) if (args.full and not replicas) else None
         assert gold is not False, "the circular order differs from the oracle's golden (tests/golden/oracle_big.json)"
         ranks_seen = None
         if ranks_orders is not None:
@@ -455,16 +479,17 @@ def main():
             "windows_that_could_not_certify": int(st.n_window_fails),
             "source_sha256": {"fnn_hip.hip": source_sha256()[:16]},
         }
-        try:
-            g = C.c_double(0.0)
-            if api.stream_probe(dev_index, 4 << 30, 5, C.byref(g)) == 0:
-                out["roofline"]["measured_stream_read_gbps"] = round(g.value, 1)
-        except Exception:
-            pass
+        if args.full:
+            try:
+                g = C.c_double(0.0)
+                if api.stream_probe(dev_index, 4 << 30, 5, C.byref(g)) == 0:
+                    out["roofline"]["measured_stream_read_gbps"] = round(g.value, 1)
+            except Exception:
+                pass
         # ---- BASELINE.json configs[4], outside the timed region: the same 32768 taxa end to end - order, circular split
         # weights (fnn_split_weights_f64: block active-set method, with the solver's own Kuhn-Tucker certificate), Nexus
         # document (the routine the CLI runs, to /dev/null) - FastNN.java:369-491
-        if n == 32768 and args.gpus == 1 and not args.no_config5:
+        if args.full and n == 32768 and args.gpus == 1 and not args.no_config5:
             try:
                 out["config5_e2e_s"] = config5(api, h, n, seed, order)
             except Exception as e:  # reported, never required for the headline
@@ -472,7 +497,7 @@ def main():
         if h is not None:
             h.close()
             h = None
-        if not args.no_cpu_baseline and args.gpus == 1:
+        if args.full and not args.no_cpu_baseline and args.gpus == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(n, seed, int(st.sum_entries))
                 out["cpu_baseline"]["measured_n4096"] = cpu_measured_small(api, dev_index)

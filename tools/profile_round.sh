@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round measurements on the GPU box (everything lands under gpurun_out/<tag>_*; copy what is to be kept to profiles/<round>/):
-#   1. the bench line (python3 bench.py);
+#   1. the whole bench line (python3 bench.py --full);
 #   2. rocprofv3 --kernel-trace --stats of the same command (without the CPU baseline and the extra chain run);
 #   3. PMC passes over the scheduled screening launches (FETCH_SIZE / WRITE_SIZE in separate runs, as MI355X_MICROARCH.md
 #      prescribes) -> HBM bytes per launch vs the algorithmic bytes;
@@ -12,7 +12,7 @@ set -o pipefail
 TAG=${1:-r03}
 OUT=$GRAFT_REPO_ROOT/gpurun_out
 cd $GRAFT_REPO_ROOT
-python3 bench.py --steps 5 --warmup 2 > $OUT/${TAG}_bench_n32768.json 2> $OUT/${TAG}_bench.err || exit 1
+python3 bench.py --steps 5 --warmup 2 --full > $OUT/${TAG}_bench_n32768.json 2> $OUT/${TAG}_bench.err || exit 1
 tail -c 600 $OUT/${TAG}_bench_n32768.json; echo
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_${TAG} -- python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-chain --no-config5 > $OUT/${TAG}_bench_under_rocprof_n32768.json 2> $OUT/${TAG}_rocprof.err || exit 2
