@@ -107,7 +107,7 @@ struct State {
     int64_t n_events, sum_entries;
     int32_t error;  // non-zero if an "unreachable" branch was taken
     // ---- fp32 screening (see screen_delta) ----
-    int32_t screen_ok;     // the bound is valid for this matrix (finite, |D| < 1e37)
+    int32_t screen_ok;     // the bound is valid for this matrix (finite, |D| (3n + 64) < 1e37: no float overflows)
     int32_t rescan_all;    // candidate list overflowed: rescan every unit
     int32_t ncand;         // units in clist
     int32_t nonneg;        // no negative entry in the input matrix (then none ever appears)
@@ -410,6 +410,8 @@ FNN_HD void scan_micro(int32_t r0, int32_t c0, int32_t m, int32_t twoP, double c
 //   the subtractions                             2 u M
 //   the same again for e, plus subnormal slack   (generously) the same
 //   total <= u Dmax (7 (c-2) + 6 n), doubled by screen_delta.
+// All of this assumes every float formed is finite: screen_ok (init_thread) asks Dmax (3n + 64) < 1e37, which keeps
+// |Sx| and every bracket term far below FLT_MAX; otherwise the run takes the plain fp64 scan.
 // Per unit the pass records min LB and min UB.  Let UBg be the smallest UB (of this rank).  The
 // pair with the true minimum has LB <= Q* <= UBg, and every pair with LB > UBg has a true Q
 // STRICTLY above the true minimum, so rescanning (fp64, exact tie-break) only the units whose
@@ -451,7 +453,7 @@ FNN_HD float screen_k1(const State& st) {
 }
 FNN_HD float screen_k2(const State& st) { return (float)((((double)st.c - 2.0) * (1.0 + (double)SCR_KAPPA * 1.000001)) * (1.0 + 2e-7)); }
 
-FNN_HD float fminf_(float a, float b) { return __builtin_fminf(a, b); }  // v_min_f32 (no NaN arises when screen_ok)
+FNN_HD float fminf_(float a, float b) { return __builtin_fminf(a, b); }  // v_min_f32 (no NaN arises when screen_ok: init_thread)
 FNN_HD float fabsf_(float a) { return __builtin_fabsf(a); }             // a source modifier on the GPU
 
 struct Brk { float lb, ub; };  // running minima of the lower / upper bounds
@@ -2035,9 +2037,12 @@ FNN_HD void init_thread(const Dev& d, int32_t k) {
     d.pslot[k] = k;
     if (d.islot) d.islot[k + 1] = k;
     if (k == 0) {
-        // the screening bound needs a finite, float-representable bound on |D| (prep kernel)
+        // the screening bound needs every float it forms to be finite (prep kernel: max |D|): |Sx| <= n Dmax and every
+        // bracket term <= ((c-2)(1 + kappa) + 2n) Dmax < 3.01 n Dmax (c <= n), so Dmax (3n + 64) < 1e37 keeps all of them
+        // 30x below FLT_MAX.  (A bound on Dmax alone is not enough: with Dmax < 1e37 but n Dmax > FLT_MAX, (float)Sx is
+        // inf, the brackets of whole rows become -inf or NaN and the rescan threshold no longer bounds the minimum.)
         const double dmax = __builtin_bit_cast(double, d.st->dmax_bits);
-        d.st->screen_ok = (d.H != nullptr && dmax == dmax && dmax < 1e37) ? 1 : 0;
+        d.st->screen_ok = (d.H != nullptr && dmax == dmax && dmax * (3.0 * (double)d.n + 64.0) < 1e37) ? 1 : 0;
         d.st->la_W = 16.0 * dmax;  // first lookahead window width; adapted at every base scan (la_close_base)
     }
 }

@@ -8,6 +8,10 @@ oracle's results for them in the build container) and the GPU tests that replay 
   neg               uniform53 shifted by -0.25: a third of the entries negative (the lookahead windows' monotonicity
                     argument needs non-negative entries: the engine takes the plain fp64 scan for every event - no screening
                     pass, no windows; with several ranks the scan of every event is sharded -)
+  outgroup          uniform53 with 3 taxa pushed 1e6 away from everyone (1e6 added to their rows and columns).  The Q
+                    criterion only shifts under such pendant lengths, but max |D| grows by 1e6, so the screening slack
+                    (screen_delta, proportional to max |D|) outgrows the spread of Q: every screening unit is a candidate
+  dup               n/4 distinct treenoise taxa, each present 4 times, permuted: zero distances and identical rows
 
 Host-generated classes depend on numpy's default_rng stream (PCG64), which is stable across numpy versions.
 """
@@ -16,6 +20,7 @@ import hashlib
 import numpy as np
 
 DEVICE_DISTS = ("uniform53", "dec4")
+OUTGROUP_DIST = 1e6
 
 
 def _tree(n, seed, dyadic):
@@ -77,6 +82,18 @@ def make(n, dist, seed, oracle):
         return np.ascontiguousarray(T + N + N.T)
     if dist == "circnoise":
         return circ_noise(n, seed)
+    if dist == "outgroup":
+        D = oracle.synth(n, seed, "uniform53")
+        o = np.random.default_rng(seed).choice(n, 3, replace=False)
+        D[o, :] += OUTGROUP_DIST
+        D[:, o] += OUTGROUP_DIST
+        np.fill_diagonal(D, 0.0)
+        return D
+    if dist == "dup":
+        k = (n + 3) // 4
+        T = make(k, "treenoise", seed, oracle)
+        idx = np.random.default_rng(seed + 2000).permutation(np.repeat(np.arange(k), 4)[:n])
+        return np.ascontiguousarray(T[np.ix_(idx, idx)])
     if dist == "neg":
         D = oracle.synth(n, seed, "uniform53")
         D -= 0.25
@@ -92,3 +109,48 @@ def sha_big(a):
     for o in range(0, flat.size, step):
         h.update(flat[o:o + step].tobytes())
     return h.hexdigest()
+
+
+# Power-of-two scalings of a matrix for the value-range tests (tests/test_value_range.py).  D -> ldexp(D, k) commutes with every
+# fp64 operation of the algorithm while nothing overflows or goes subnormal, so the trajectory stays the same and every scan
+# minimum is ldexp(best, k); the engine's fp32 / bf16 screening copy, on the other hand, sees very different numbers.
+FLT_MAX = float(np.finfo(np.float32).max)
+SCREEN_DMAX_LIMIT = 1e37          # max |D| (3n + 64) must stay below this for the engine to screen (fnn_core.h: init_thread)
+
+
+def screens(D, k=0):
+    """Whether the engine screens ldexp(D, k) (fnn_core.h: init_thread, screen_ok)."""
+    return np.ldexp(float(np.abs(D).max()), k) * (3.0 * D.shape[0] + 64.0) < SCREEN_DMAX_LIMIT
+
+
+def float_rowsum_overflow(D, k):
+    """Fraction of the rows whose fp64 row sum at the start, scaled by 2^k, rounds to inf in float (as (float)Sx does)."""
+    s = np.abs(D).sum(axis=1)
+    with np.errstate(over="ignore"):
+        return float(np.isinf(np.ldexp(s, k).astype(np.float32)).mean())
+
+
+def scale_exponents(D, band=(0.1, 0.9)):
+    """The exponents k of the value-range sweep, with the band they are meant to reach:
+      k_band  max |D| 2^k < 1e37 and 10-90 % (`band`) of the float row sums overflow at the start (the one closest to half);
+              absent when no power of two reaches that band
+      k_all   the largest k with max |D| 2^k < 1e37: every float row sum overflows at the start
+      k_off   the smallest k with max |D| 2^k >= 1e37
+      k_edge  the largest k at which the engine still screens (max |D| 2^k (3n + 64) < 1e37: no float overflows; the engine
+              screened up to k_all once, and diverged from the oracle in the band)
+      -60, -140, -900: small entries, entries in the fp32 / bf16 subnormal range, entries that are 0 in float"""
+    dmax = float(np.abs(D).max())
+    k_all = int(np.floor(np.log2(SCREEN_DMAX_LIMIT / dmax)))
+    while np.ldexp(dmax, k_all) >= SCREEN_DMAX_LIMIT:
+        k_all -= 1
+    while np.ldexp(dmax, k_all + 1) < SCREEN_DMAX_LIMIT:
+        k_all += 1
+    k_edge = k_all
+    while not screens(D, k_edge):
+        k_edge -= 1
+    ks = {"k_all": k_all, "k_off": k_all + 1, "k_edge": k_edge, "k_m60": -60, "k_m140": -140, "k_m900": -900}
+    fr = {k: float_rowsum_overflow(D, k) for k in range(k_all - 40, k_all + 1)}
+    inband = [(abs(f - 0.5), k) for k, f in fr.items() if band[0] <= f <= band[1]]
+    if inband:  # (small n: the row sums may be too concentrated for any power of two to split them)
+        ks["k_band"] = min(inband)[1]
+    return ks

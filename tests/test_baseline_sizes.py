@@ -33,7 +33,13 @@ BIG_CASES = [(4096, "uniform53", 1), (4096, "dec4", 1), (16384, "uniform53", 1),
              # weights outgrow the solver's default factor) and the 4-decimal generator at 16384 taxa
              (4096, "circnoise", 11), (8192, "circnoise", 12), (16384, "dec4", 1),
              # tree + noise at the headline size (2.6 h of the oracle on 8 threads)
-             (32768, "treenoise", 11)]
+             (32768, "treenoise", 11),
+             # the screened default mode at its edges: 3 far-away taxa (loose brackets: every unit is rescanned), duplicated taxa
+             # (zero distances, identical rows), sizes that are not a multiple of the 2048-column tile, and the size just below
+             # the one where screening switches on
+             (4096, "outgroup", 13), (8192, "outgroup", 14), (4096, "dup", 16), (8192, "dup", 17),
+             (4097, "uniform53", 1), (6007, "treenoise", 6), (8193, "dec4", 1), (4095, "tree", 5)]
+SCREEN_MIN_N = 4096   # the default mode screens from this size on (fnn_hip.hip: screen_min_n)
 
 
 
@@ -108,6 +114,12 @@ def test_default_mode_matches_oracle_golden(hip_api, oracle, n, dist, seed):
     assert hashlib.sha256(best.tobytes()).hexdigest() == c["best_bits_sha256"]
     if dist == "neg":
         assert st.n_window_hits == 0, "windows must stay off on a matrix with negative entries"
+    elif n < SCREEN_MIN_N:
+        assert st.n_screen_events == 0 and st.n_window_hits == 0, "below screen_min_n the default mode is the plain fp64 scan"
+    elif dist == "outgroup":
+        # loose brackets: far more units rescanned than the ~16 per event of the usual inputs (every unit of the 256-768 at
+        # these sizes is a candidate; tests/test_value_range.py: test_outgroup_slack_exceeds_the_spread_of_q)
+        assert st.n_rescan_units > 64 * st.n_screen_events, (st.n_rescan_units, st.n_screen_events)
     else:
         assert st.n_base_scans > 0 and st.n_window_hits > 0, "the shipped mode (lookahead windows) did not run"
     # the write-through hand-over of k_track's fan-in is measured behaviour of the part: a reread means

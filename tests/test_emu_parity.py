@@ -200,3 +200,36 @@ def test_get_matrix_returns_the_resident_matrix_until_the_run_consumes_it(emu_ap
         with pytest.raises(FnnError) as ei:
             h.matrix()
         assert ei.value.code == -5
+
+
+@pytest.mark.parametrize("n,dist,seed,mode", [(400, "uniform53", 1, 0), (400, "tree", 2, 2), (700, "treenoise", 3, 5),
+                                               (300, "outgroup", 4, 0), (400, "dup", 5, 2), (300, "neg", 6, 5)])
+def test_value_range_sweep(emu_api, oracle, n, dist, seed, mode):
+    """The screened mode (on at these sizes in the emulation) on ldexp(D, k) for the exponents of tests/test_value_range.py:
+    the oracle's trajectory with every scan minimum times 2^k.  Where no power of two splits the float row sums, a scale
+    that puts FLT_MAX at their median (or as close as max |D| < 1e37 allows) does (compared with the oracle on that matrix).
+    The screening guard of the engine once admitted that band, and the outgroup class diverged there."""
+    import inputs
+    emu_api.set_order_mode(mode)
+    D = inputs.make(n, dist, seed, oracle)
+    o0, e0, s0 = oracle.run(D)
+
+    def run(Dk):
+        with Handle(emu_api, n, record_events=True) as h:
+            h.set_matrix(Dk)
+            order, st = h.run()
+            return order, st, h.events()
+
+    for k in inputs.scale_exponents(D, band=(0.0, 1.0)).values():
+        order, st, ev = run(np.ldexp(D, k))
+        assert (order == o0).all() and st.sum_entries == s0, k
+        for f in ("m_before", "c_before", "cx_id", "cy_id", "x_id", "y_id", "kind", "u_id", "entries"):
+            assert (ev[f] == e0[f]).all(), (k, f)
+        assert (ev["best"].view(np.int64) == np.ldexp(e0["best"], k).view(np.int64)).all(), k
+    s = np.abs(D).sum(axis=1)
+    Db = D * min(inputs.FLT_MAX / np.median(s), 0.99 * inputs.SCREEN_DMAX_LIMIT / np.abs(D).max())
+    assert 0.0 < inputs.float_rowsum_overflow(Db, 0) < 1.0 and np.abs(Db).max() < inputs.SCREEN_DMAX_LIMIT
+    o1, e1, s1 = oracle.run(Db)
+    order, st, ev = run(Db)
+    assert (order == o1).all() and st.sum_entries == s1
+    assert ev.tobytes() == e1.tobytes()
