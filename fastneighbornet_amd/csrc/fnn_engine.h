@@ -99,7 +99,6 @@ class Engine {
             !(dev.spos = (int32_t*)be.alloc(sizeof(int32_t) * (nn + 8))) ||
             !(dev.pslot = (int32_t*)be.alloc(sizeof(int32_t) * (nn + 8))) ||
             !(dev.chain = (double*)be.alloc(sizeof(double) * CHAIN_BUFS * (size_t)dev.cstride)) ||
-            !(dev.plan = (uint64_t*)be.alloc(sizeof(uint64_t) * PLAN_WORDS)) ||
             !(dev.recs = (Cand*)be.alloc(sizeof(Cand) * be.max_records(n))) ||
             !(dev.rchk = (uint64_t*)be.alloc(sizeof(uint64_t) * (2048 + 8))) ||
             !(dev.T = (double*)be.alloc(sizeof(double) * (nn + 8))) ||
@@ -143,7 +142,7 @@ class Engine {
 
     void destroy() {
         be.free(dev.D); be.free(dev.Sx); be.free(dev.sid); be.free(dev.spos); be.free(dev.pslot);
-        be.free(dev.chain); be.free(dev.plan); be.free(dev.recs); be.free(dev.rchk); be.free(dev.T); be.free(dev.gsend); be.free(dev.grecv); be.free(dev.wsend); be.free(dev.wrecv); be.free(d_status); d_status = nullptr; be.free(dev.H); be.free(dev.srec); be.free(dev.stile); be.free(dev.clist); be.free(dev.shit); be.free(dev.islot); be.free(dev.cstamp); be.free(dev.tpairs); be.free(dev.fresh); be.free(dev.ticket); be.free(dev.lacnt); be.free(dev.rperm); be.free(dev.rl_stamp); be.free(dev.rl_cnt); be.free(dev.rl_list); be.free(dev.rl_val); be.free(dev.rl_mail); be.free(dev.ticks); be.free(dev.lalog); be.free(dev.upart); be.free(dev.st); be.free(dev.evlog); be.free(dev.agglog);
+        be.free(dev.chain); be.free(dev.recs); be.free(dev.rchk); be.free(dev.T); be.free(dev.gsend); be.free(dev.grecv); be.free(dev.wsend); be.free(dev.wrecv); be.free(d_status); d_status = nullptr; be.free(dev.H); be.free(dev.srec); be.free(dev.stile); be.free(dev.clist); be.free(dev.shit); be.free(dev.islot); be.free(dev.cstamp); be.free(dev.tpairs); be.free(dev.fresh); be.free(dev.ticket); be.free(dev.lacnt); be.free(dev.rperm); be.free(dev.rl_stamp); be.free(dev.rl_cnt); be.free(dev.rl_list); be.free(dev.rl_val); be.free(dev.rl_mail); be.free(dev.ticks); be.free(dev.lalog); be.free(dev.upart); be.free(dev.st); be.free(dev.evlog); be.free(dev.agglog);
         dev = Dev{};
         be.close();
     }
@@ -331,7 +330,7 @@ class Engine {
             return fail(FNN_EHIP, "fnn_begin: state upload failed (" + be.err() + ")");
         if (be.memset(dev.islot, 0xFF, sizeof(int32_t) * (3 * (size_t)(n > 0 ? n : 1) + 8)) != FNN_OK ||
             be.memset(dev.cstamp, 0, sizeof(int32_t) * (3 * (size_t)(n > 0 ? n : 1) + 8)) != FNN_OK ||
-            be.memset(dev.ticket, 0, sizeof(uint32_t) * 32 * 72) != FNN_OK || be.memset(dev.plan, 0, sizeof(uint64_t) * PLAN_WORDS) != FNN_OK || be.memset(dev.lacnt, 0, 256) != FNN_OK || be.memset(dev.ticks, 0, sizeof(int64_t) * TICK_WORDS) != FNN_OK)
+            be.memset(dev.ticket, 0, sizeof(uint32_t) * 32 * 72) != FNN_OK || be.memset(dev.lacnt, 0, 256) != FNN_OK || be.memset(dev.ticks, 0, sizeof(int64_t) * TICK_WORDS) != FNN_OK)
             return fail(FNN_EHIP, "fnn_begin: memset failed (" + be.err() + ")");
         if (n > 3) {
             // max |D| (error bounds of the screening pass and of the certified 4-candidate choice), the bf16 copy if wanted
@@ -501,14 +500,11 @@ class Engine {
             // with lookahead windows on, k_update closes the events and the exact row sum of the new
             // cluster is computed inside the next event's k_track (flushed before the host looks)
             be.defer_chain = dev.la != 0 && !std::getenv("FNN_NO_DEFER");
-            const bool graph = be.graph_batches && comm_mode == 0;
-            if (graph && be.capture_begin() != FNN_OK) return fail(FNN_EHIP, "stream capture failed (" + be.err() + ")");
             for (int i = 0; i < batch; i++) {
                 int32_t rce = enqueue_event();
                 if (rce != FNN_OK) return rce;
             }
             if (be.defer_chain && be.launch_chain_flush(dev) != FNN_OK) return fail(FNN_EHIP, "launch failed (" + be.err() + ")");
-            if (graph && be.capture_end_launch() != FNN_OK) return fail(FNN_EHIP, "graph launch failed (" + be.err() + ")");
             be.defer_chain = false;
             int32_t rc = enqueue_status_exchange();
             if (rc != FNN_OK) return rc;

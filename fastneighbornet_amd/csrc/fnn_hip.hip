@@ -1474,13 +1474,6 @@ struct DecideLds {
     double tfin[2];            // T of the previous event's new cluster, just summed
     double rx[4];
     Quad qd;
-    // fused event kernel (k_track with fuse): the plan message (sent by the deciding workgroup, received by the column workgroups),
-    // the slot of the previous event's cluster whose T the decide step has just summed (tfin; -2: none), and the deciding
-    // workgroup's copy of the involved slots' block
-    PlanMsg msg;
-    int32_t msg_pU, berr;
-    int32_t fz[6];             // {chain_pending, chain_buf, chain_U, event tag, column blocks} at the start of the launch, the workgroup's index
-    double blk[MAX_S * MAX_S], sxl[MAX_S], tl[MAX_S];
 };
 
 constexpr int ST_NW = (int)(sizeof(State) / 4);
@@ -1580,7 +1573,6 @@ __device__ __forceinline__ void decide_step(const Dev& d, DecideLds& S, ChainLds
     const bool need = S.need != 0;
     const int32_t m = lst.m, P = lst.P;
     const int32_t tpU = lst.tp_n > 0 ? lst.tp_U : -2;
-    if (tid == 0) S.msg_pU = tpU;
     // ONE round trip: wave 0 fetches the table entries the plan can touch, the 4 x 4 block of the matrix over the two
     // clusters' nodes and their T; wave 1 sums the partial sums of T of the previous event's new cluster
     if (wv == 0) {
@@ -1627,8 +1619,7 @@ __device__ __forceinline__ void decide_step(const Dev& d, DecideLds& S, ChainLds
             for (int off = 32; off >= 1; off >>= 1) { tu += __shfl_down(tu, off, 64); tv += __shfl_down(tv, off, 64); }
             if (lane == 0) {
                 S.tfin[0] = tu; S.tfin[1] = tv;
-                // write-through: in the fused event kernel a column thread of the same launch (another compute unit, maybe another L2
-                // slice) stores to the same address later; two dirty copies would be written back in an undefined order
+                // (write-through where a plain store would do - every reader is a later kernel: kept from the removed one-launch event)
                 __hip_atomic_store(reinterpret_cast<uint64_t*>(d.T + lst.tp_U), __builtin_bit_cast(uint64_t, tu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(reinterpret_cast<uint64_t*>(d.T + lst.tp_U + 1), __builtin_bit_cast(uint64_t, tv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
@@ -2171,19 +2162,16 @@ constexpr int TRK_THREADS = 1024;
 constexpr int TRK_GROUP = 16;   // arrival tickets in two levels: same-address device-scope atomics cost ~50 ns each
 constexpr int TRK_FLAG = 32 * 65;  // word of d.ticket that carries "chain of event # done"
 constexpr int TRK_BAD = 32 * 67;   // word of d.ticket: a sweep item did not find the cluster it expected
-constexpr int TRK_ERR = 32 * 66;   // word of d.ticket: a wait inside the fused event kernel ran into its deadline (reported by the next launch)
 
 __device__ __forceinline__ void chain_workgroup(const Dev& d, ChainLds<CH_EPT>& L) {
     State* st = d.st;
     if (!st->chain_pending) return;
-    // (everything this workgroup needs from the control block is read NOW: in the fused event kernel the deciding workgroup
-    //  closes the event and writes the control block back while this sum may still be running)
-    const int32_t cU = st->chain_U, cm = st->chain_m, cb = st->chain_buf;
+    const int32_t cU = st->chain_U, cm = st->chain_m;
     const unsigned evtag = (unsigned)st->n_events;
-    const double usx = block_chain_sum2<CH_EPT>(d.chain + (size_t)cb * d.cstride, cm, CH_GUARD_BITS, L, nullptr);
+    const double usx = block_chain_sum2<CH_EPT>(d.chain, cm, CH_GUARD_BITS, L, nullptr);
     if (threadIdx.x == 0) {
-        // u.Sx and u.nbr.Sx (NetMakerOriginal.java:532, 535): write-through, drained, then the flag - column threads of the
-        // SAME launch may be waiting for them (fused event kernel); every later kernel sees them anyway
+        // u.Sx and u.nbr.Sx (NetMakerOriginal.java:532, 535): write-through, drained, then the flag - the exact re-sweep of the
+        // SAME launch (the deciding workgroup) waits on that flag before it reads them; every later kernel sees them anyway
         __hip_atomic_store(reinterpret_cast<uint64_t*>(d.Sx + cU), __builtin_bit_cast(uint64_t, usx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(reinterpret_cast<uint64_t*>(d.Sx + cU + 1), __builtin_bit_cast(uint64_t, usx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2215,19 +2203,7 @@ __device__ __forceinline__ void sweep_exact_item(const Dev& d, int64_t r, const 
 constexpr int TRK_REC_U = 1024;  // offset of the swept-pair records in d.recs
 
 struct SpecialOut { double val, tu, tv; };
-// WGB: the phases are separated by workgroup barriers (k_update: the other waves of the workgroup keep them company); without
-// it the calling wave is alone with the block - its LDS accesses execute in program order, a fence keeps the compiler from
-// moving them - and no other wave of the workgroup has to take part (the fused event kernel)
-template <bool WGB>
-__device__ __forceinline__ void special_sync() {
-    if (WGB) __syncthreads();
-    else {  // (LDS instructions of one wave execute in order: only the compiler has to be kept from moving them - no s_waitcnt on the
-            //  global stores and loads that are in flight, which a workgroup-scope fence would insert)
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-template <bool WGB>
+// the phases are separated by workgroup barriers (k_update: the other waves of the workgroup keep them company)
 __device__ __forceinline__ SpecialOut special_wave(const Dev& d, const State& lst, double* blk, double* sxl, double* tl, int32_t* berr, double* chain_dst) {
     const int lane = threadIdx.x & 63;
     const int nS = __builtin_amdgcn_readfirstlane(lst.nS);
@@ -2290,7 +2266,7 @@ __device__ __forceinline__ SpecialOut special_wave(const Dev& d, const State& ls
             }
         }
     }
-    special_sync<WGB>();
+    __syncthreads();
     // ---- the micro-ops, one phase each (fnn_core.h: op_thread)
     for (int ph = 0; ph < nops; ph++) {
         const int kind = __builtin_amdgcn_readfirstlane(lst.ops[ph].kind), mcur = __builtin_amdgcn_readfirstlane(lst.ops[ph].mcur);
@@ -2340,7 +2316,7 @@ __device__ __forceinline__ SpecialOut special_wave(const Dev& d, const State& ls
                 }
             }
         }
-        special_sync<WGB>();
+        __syncthreads();
     }
     // ---- add (new layout), NetMakerOriginal.java:520-533
     if (!ev_finish) {
@@ -2376,7 +2352,7 @@ __device__ __forceinline__ SpecialOut special_wave(const Dev& d, const State& ls
             out.val = val;
         }
     }
-    special_sync<WGB>();
+    __syncthreads();
     return out;
 }
 
@@ -2388,15 +2364,7 @@ struct UniLane { __device__ __forceinline__ int32_t operator()(int32_t x) const 
 // one thread per cluster; the CPU emulation runs that one against the oracle.  A wave runs alone on its SIMD
 // here and issues one instruction every ~4 cycles, so the length of a thread's instruction stream IS the
 // duration: splitting the pair halves it.)  All 64 lanes of a wave must call it (shuffles).
-// FUSED (k_track with fuse): the column threads run in the SAME launch as the decide step and the chain workgroup; what
-// those produce for a column comes in through `fx` instead of plain loads.
-struct BulkFix {
-    int32_t cU = -2, chain_wait = 0; unsigned evtag = 0;   // Sx[cU], Sx[cU + 1]: delivered by the chain workgroup of this launch
-    int32_t pU = -2; double tfin0 = 0.0, tfin1 = 0.0;      // T[pU], T[pU + 1]: summed by this launch's decide step
-    int32_t pov_n = 0, pov_slot[2] = {-1, -1}, pov_pos[2] = {0, 0};  // reference positions the plan changed (State.pov_*)
-};
-template <bool FUSED>
-__device__ __forceinline__ void bulk_column(const Dev& d, const PlanView& pv, const int32_t k, double* __restrict__ chain_dst, const BulkFix& fx,
+__device__ __forceinline__ void bulk_column(const Dev& d, const PlanView& pv, const int32_t k, double* __restrict__ chain_dst,
                                             double& dsum, double& dabs, double& tu, double& tv) {
     const bool paired = k < 2 * pv.P_old;
     bool act = k < pv.m_old;
@@ -2410,21 +2378,6 @@ __device__ __forceinline__ void bulk_column(const Dev& d, const PlanView& pv, co
     double sx = act ? d.Sx[k] : 0.0;
     double t_old = act ? d.T[k] : 0.0;
     int32_t pos = act ? d.spos[k] : 0;
-    if (FUSED && act) {
-        // what this launch itself produced cannot be read with plain loads (other compute units, other L2 slices):
-        if (k == fx.pU) t_old = fx.tfin0;          // T of the previous event's cluster: summed by this launch's decide step
-        if (k == fx.pU + 1) t_old = fx.tfin1;
-#pragma unroll
-        for (int q = 0; q < 2; q++) if (q < fx.pov_n && k == fx.pov_slot[q]) pos = fx.pov_pos[q];  // a position the plan changed
-        if (fx.chain_wait && (k == fx.cU || k == fx.cU + 1)) {  // its exact row sum: from the chain workgroup of this launch
-            const long long t0 = (long long)wall_clock64();
-            while (__hip_atomic_load(d.ticket + TRK_FLAG, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != fx.evtag) {
-                if ((long long)wall_clock64() - t0 > TRK_WAIT_TICKS) { atomicOr(d.ticket + TRK_ERR, 1u); break; }
-                __builtin_amdgcn_s_sleep(2);
-            }
-            sx = __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<const uint64_t*>(d.Sx + k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        }
-    }
     const bool odd = (k & 1) != 0;
     double told = 0.0;
     if (!pv.ev_finish) {
@@ -2490,131 +2443,21 @@ __device__ __forceinline__ void bulk_column(const Dev& d, const PlanView& pv, co
     }
 }
 
-
-// ---- the plan message of the fused event kernel (fnn_core.h: PlanMsg) ----
-// post: wave 0 of the deciding workgroup, from its LDS copy; every word carries the launch's tag, so no flag and no drain
-__device__ __forceinline__ void plan_post(const Dev& d, const PlanMsg& m, unsigned tag) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(&m);
-    __hip_atomic_store(d.plan + lane, ((uint64_t)tag << 32) | w[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(d.plan + 64 + lane, ((uint64_t)tag << 32) | w[64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// "no update in this launch" (kind 0): the waiting workgroups leave.  One wave.
-__device__ __forceinline__ void plan_post_none(const Dev& d, unsigned tag) {
-    const int lane = threadIdx.x & 63;
-    __hip_atomic_store(d.plan + lane, (uint64_t)tag << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(d.plan + 64 + lane, (uint64_t)tag << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// wait (wave 0 polls, the whole workgroup joins at the barrier); a deadline instead of a hang
-__device__ __forceinline__ void plan_wait(const Dev& d, PlanMsg& m, unsigned tag) {
-    if (threadIdx.x < 64) {
-        const int lane = threadIdx.x;
-        uint32_t* w = reinterpret_cast<uint32_t*>(&m);
-        const long long t0 = (long long)wall_clock64();
-        for (;;) {
-            const uint64_t a = __hip_atomic_load(d.plan + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint64_t b = __hip_atomic_load(d.plan + 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const bool ok = (uint32_t)(a >> 32) == tag && (uint32_t)(b >> 32) == tag;
-            if (__ballot(ok) == ~0ULL) { w[lane] = (uint32_t)a; w[64 + lane] = (uint32_t)b; break; }
-            if ((long long)wall_clock64() - t0 > TRK_WAIT_TICKS) {
-                w[lane] = 0u; w[64 + lane] = 0u;  // (kind = 0)
-                if (lane == 0) atomicOr(d.ticket + TRK_ERR, 2u);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(6);
-        }
-    }
-    __syncthreads();
-}
-
-// fuse != 0: a WINDOW event in ONE launch.  The launch sequence has no scan kernels (has_scan == 0) and no k_update: when
-// the window serves the event, the deciding workgroup (the tracking workgroup that arrives last) posts the plan as a message
-// (plan_post), runs the involved slots' phases itself and closes the event; tracking workgroup b < ceil(m / 1024) has waited for
-// the message and now updates the columns [1024 b, 1024 b + 1024) (bulk_column<true>); the SPARE workgroup (the launch's last)
-// takes the block of the deciding workgroup.  Saves a kernel boundary per event (~4.5 us: dispatch, the release at the end of
-// one kernel and the acquire at the start of the next) at the price of one message round trip (~1 us), and the chain
-// workgroup's exact row sum (14-23 us) now runs beside tracking AND update.  What the launch itself produces for a column
-// thread - T of the previous event's cluster (decide step), its exact row sum (chain workgroup), reference positions the plan
-// moved - travels in the message or is read write-through (BulkFix); the row-sum addends alternate between two chain buffers
-// (State.chain_buf) because the chain workgroup of this launch is still reading the other one.
-// ---- a COLUMN workgroup of the fused event kernel: block `block` of BULK_COLS columns by its first BULK_COLS threads (one wave per
-// SIMD, as in k_update: the column thread is a chain of latencies and scattered stores - a 1024-column block on one compute unit
-// took 7 us, 256 columns take 4); the other waves only keep the barriers company.
-constexpr int BULK_COLS = 256;
-__device__ __forceinline__ void column_workgroup(const Dev& d, PlanMsg& M, int block, double (*shp)[4], unsigned tag, int prof2) {
-    long long tk0 = prof2 ? (long long)wall_clock64() : 0;
-    // the plan cannot be there before the tracking, the fan-in and the decide step of this launch have run (>= 12 us): sleep through
-    // most of that instead of polling (the polls of all column workgroups go to the same few cache lines)
-    if (threadIdx.x < 64) {
-        const long long t0 = (long long)wall_clock64();
-        while ((long long)wall_clock64() - t0 < 1400) __builtin_amdgcn_s_sleep(32);  // 14 us of the 100 MHz clock
-    }
-    plan_wait(d, M, tag);
-    if (prof2) { const long long now_ = (long long)wall_clock64(); d.ticks[12] += now_ - tk0; tk0 = now_; }
-    if (M.kind != 1 || block >= M.nbulk) return;
-    double dsum = 0.0, dabs = 0.0, tu = 0.0, tv = 0.0;
-    if (threadIdx.x < BULK_COLS) {
-        const PlanView pv = plan_view(M, UniLane{});
-        BulkFix fx;
-        fx.cU = __builtin_amdgcn_readfirstlane(M.cU); fx.chain_wait = __builtin_amdgcn_readfirstlane(M.chain_wait);
-        fx.evtag = (unsigned)__builtin_amdgcn_readfirstlane(M.evtag);
-        fx.pU = __builtin_amdgcn_readfirstlane(M.pU);
-        fx.tfin0 = __builtin_bit_cast(double, ((uint64_t)(uint32_t)M.tfin[1] << 32) | (uint32_t)M.tfin[0]);
-        fx.tfin1 = __builtin_bit_cast(double, ((uint64_t)(uint32_t)M.tfin[3] << 32) | (uint32_t)M.tfin[2]);
-        fx.pov_n = __builtin_amdgcn_readfirstlane(M.pov_n);
-        fx.pov_slot[0] = __builtin_amdgcn_readfirstlane(M.pov_slot[0]); fx.pov_slot[1] = __builtin_amdgcn_readfirstlane(M.pov_slot[1]);
-        fx.pov_pos[0] = __builtin_amdgcn_readfirstlane(M.pov_pos[0]); fx.pov_pos[1] = __builtin_amdgcn_readfirstlane(M.pov_pos[1]);
-        const int chain_dst = __builtin_amdgcn_readfirstlane(M.chain_dst);
-        if (prof2) { const long long now_ = (long long)wall_clock64(); d.ticks[13] += now_ - tk0; tk0 = now_; }
-        bulk_column<true>(d, pv, (int32_t)(block * BULK_COLS + (int)threadIdx.x), d.chain + (size_t)chain_dst * d.cstride, fx, dsum, dabs, tu, tv);
-        if (prof2) { const long long now_ = (long long)wall_clock64(); d.ticks[14] += now_ - tk0; tk0 = now_; }
-        // per-workgroup partial sums (tree order), as k_update's
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            dsum += __shfl_down(dsum, off, 64); dabs += __shfl_down(dabs, off, 64);
-            tu += __shfl_down(tu, off, 64); tv += __shfl_down(tv, off, 64);
-        }
-        if ((threadIdx.x & 63) == 0) { double* r = shp[threadIdx.x >> 6]; r[0] = dsum; r[1] = dabs; r[2] = tu; r[3] = tv; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const int k = threadIdx.x;
-        d.upart[4 * (size_t)block + k] = ((shp[0][k] + shp[1][k]) + shp[2][k]) + shp[3][k];
-    }
-    if (prof2) d.ticks[15] += (long long)wall_clock64() - tk0;
-}
-
-// FUSE: a WINDOW event in ONE launch.  The launch sequence has no scan kernels (has_scan == 0) and no k_update: the grid carries
-// `ncol` COLUMN workgroups behind the tracking (and helper) workgroups.  When the window serves the event, the deciding workgroup
-// (the tracking workgroup that arrives last) posts the plan as a message (plan_post), runs the involved slots' phases itself - wave 0
-// alone, no workgroup barrier - and closes the event; column workgroup b has waited for the message and updates the columns
-// [256 b, 256 b + 256) (bulk_column<true>).  Saves a kernel boundary per event (~4.5 us: dispatch, the release at the end of one
-// kernel and the acquire at the start of the next) at the price of one message round trip (~1 us), and the chain workgroup's exact
-// row sum (14-23 us) runs beside tracking AND update.  What the launch itself produces for a column thread - T of the previous
-// event's cluster (decide step), its exact row sum (chain workgroup), reference positions the plan moved - travels in the message
-// or is read write-through (BulkFix); the row-sum addends alternate between two chain buffers (State.chain_buf) because the chain
-// workgroup of this launch is still reading the other one.  No address is written twice in one launch by different workgroups
-// with plain stores (their L2 slices would write back in an undefined order): T of the previous cluster goes out write-through.
-template <bool HELP, bool FUSE>
-__global__ __launch_bounds__(TRK_THREADS) void k_track(Dev d, int force_base, int timed, int has_scan, int tgroup, int ticks, unsigned jobtag, int ncol) {
+// ---- k_track (described above, at TRK_THREADS)
+template <bool HELP>
+__global__ __launch_bounds__(TRK_THREADS) void k_track(Dev d, int force_base, int timed, int has_scan, int tgroup, int ticks, unsigned jobtag) {
     __shared__ ChainLds<CH_EPT> L;
     __shared__ DecideLds S;
     __shared__ Cand sh[TRK_THREADS / 64], shu[TRK_THREADS / 64];
     __shared__ int lastflag;
     __shared__ double shs[2];
     __shared__ unsigned hword;
-    __shared__ double shp[BULK_COLS / 64][4];
     State* st = d.st;
     if (blockIdx.x == 0) {  // the chain workgroup
         chain_workgroup(d, L);
         return;
     }
-    const int wg = (int)blockIdx.x - 1, G = (int)gridDim.x - 1 - (HELP ? TRK_NHELP : 0) - (FUSE ? ncol : 0);
-    if (FUSE && wg >= G + (HELP ? TRK_NHELP : 0)) {  // a column workgroup
-        const int block = wg - G - (HELP ? TRK_NHELP : 0);
-        column_workgroup(d, S.msg, block, shp, jobtag, (ticks != 0 && threadIdx.x == 0 && block == 0) ? 1 : 0);
-        return;
-    }
+    const int wg = (int)blockIdx.x - 1, G = (int)gridDim.x - 1 - (HELP ? TRK_NHELP : 0);
     if (HELP && wg >= G) {  // a helper workgroup of the exact ComputeRx sums (see decide_step)
         rx_helper_workgroup(d, L, wg - G, jobtag, &hword);
         return;
@@ -2635,7 +2478,6 @@ __global__ __launch_bounds__(TRK_THREADS) void k_track(Dev d, int force_base, in
             st->ev_active = 0;  // (a launch sequence without a decide kernel must not replay the last event)
             if (HELP) job_post(d, jobtag, 0u);
         }
-        if (FUSE && wg == 0 && threadIdx.x < 64) plan_post_none(d, jobtag);
         return;
     }
     // every tracking workgroup fetches the control block now (nothing writes to it while they track): the one that
@@ -2646,7 +2488,6 @@ __global__ __launch_bounds__(TRK_THREADS) void k_track(Dev d, int force_base, in
             st->n_stalled++;
             if (HELP) job_post(d, jobtag, 0u);
         }
-        if (FUSE && wg == 0 && threadIdx.x < 64) plan_post_none(d, jobtag);
         return;
     }
     if (force_base || !la_active(*st)) {
@@ -2658,16 +2499,10 @@ __global__ __launch_bounds__(TRK_THREADS) void k_track(Dev d, int force_base, in
             st->stall = has_scan ? 0 : 1;
             if (!has_scan) st->n_stalled++;
         }
-        if (FUSE && wg == 0 && threadIdx.x < 64) plan_post_none(d, jobtag);
         return;
     }
-    // (fused event kernel) the pending row sum as the control block describes it at the START of the launch
-    const int32_t chain_pending0 = st->chain_pending, chain_buf0 = st->chain_buf, chain_U0 = st->chain_U, m0 = st->m;
+    const int32_t chain_pending0 = st->chain_pending, chain_U0 = st->chain_U;
     const unsigned evtag0 = (unsigned)st->n_events;
-    if (FUSE && threadIdx.x == 0) {  // (parked in LDS for the tail: no scalar register stays live across the decide step for them)
-        S.fz[0] = chain_pending0; S.fz[1] = chain_buf0; S.fz[2] = chain_U0; S.fz[3] = (int32_t)evtag0;
-        S.fz[4] = (m0 + BULK_COLS - 1) / BULK_COLS; S.fz[5] = 0;
-    }
     TrackArgs ta = track_args(*st);
     const int64_t items = track_item_count(ta);
     // The swept cluster's exact row sum is being computed by workgroup 0: the sweep runs on the tree-ordered
@@ -2765,7 +2600,6 @@ __global__ __launch_bounds__(TRK_THREADS) void k_track(Dev d, int force_base, in
         b = cand_none();
         bu = b;
         const unsigned badword = __hip_atomic_load(d.ticket + TRK_BAD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned errword = FUSE ? __hip_atomic_load(d.ticket + TRK_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
         const uint32_t tag = evtag0;
         bool stale = false, reread = false;
         for (int pass = 0; pass < 2; pass++) {
@@ -2796,7 +2630,6 @@ __global__ __launch_bounds__(TRK_THREADS) void k_track(Dev d, int force_base, in
                 d.ticket[TRK_BAD] = 0u;
                 lastflag = 2;
             }
-            if (errword != 0u) S.lst.error = 16;  // a wait of an earlier fused launch ran into its deadline
             if (stale) lastflag = 2;  // (a record that could not be read back intact: the window gives this event up)
             if (reread) S.lst.n_ev_persistent++;
         }
@@ -2859,99 +2692,6 @@ __global__ __launch_bounds__(TRK_THREADS) void k_track(Dev d, int force_base, in
         for (int q = 0; q < 8; q++) d.ticks[q] += S.tk[q + 1] - S.tk[q];
     }
     __syncthreads();
-    if (FUSE) {
-        // The rest of the event by WAVE 0 alone (the other waves wait at the barrier in front of the write-back): no workgroup
-        // barrier on this stretch - one wave's LDS accesses execute in program order (special_sync<false>).
-        if (threadIdx.x < 64) {
-            const int lane = (int)threadIdx.x;
-            const int32_t chain_pending0 = S.fz[0], chain_buf0 = S.fz[1], chain_U0 = S.fz[2], nbulk = S.fz[4];
-            const unsigned evtag0 = (unsigned)S.fz[3];
-            long long tk0 = prof ? (long long)wall_clock64() : 0;
-#define FUS_TICK(slot) do { if (prof) { const long long now_ = (long long)wall_clock64(); d.ticks[8 + (slot)] += now_ - tk0; tk0 = now_; } } while (0)
-            const bool upd = lst.la_hit && lst.ev_active;
-            if (!upd) plan_post_none(d, jobtag);
-            else {
-                // ---- the plan message: the tail of the control block (nS .. tgt) word for word, the scalars by three lanes
-                PlanMsg& M = S.msg;
-                const int chain_wait = chain_pending0 ? 1 : 0;
-                const int chain_dst = (chain_pending0 && chain_buf0 == 0) ? CHAIN_ALT : 0;
-                static_assert(offsetof(PlanMsg, fill) - offsetof(PlanMsg, nS) == 60 * 4 && sizeof(State) - offsetof(State, nS) == 60 * 4, "plan tail layout");
-                if (lane < 60) (&M.nS)[lane] = (&lst.nS)[lane];
-                if (lane < 44) M.fill[lane] = 0;
-                if (lane == 61) {
-                    M.kind = 1; M.last_wg = wg; M.pU = S.msg_pU; M.cU = chain_pending0 ? chain_U0 : -2; M.chain_wait = chain_wait;
-                    M.evtag = (int32_t)evtag0; M.chain_dst = chain_dst; M.nbulk = nbulk;
-                }
-                if (lane == 62) {
-                    M.pov_n = lst.pov_n; M.pov_slot[0] = lst.pov_slot[0]; M.pov_slot[1] = lst.pov_slot[1];
-                    M.pov_pos[0] = lst.pov_pos[0]; M.pov_pos[1] = lst.pov_pos[1]; M.pad0 = 0;
-                    M.m_old = lst.m_old; M.P_old = lst.P_old; M.ev_finish = lst.ev_finish; M.xs = lst.xs; M.ys = lst.ys; M.pad1 = 0;
-                }
-                if (lane == 63) {
-                    const uint64_t t0b = __builtin_bit_cast(uint64_t, S.tfin[0]), t1b = __builtin_bit_cast(uint64_t, S.tfin[1]);
-                    M.tfin[0] = (int32_t)(uint32_t)t0b; M.tfin[1] = (int32_t)(uint32_t)(t0b >> 32);
-                    M.tfin[2] = (int32_t)(uint32_t)t1b; M.tfin[3] = (int32_t)(uint32_t)(t1b >> 32);
-                }
-                special_sync<false>();
-                plan_post(d, M, jobtag);
-                FUS_TICK(0);
-                // ---- the involved slots' phases on this LDS copy (k_update's special workgroup, here without fetching the control block)
-                double* blk = S.blk; double* sxl = S.sxl; double* tl = S.tl;
-                if (lane == 0) S.berr = 0;
-                {
-                    bool mine = lane < lst.nS && chain_wait && (lst.S[lane < MAX_S ? lane : 0] == chain_U0 || lst.S[lane < MAX_S ? lane : 0] == chain_U0 + 1);
-                    if (__ballot(mine) != 0ULL) {  // an involved slot's exact row sum is still on its way from the chain workgroup of this launch
-                        const long long t_wait = (long long)wall_clock64();
-                        while (__hip_atomic_load(d.ticket + TRK_FLAG, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != evtag0) {
-                            if ((long long)wall_clock64() - t_wait > TRK_WAIT_TICKS) { if (lane == 0) lst.error = 10; break; }
-                            __builtin_amdgcn_s_sleep(2);
-                        }
-                    }
-                }
-                {
-                    const int32_t e = (int32_t)lane, i = e / MAX_S, j = e % MAX_S;
-                    special_block_load(dl, blk, sxl, tl, e);
-                    if (i < lst.nS && j == 0 && chain_wait && (lst.S[i] == chain_U0 || lst.S[i] == chain_U0 + 1))
-                        sxl[i] = __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<const uint64_t*>(d.Sx + lst.S[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                    if (i < lst.nS && j == 1 && S.msg_pU >= 0 && (lst.S[i] == S.msg_pU || lst.S[i] == S.msg_pU + 1)) tl[i] = S.tfin[lst.S[i] - S.msg_pU];
-                }
-                special_sync<false>();
-                FUS_TICK(1);
-                const SpecialOut o = special_wave<false>(d, lst, blk, sxl, tl, &S.berr, d.chain + (size_t)chain_dst * d.cstride);
-                double dsum = o.val, dabs = o.val < 0.0 ? -o.val : o.val, tu = o.tu, tv = o.tv;
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) {
-                    dsum += __shfl_down(dsum, off, 64); dabs += __shfl_down(dabs, off, 64);
-                    tu += __shfl_down(tu, off, 64); tv += __shfl_down(tv, off, 64);
-                }
-                if (lane == 0) {  // this workgroup's partial sums: record nbulk (behind the column blocks')
-                    double* r = d.upart + 4 * (size_t)nbulk;
-                    r[0] = dsum; r[1] = dabs; r[2] = tu; r[3] = tv;
-                }
-                FUS_TICK(2);
-                special_block_store(dl, blk, sxl, tl, (int32_t)lane);
-                // the close of the event (nothing in the update reads what it writes)
-                if (lane == 0) {
-                    lst.tp_n = lst.ev_finish ? 0 : nbulk + 1;  // partial sums of T of the new cluster's nodes: the next decide step adds them up
-                    lst.tp_U = lst.U;
-                    if (S.berr) lst.error = S.berr;
-                    lst.upart_n = nbulk + 1;
-                    lst.chain_m = lst.m;
-                    lst.chain_U = lst.U;
-                    lst.chain_buf = chain_dst;
-                    lst.chain_pending = lst.ev_finish ? 0 : 1;
-                    close_event(dl);
-                    if (lst.ev_finish) {  // special finish: u, v keep the default Sx (NetNode.java:15); nothing to sum
-                        d.Sx[lst.U] = 0.0;
-                        d.Sx[lst.U + 1] = 0.0;
-                    }
-                }
-                FUS_TICK(3);
-            }
-#undef FUS_TICK
-        }
-        __syncthreads();
-    }
     state_out(st, lst);
 #undef TRK_TICK
 }
@@ -3000,7 +2740,7 @@ __global__ __launch_bounds__(256) void k_update(Dev d, int defer, int ticks) {
         __syncthreads();
         UPD_TICK(1);
         if (threadIdx.x < 64) {  // (the other waves only keep the barriers company)
-            const SpecialOut o = special_wave<true>(d, lst, blk, sxl, tl, &berr, d.chain);
+            const SpecialOut o = special_wave(d, lst, blk, sxl, tl, &berr, d.chain);
             dsum = o.val;
             dabs = o.val < 0.0 ? -o.val : o.val;
             tu = o.tu;
@@ -3020,7 +2760,6 @@ __global__ __launch_bounds__(256) void k_update(Dev d, int defer, int ticks) {
                 lst.upart_n = (int)gridDim.x;
                 lst.chain_m = lst.m;
                 lst.chain_U = lst.U;
-                lst.chain_buf = 0;
                 lst.chain_pending = lst.ev_finish ? 0 : 1;
                 close_event(dl);
                 if (lst.ev_finish) {  // special finish: u, v keep the default Sx (NetNode.java:15); nothing to sum
@@ -3032,11 +2771,10 @@ __global__ __launch_bounds__(256) void k_update(Dev d, int defer, int ticks) {
         __syncthreads();
         state_out(st, lst);
     } else {
-        // ONE thread per column (node): bulk_column, shared with the fused event kernel (k_track with fuse)
+        // ONE thread per column (node): bulk_column
         const PlanView pv = plan_view(lst, UniLane{});
         UPD_TICK(1);
-        const BulkFix nofix{};
-        bulk_column<false>(d, pv, (int32_t)(blockIdx.x * 256 + threadIdx.x), d.chain, nofix, dsum, dabs, tu, tv);
+        bulk_column(d, pv, (int32_t)(blockIdx.x * 256 + threadIdx.x), d.chain, dsum, dabs, tu, tv);
         UPD_TICK(2);
     }
     // per-workgroup partial sums (tree order): of the new cluster's row-sum addends and their magnitudes (for
@@ -3250,8 +2988,6 @@ struct HipBackend {
     bool skip_unsched_scans = true; // FNN_UNSCHED_SCANS=1: keep the (mostly idle) scan kernels in unscheduled events
     int track_group = TRK_GROUP;  // k_track: workgroups per first-level arrival counter (FNN_TRACK_GROUP)
     bool defer_chain = false; // set by the engine: k_update closes the event, the exact u.Sx sum runs inside the next k_track
-    bool fuse_events = false; // window events as ONE launch (k_track<.., true>; FNN_FUSE=1).  Off: measured 1.456 s against 1.408 s at 32768 taxa
-    bool fused_last = false;  // the launch sequence being enqueued is such a fused one
     bool scan_nt = true;    // non-temporal matrix loads in the scan (FNN_SCAN_NT)
     bool ticks = false;     // FNN_TICKS=1: k_track records the phase split of its last workgroup (fnn_debug_event_ticks)
 
@@ -3318,8 +3054,6 @@ struct HipBackend {
         if (const char* e = std::getenv("FNN_EMIT_GRID")) { int v = std::atoi(e); if (v >= 1 && v <= 65535) emit_grid = v; }
         if (const char* e = std::getenv("FNN_RX_HELPERS")) rx_helpers_cfg = std::atoi(e) != 0 ? TRK_NHELP : 0;
         if (const char* e = std::getenv("FNN_TRACK_GROUP")) { int v = std::atoi(e); if (v >= 2 && v <= 1024) track_group = v; }
-        if (const char* e = std::getenv("FNN_FUSE")) fuse_events = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FNN_GRAPH")) graph_batches = std::atoi(e) != 0;
         if (const char* e = std::getenv("FNN_TRACK_GRID")) { int v = std::atoi(e); if (v >= 1 && v <= 1024) track_grid = v; }
         // the first-level arrival counters sit at d.ticket + 32 (g + 1), g < ceil(grid / group); word 32 * 65 is TRK_FLAG, 32 * 67
         // TRK_BAD and the array holds 32 * 72 words: at most 64 groups (the two switches are development aids, but an
@@ -3406,7 +3140,7 @@ struct HipBackend {
     // of that launch altogether, so durations and classes cannot get out of step)
     template <class F>
     void timed(int cls, bool on, F&& launch) {
-        hipEvent_t e0 = on && !capturing ? next_event() : nullptr, e1 = e0 ? next_event() : nullptr;
+        hipEvent_t e0 = on ? next_event() : nullptr, e1 = e0 ? next_event() : nullptr;
         if (e0 && !e1) ev_used--;
         if (e0 && e1) {
             ev_kind.push_back((char)cls);
@@ -3414,30 +3148,6 @@ struct HipBackend {
             launch();
             (void)hipEventRecord(e1, stream);
         } else launch();
-    }
-    // Experiment (FNN_GRAPH=1, off by default): a batch of events captured into a hipGraph and launched as one - to see what the
-    // runtime's per-dispatch handling contributes to the kernels' traced durations (the launch parameters differ from batch to batch,
-    // so every batch is captured and instantiated anew: this measures the device side, it is not a way to run faster as it stands).
-    double graph_exec_s = 0.0;
-    int graph_count = 0;
-    bool graph_batches = false, capturing = false;  // (no event records inside a capture: the scans' live timing is off in this mode)
-    int32_t capture_begin() {
-        capturing = HIPOK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        return capturing ? FNN_OK : FNN_EHIP;
-    }
-    int32_t capture_end_launch() {
-        hipGraph_t g = nullptr;
-        hipGraphExec_t ge = nullptr;
-        capturing = false;
-        if (!HIPOK(hipStreamEndCapture(stream, &g))) return FNN_EHIP;
-        bool fine = HIPOK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-        const auto t0 = std::chrono::steady_clock::now();
-        fine = fine && HIPOK(hipGraphLaunch(ge, stream)) && HIPOK(hipStreamSynchronize(stream));
-        graph_exec_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (++graph_count % 64 == 0) std::fprintf(stderr, "[fnn] graphs: %d launched, %.4f s between launch and completion\n", graph_count, graph_exec_s);
-        if (ge) (void)hipGraphExecDestroy(ge);
-        (void)hipGraphDestroy(g);
-        return fine ? FNN_OK : FNN_EHIP;
     }
     int32_t sync() {
         if (!HIPOK(hipStreamSynchronize(stream))) return FNN_EHIP;
@@ -3536,17 +3246,11 @@ struct HipBackend {
         //  device stalls - this and the following such events do nothing - until the host, which
         //  looks at the state every batch, launches an event with a scan)
         const bool has_scan = sched || !screen || !skip_unsched_scans;
-        // a WINDOW event in one launch (k_track with fuse: tracking, decide step and the update; no k_update follows): only launch
-        // sequences without scan kernels, with the row sum deferred, and while every block of 1024 columns finds a tracking workgroup
-        fused_last = fuse_events && d.la && screen && !has_scan && defer_chain;
-        const int fz = fused_last ? (m_bound + BULK_COLS - 1) / BULK_COLS : 0;  // column workgroups of a fused launch
         if (d.la) timed(TC_TRACK, tall, [&]() {
-            track_tag = (track_tag % 0x7FFFFFEu) + 1u;  // (never 0: the JOB word and the plan message start out as 0)
+            track_tag = (track_tag % 0x7FFFFFEu) + 1u;  // (never 0: the JOB word starts out as 0)
             const int fb = (sched || !screen) ? 1 : 0, hs = has_scan ? 1 : 0, tk = ticks ? 1 : 0;
-            if (rx_helpers > 0 && fz) hipLaunchKernelGGL((k_track<true, true>), dim3(track_grid + 1 + TRK_NHELP + fz), dim3(TRK_THREADS), 0, stream, d, fb, fb, hs, track_group, tk, track_tag, fz);
-            else if (rx_helpers > 0) hipLaunchKernelGGL((k_track<true, false>), dim3(track_grid + 1 + TRK_NHELP), dim3(TRK_THREADS), 0, stream, d, fb, fb, hs, track_group, tk, track_tag, 0);
-            else if (fz) hipLaunchKernelGGL((k_track<false, true>), dim3(track_grid + 1 + fz), dim3(TRK_THREADS), 0, stream, d, fb, fb, hs, track_group, tk, track_tag, fz);
-            else hipLaunchKernelGGL((k_track<false, false>), dim3(track_grid + 1), dim3(TRK_THREADS), 0, stream, d, fb, fb, hs, track_group, tk, track_tag, 0);
+            if (rx_helpers > 0) hipLaunchKernelGGL(k_track<true>, dim3(track_grid + 1 + TRK_NHELP), dim3(TRK_THREADS), 0, stream, d, fb, fb, hs, track_group, tk, track_tag);
+            else hipLaunchKernelGGL(k_track<false>, dim3(track_grid + 1), dim3(TRK_THREADS), 0, stream, d, fb, fb, hs, track_group, tk, track_tag);
         });
         int nrecs;
         if (screen && !has_scan) nrecs = 0;  // (a window event: the tail of k_track decides; no decide kernel follows)
@@ -3598,7 +3302,6 @@ struct HipBackend {
             if (rx_helpers > 0) hipLaunchKernelGGL(k_decide<true>, dim3(1 + TRK_NHELP), dim3(CH_T), 0, stream, d, src, nrecs, track_tag);
             else hipLaunchKernelGGL(k_decide<false>, dim3(1), dim3(CH_T), 0, stream, d, src, nrecs, track_tag);
         });
-        if (nrecs == 0 && fused_last) return;  // (the window event's k_track has done the update itself)
         timed(TC_UPDATE, tall, [&]() { hipLaunchKernelGGL(k_update, dim3(g1.x + 1), dim3(256), 0, stream, d, defer_chain ? 1 : 0, ticks ? 1 : 0); });
         if (!defer_chain) timed(TC_OTHER, tall, [&]() { hipLaunchKernelGGL(k_finalize, dim3(1), dim3(CH_T), 0, stream, d); });
     }

@@ -38,9 +38,7 @@ def main():
     for name, env, hkw in [("default", {}, {}), ("windows off", {"FNN_LA_K": "-1"}, {}), ("screening off", {}, {"disable_screen": True}),
                            ("exact rx forced", {}, {"force_exact_rx": True}), ("no deferred chain", {"FNN_NO_DEFER": "1"}, {}),
                            ("default again", {}, {}), ("default, third time", {}, {}),
-                           ("window events as two launches (FNN_FUSE=0)", {"FNN_FUSE": "0"}, {}),
-                           ("fused, ComputeRx helpers off", {"FNN_RX_HELPERS": "0"}, {}),
-                           ("two launches, ComputeRx helpers off", {"FNN_FUSE": "0", "FNN_RX_HELPERS": "0"}, {})]:
+                           ("ComputeRx helpers off", {"FNN_RX_HELPERS": "0"}, {})]:
         try:
             order, st, ev = run(n, dist, seed, env, **hkw)
         except Exception as e:  # noqa: BLE001
