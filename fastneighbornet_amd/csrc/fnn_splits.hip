@@ -31,6 +31,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -212,7 +213,7 @@ __global__ __launch_bounds__(T) void k_vec(VecArgs g) {
 
 // reductions: per-workgroup partials, folded by a second launch (fixed order: reproducible)
 struct Best { double v; int64_t k; };
-enum { RD_DOT = 0, RD_COUNT_NEG, RD_COUNT_LT, RD_COUNT_EQ, RD_MIN_RATIO, RD_MIN_ACTIVE_GRAD, RD_ANY_NEG, RD_MAX_UNMASKED };
+enum { RD_DOT = 0, RD_COUNT_NEG, RD_COUNT_LT, RD_COUNT_EQ, RD_MIN_RATIO, RD_MIN_ACTIVE_GRAD, RD_ANY_NEG, RD_MAX_UNMASKED, RD_COUNT_NONFINITE };
 template <int RD>
 __global__ __launch_bounds__(T) void k_reduce(const double* a, const double* b, const uint8_t* act, double s0, int n, int64_t ld,
                                               double* partial, Best* bpartial, const double* sc) {
@@ -229,6 +230,7 @@ __global__ __launch_bounds__(T) void k_reduce(const double* a, const double* b, 
             else if (RD == RD_COUNT_NEG) acc += a[k] < 0.0 ? 1.0 : 0.0;
             else if (RD == RD_COUNT_LT) acc += (a[k] < 0.0 && a[k] < s0) ? 1.0 : 0.0;
             else if (RD == RD_COUNT_EQ) acc += (a[k] < 0.0 && a[k] == s0) ? 1.0 : 0.0;
+            else if (RD == RD_COUNT_NONFINITE) acc += (fabs(a[k]) <= DBL_MAX) ? 0.0 : 1.0;  // (NaN compares false)
             else if (RD == RD_MIN_RATIO) {  // first minimum of old_x / (old_x - x) over x < 0 (:434-445)
                 if (a[k] < 0.0) {
                     const double xi = b[k] / (b[k] - a[k]);
@@ -1706,6 +1708,10 @@ static int32_t split_weights_impl(const double* D, int32_t n, int64_t ldD, const
     hipLaunchKernelGGL(k_reorder, dim3((unsigned)((n + T - 1) / T), (unsigned)n), dim3(T), 0, S.s, S.Dm, (int64_t)n, S.ord, S.d, n, S.ld);
     S.release(S.Dm);  // (the raw copy has served: its n^2 doubles go back to the pool before the factor is sized)
     S.Dm = nullptr;
+    // A NaN or an infinity among the distances makes every comparison below false: the closed form would be "feasible" and NaN
+    // weights would go back with FNN_OK.  Refuse them before any route is chosen.
+    if (S.reduce_sum<RD_COUNT_NONFINITE>(S.d, nullptr) != 0.0)
+        return fnn::fail(FNN_EINVAL, "fnn_split_weights_f64: the distances contain a NaN or an infinity");
     // the closed form if it is feasible; else from below (block active-set method, exact sub-problems); the reference's own
     // method (from above, conjugate gradients) where the free set is too large for a dense factor AND that route is affordable
     int route = FNN_SW_ROUTE_CLOSED_FORM;

@@ -311,7 +311,11 @@ enum { FNN_SW_GIVEUP_NONE = 0, FNN_SW_GIVEUP_CAPACITY = 1,   /* the free set out
  * reference route stops by its own rule, CG_EPSILON = 1e-8, ~1e-5 short of the optimum, and reports certified = 0 with
  * FNN_OK); FNN_ECAPACITY when the block method's factor cannot hold the free set and n is above the size up to which the
  * reference route is taken automatically (FNN_SW_REFERENCE_MAX_N, default 1024: measured in DESIGN.md section 7).  Before
- * that the block method retries with a factor of four times the capacity, up to what device memory holds (~150 000 splits). */
+ * that the block method retries with a factor of four times the capacity, up to what device memory holds (~150 000 splits).
+ * FNN_EINVAL when one of the n (n - 1) / 2 distances that the ordering selects is a NaN or an infinity (checked on the device
+ * before any route is chosen).  Every threshold of the solver is relative to max|A^T d|, so D -> ldexp(D, k) gives exactly
+ * ldexp(weights, k) on the same route with the same counters while 2|k| + log2(n^4 max|D|^2) < 1000 (the objective is quadratic
+ * in the scale and must stay a normal double). */
 int32_t fnn_split_weights_f64(const double* D, int32_t n, int64_t ld, const int32_t* ordering, int32_t device,
                               double* weights_out, fnn_sw_stats* stats);
 /* The same solve, returning only the weights above `threshold` (the reference's list keeps x[k] > 1e-6, FastNN.java:455-466): pairs

@@ -6,6 +6,7 @@ circular metrics.  GPU part: fnn_split_weights_f64 against the oracle."""
 import numpy as np
 import pytest
 
+from common import kkt_violation
 from oracle import csw_oracle as W
 
 
@@ -74,19 +75,6 @@ def fast_x(n, live):
             x[(2 * n - fi - 3) * fi // 2 + fj - 1] = live[k]
             k += 1
     return x
-
-
-def kkt_violation(D, order, live):
-    """Optimality certificate of min |A x - d|^2, x >= 0, independent of any solver: the largest violation of
-    x >= 0, of g >= 0 on the zero weights and of g = 0 on the positive ones (g = A^T (A x - d)), relative to |A^T d|."""
-    from common import live_to_fast
-    n = D.shape[0]
-    d = W.setup_d(D, order)
-    x = live_to_fast(n, live)
-    g = W.calculate_atx(n, W.calculate_ab(n, x) - d)
-    scale = np.abs(W.calculate_atx(n, d)).max()
-    pos = x > 0
-    return max(float(-x.min()), float(np.abs(g[pos]).max(initial=0.0) / scale), float((-g[~pos]).max(initial=0.0) / scale))
 
 
 @pytest.mark.gpu
