@@ -1306,11 +1306,14 @@ FNN_HD void t_finalize(const Dev& d) {
 // The body below is the control flow, written once: `Env` supplies single-reader loads / single-writer stores (GPU:
 // lane 0 of the control wave + a broadcast; the control values are wave-uniform) and the row minimum itself (GPU: the
 // whole workgroup; CPU emulation: a loop).  The HashMap foundRowMinimums of one call is the per-slot entry
-// {rl_stamp == n_events + 1, rl_val, rl_cnt, rl_list}; a list longer than RL_TIES, or more than RL_MINS mutual pairs,
-// is reported as an error (degenerate inputs only: every list holds the two nodes of a cluster at most otherwise).
+// {rl_stamp == n_events + 1, rl_val, rl_cnt, rl_list}; a list longer than RL_TIES (code 20), or more than RL_MINS mutual
+// pairs (code 22), ends the run with FNN_ECAPACITY.  Rows tie exactly when taxa are identical (k copies of a taxon: k - 1
+// tied row minima, so 18 copies are refused) or the matrix is constant; every list holds the two nodes of a cluster at
+// most otherwise.  The truncated list holds RL_TIES valid rows, so the search goes on safely until the host looks.
 // ---------------------------------------------------------------------------
 constexpr int RL_TIES = 16;
 constexpr int RL_MINS = 64;
+static_assert(RL_TIES <= RL_MINS, "nmin counts at most one pair per entry of ONE list: code 22 is unreachable while this holds");
 constexpr int RL_GMAX = 16;                       // workgroups the row pass of one minimum may be spread over
 constexpr int RL_REC_WORDS = 2 + RL_TIES;         // a workgroup's record: value, (count | tag), RL_TIES (position | slot)
 constexpr int RL_MAIL_WORDS = 32 + RL_GMAX * 32;  // command word (line 0), arrival counter (line 1), records (256 B apart)

@@ -210,8 +210,20 @@ class Engine {
     int32_t pull_state() {
         if (be.d2h(&hst, dev.st, sizeof(State)) != FNN_OK)
             return fail(FNN_EHIP, "state download failed (" + be.err() + ")");
-        if (hst.error) return fail(FNN_ESTATE, "engine reached an unreachable branch, code " + std::to_string(hst.error));
+        if (hst.error) return fail_device_code(hst.error);
         return FNN_OK;
+    }
+    // A non-zero State::error.  Codes 20 and 22 are the fixed capacities of the Relaxed search (fnn_core.h "Relaxed mode": a tie
+    // list holds RL_TIES rows, a step keeps RL_MINS mutual pairs), which valid inputs can exceed; every other code is an
+    // internal-consistency check.
+    int32_t fail_device_code(int32_t code, const std::string& where = "") {
+        if (code == 20 || code == 22)
+            return fail(FNN_ECAPACITY, "Relaxed mode: a row of the selection criterion attains its minimum at more than " + std::to_string(RL_TIES) +
+                                           " rows, and the engine keeps at most " + std::to_string(RL_TIES) + " tied row minima per row (" +
+                                           (code == 20 ? "tie list" : "list of mutual pairs") + " full, device code " + std::to_string(code) + where +
+                                           "). The usual cause is more than " + std::to_string(RL_TIES + 1) +
+                                           " identical taxa, or a constant matrix. -mode Canonical handles this input.");
+        return fail(FNN_ESTATE, "engine reached an unreachable branch, code " + std::to_string(code) + where);
     }
     // Several ranks: an error in ONE rank's device state (codes 12 / 13: an exchange block of another event; any internal-consistency
     // code) must stop EVERY rank at the same host round trip - a rank that stopped alone would leave the others waiting in their next
@@ -244,9 +256,8 @@ class Engine {
         }
         for (int32_t r = 0; r < world; r++)
             if (codes[(size_t)r])
-                return fail(FNN_ESTATE, "engine reached an unreachable branch, code " + std::to_string(codes[(size_t)r]) + " on rank " + std::to_string(r) +
-                                            " (every rank stops here; this is rank " + std::to_string(rank) + ")");
-        if (hst.error) return fail(FNN_ESTATE, "engine reached an unreachable branch, code " + std::to_string(hst.error));
+                return fail_device_code(codes[(size_t)r], " on rank " + std::to_string(r) + " (every rank stops here; this is rank " + std::to_string(rank) + ")");
+        if (hst.error) return fail_device_code(hst.error);
         return FNN_OK;
     }
 

@@ -2007,14 +2007,17 @@ struct RlBlockEnv {
             for (unsigned long long rest = has & ~1ULL; rest; rest &= rest - 1) {
                 const int w = (int)__builtin_ctzll(rest);
                 const int32_t cw = __builtin_amdgcn_readlane(c, w);
-                if (cw > RL_TIES || total + cw > RL_TIES) { total = RL_TIES + 1; break; }
+                // (more ties than a list holds: fill it up from this record - a count of RL_TIES + 1 comes with RL_TIES entries -,
+                //  so that the truncated list of error 20 holds rows and nothing stale; the digest covers whole records only)
+                const int32_t room = RL_TIES - total, take = cw < room ? cw : room;
                 uint64_t e = 0;
-                if (lane < cw) {
+                if (lane < take) {
                     e = ld_sc1(rl_rec(d, w) + 2 + lane);
                     L.tpos[total + lane] = (int32_t)(e >> 32);
                     L.tslot[total + lane] = (int32_t)(uint32_t)e;
                     e *= (uint64_t)(2 * lane + 3);
                 }
+                if (cw > take) { total = RL_TIES + 1; break; }
 #pragma unroll
                 for (int off = 32; off >= 1; off >>= 1) e ^= (uint64_t)__shfl_xor((unsigned long long)e, off, 64);
                 if (rl_h16((e + 1ULL) ^ ((uint64_t)seq << 1)) != (uint32_t)__builtin_amdgcn_readlane((int)th, w)) ok = 0;

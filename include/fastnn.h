@@ -43,7 +43,10 @@ typedef enum fnn_status {
     FNN_ECAPACITY = -6,/* split weights: the optimum has more positive splits than the dense factor of the block method
                           holds (nearly circular distances: O(n^2) splits) and the fall-back - CircularSplitWeights.java's
                           conjugate-gradient route - is not affordable at this size; nothing is returned
-                          (FNN_SW_ALLOW_REFERENCE_ROUTE=1 takes that route anyway) */
+                          (FNN_SW_ALLOW_REFERENCE_ROUTE=1 takes that route anyway).
+                          Relaxed mode (FNN_MODE_RELAXED): a row of the selection criterion has more than 16 tied row minima,
+                          more than the search keeps per row - in practice more than 17 identical taxa, or a constant
+                          matrix; no order is returned, the Canonical mode handles such input */
     FNN_EINEXACT = -7  /* split weights: weights_out IS filled, but the solver's own Kuhn-Tucker check of them exceeds
                           1e-9 of max|A^T d| (fnn_sw_stats.kkt_violation says by how much): not the certified optimum */
 } fnn_status;

@@ -12,6 +12,8 @@ oracle's results for them in the build container) and the GPU tests that replay 
                     criterion only shifts under such pendant lengths, but max |D| grows by 1e6, so the screening slack
                     (screen_delta, proportional to max |D|) outgrows the spread of Q: every screening unit is a candidate
   dup               n/4 distinct treenoise taxa, each present 4 times, permuted: zero distances and identical rows
+  dupk(n, k, ...)   the same with every taxon present k times: identical rows give bit-identical values of the selection
+                    criterion, so every row has k - 1 tied row minima at the first event (the Relaxed mode's tie lists)
 
 Host-generated classes depend on numpy's default_rng stream (PCG64), which is stable across numpy versions.
 """
@@ -100,6 +102,28 @@ def make(n, dist, seed, oracle):
         np.fill_diagonal(D, 0.0)
         return D
     raise ValueError(dist)
+
+
+def dupk(n, k, seed, oracle):
+    """ceil(n / k) distinct treenoise taxa, each present k times (the last one as often as fits), permuted as "dup" is."""
+    t = -(-n // k)
+    T = make(t, "treenoise", seed, oracle)
+    idx = np.random.default_rng(seed + 2000).permutation(np.repeat(np.arange(t), k)[:n])
+    return np.ascontiguousarray(T[np.ix_(idx, idx)])
+
+
+def first_event_ties(D, rows=None):
+    """For each of `rows` (default: all) the indices q != p that attain min_q (n - 2) D[p, q] - S[p] - S[q], the selection
+    criterion of the first event (no clusters yet), as a list of index arrays.  Plain numpy, independent of the engine: the
+    tests use it to assert what their inputs are meant to provoke."""
+    n = D.shape[0]
+    S = D.sum(axis=1)
+    out = []
+    for p in (range(n) if rows is None else rows):
+        q = ((n - 2.0) * D[p] - S[p]) - S
+        q[p] = np.inf
+        out.append(np.nonzero(q == q.min())[0])
+    return out
 
 
 def sha_big(a):
