@@ -60,6 +60,15 @@ class FnnSwStats(C.Structure):
                 ("t_alloc_s", C.c_double), ("reserved2", C.c_int64 * 4)]
 
 
+class FnnBatchStats(C.Structure):
+    _fields_ = [("n_problems", C.c_int64), ("n_lds", C.c_int64), ("n_fallback", C.c_int64), ("n_events", C.c_int64),
+                ("lds_max_n", C.c_int32), ("block_threads", C.c_int32), ("lds_bytes", C.c_int32), ("chunks", C.c_int32),
+                ("t_upload_s", C.c_double), ("t_kernel_s", C.c_double), ("t_total_s", C.c_double), ("reserved", C.c_int64 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 EVENT_DTYPE = np.dtype(
     [("m_before", "<i4"), ("c_before", "<i4"), ("cx_id", "<i4"), ("cy_id", "<i4"),
      ("x_id", "<i4"), ("y_id", "<i4"), ("kind", "<i4"), ("u_id", "<i4"),
@@ -81,11 +90,13 @@ _ip = C.POINTER(C.c_int32)
 
 
 class Api:
-    def __init__(self, lib: C.CDLL, prefix: str):
+    def __init__(self, lib: C.CDLL, prefix: str, engine: bool = True):
         self.lib = lib
         self.prefix = prefix
         f = self._fn
         f("last_error", C.c_char_p, [])
+        if not engine:  # (a library with the batch entry points only: the CPU driver of tests/emu/fnn_batch_emu.cpp)
+            return
         f("create", C.c_int32, [C.c_int32, C.POINTER(FnnOpts), C.POINTER(C.c_void_p)])
         f("destroy", C.c_int32, [C.c_void_p])
         f("set_rows", C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, _dp, C.c_int64])
@@ -118,6 +129,41 @@ class Api:
         if rc < 0:
             raise FnnError(rc, (self.last_error() or b"").decode("utf-8", "replace"))
         return rc
+
+
+_BATCH_ARGS = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(FnnOpts), _ip, C.c_void_p, _ip,
+               C.POINTER(FnnBatchStats)]
+
+
+def bind_batch(a: Api) -> Api:
+    """The batch entry points of include/fastnn.h (many small problems, one workgroup each) on `a`."""
+    a._fn("batch_lds_max_n", C.c_int32, [])
+    a._fn("canonical_order_batch_f64", C.c_int32, _BATCH_ARGS)
+    a._fn("canonical_order_batch_device_f64", C.c_int32, _BATCH_ARGS)
+    return a
+
+
+def run_batch(a: Api, D, n: int, ld: int, stride: int, batch: int, validate: bool = False, device: int = 0,
+              events: bool = False, on_device: bool = False, fill: int = 0):
+    """One batch call; D = address of problem 0 (host memory, or device memory with on_device).  Returns
+    (orders[batch, n + 1], events[batch, n] or None, nevents[batch], stats); on failure FnnError carries the untouched
+    output array as `.orders` (filled with `fill`)."""
+    orders = np.full((batch, n + 1), fill, dtype=np.int32)
+    ev = np.zeros((batch, max(n, 1)), dtype=EVENT_DTYPE) if events else None
+    nev = np.full(batch, fill, dtype=np.int32)
+    opts = FnnOpts()
+    opts.device = device
+    opts.validate = 1 if validate else 0
+    st = FnnBatchStats()
+    fn = a.canonical_order_batch_device_f64 if on_device else a.canonical_order_batch_f64
+    rc = fn(D, n, ld, stride, batch, C.byref(opts), orders.ctypes.data_as(_ip), ev.ctypes.data if events else None,
+            nev.ctypes.data_as(_ip), C.byref(st))
+    try:
+        a.check(rc)
+    except FnnError as e:
+        e.orders = orders
+        raise
+    return orders, ev, nev, st
 
 
 class Handle:

@@ -10,8 +10,10 @@ ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libfastnn_hip.so")
 SRC = os.path.join(HERE, "csrc", "fnn_hip.hip")
 SRC_SPLITS = os.path.join(HERE, "csrc", "fnn_splits.hip")  # circular split weights
-DEPS = [SRC, SRC_SPLITS, os.path.join(HERE, "csrc", "fnn_core.h"), os.path.join(HERE, "csrc", "fnn_engine.h"),
-        os.path.join(HERE, "csrc", "fnn_chain.h"), os.path.join(ROOT, "include", "fastnn.h")]
+SRC_BATCH = os.path.join(HERE, "csrc", "fnn_batch.hip")    # many small problems, one workgroup each
+SOURCES = (SRC, SRC_SPLITS, SRC_BATCH)
+DEPS = [SRC, SRC_SPLITS, SRC_BATCH, os.path.join(HERE, "csrc", "fnn_core.h"), os.path.join(HERE, "csrc", "fnn_engine.h"),
+        os.path.join(HERE, "csrc", "fnn_chain.h"), os.path.join(HERE, "csrc", "fnn_small.h"), os.path.join(ROOT, "include", "fastnn.h")]
 
 # -ffp-contract=off: one rounding per fp64 operation on host and device (parity with Java doubles)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
@@ -93,7 +95,7 @@ def build_host(force: bool = False) -> None:
 
 OBJ_DIR = os.path.join(HERE, "csrc", "build")  # objects are kept (git-ignored): a source is recompiled only when it or a header changed
 HEADERS = [os.path.join(HERE, "csrc", "fnn_core.h"), os.path.join(HERE, "csrc", "fnn_engine.h"), os.path.join(HERE, "csrc", "fnn_chain.h"),
-           os.path.join(ROOT, "include", "fastnn.h")]
+           os.path.join(HERE, "csrc", "fnn_small.h"), os.path.join(ROOT, "include", "fastnn.h")]
 
 
 def toolchain_stamp() -> str:
@@ -115,10 +117,10 @@ def build(force: bool = False) -> str:
     if not (os.path.exists(stamp_file) and open(stamp_file).read().strip() == stamp):
         # Objects without a matching stamp: other flags, another hipcc / ROCm, or a tree from before the stamp existed.  On a
         # box that received prebuilt objects together with their stamp (the GPU box: same image) nothing is recompiled.
-        force = force or any(os.path.exists(os.path.join(OBJ_DIR, os.path.splitext(os.path.basename(x))[0] + ".o")) for x in (SRC, SRC_SPLITS)) and \
+        force = force or any(os.path.exists(os.path.join(OBJ_DIR, os.path.splitext(os.path.basename(x))[0] + ".o")) for x in SOURCES) and \
             os.path.exists(stamp_file)
     todo, objs = [], []
-    for src in (SRC, SRC_SPLITS):
+    for src in SOURCES:
         obj = os.path.join(OBJ_DIR, os.path.splitext(os.path.basename(src))[0] + ".o")
         objs.append(obj)
         newest = max(os.path.getmtime(p) for p in [src] + HEADERS)
@@ -132,7 +134,7 @@ def build(force: bool = False) -> str:
                 d = os.path.join(td, os.path.splitext(os.path.basename(src))[0])
                 os.makedirs(d)
                 shutil.copyfile(compile_one(src, d), obj)
-            with ThreadPoolExecutor(2) as ex:
+            with ThreadPoolExecutor(len(SOURCES)) as ex:
                 list(ex.map(one, todo))
     if todo or not os.path.exists(stamp_file):
         open(stamp_file, "w").write(stamp + "\n")

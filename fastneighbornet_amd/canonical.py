@@ -93,6 +93,55 @@ def canonical_order(D: np.ndarray, device: int = 0, validate: bool = True) -> np
     return order
 
 
+def batch_layout(D: np.ndarray):
+    """(array, ld, stride) for a (B, n, n) fp64 array: the array itself where its strides can be said as a row stride and a
+    problem stride in doubles (ld >= n, stride >= n * ld), a contiguous copy otherwise."""
+    B, n, _ = D.shape
+    s0, s1, s2 = D.strides
+    if D.dtype == np.float64 and D.flags.aligned and D.dtype.isnative and B > 0 and n > 0 and s2 == 8 and s1 % 8 == 0 \
+            and s0 % 8 == 0 and s1 // 8 >= n and s0 // 8 >= n * (s1 // 8):
+        return D, s1 // 8, s0 // 8
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    return D, max(n, 1), max(n * n, 1)
+
+
+def canonical_order_batch(D, validate: bool = False, device: int = 0, events: bool = False):
+    """Many problems of one size in one call (`fnn_canonical_order_batch_f64`): D has shape (B, n, n).  Up to
+    `fnn_batch_lds_max_n()` taxa every problem runs in a workgroup of its own, out of LDS; larger ones go one by one
+    through the one-problem engine.  A numpy array goes to the host entry (its strides are honoured where they amount to a
+    row and a problem stride, otherwise it is copied); a torch.float64 tensor on the GPU goes to the device entry after
+    torch.cuda.synchronize().  Returns orders[B, n + 1], or (orders, events[B, n], nevents[B]) with events=True."""
+    from . import api
+    a = api()
+    on_device = False
+    if hasattr(D, "is_cuda") and hasattr(D, "data_ptr"):  # a torch tensor
+        import torch
+        if D.dim() != 3 or D.shape[1] != D.shape[2]:
+            raise ValueError("D must have shape (B, n, n)")
+        if D.is_cuda:
+            if D.dtype != torch.float64:
+                raise TypeError("a tensor on the GPU must be torch.float64")
+            D = D.contiguous()
+            torch.cuda.synchronize(D.device)  # the batch call is not ordered against the stream that produced D
+            if D.device.index is not None:
+                device = D.device.index
+            B, n = int(D.shape[0]), int(D.shape[1])
+            ptr, ld, stride, on_device, keep = D.data_ptr(), max(n, 1), max(n * n, 1), True, D
+        else:
+            D = D.numpy()
+    if not on_device:
+        D = np.asarray(D)
+        if D.ndim != 3 or D.shape[1] != D.shape[2]:
+            raise ValueError("D must have shape (B, n, n)")
+        B, n = D.shape[0], D.shape[1]
+        keep, ld, stride = batch_layout(D)
+        ptr = keep.ctypes.data
+    orders, ev, nev, _ = _capi.run_batch(a, ptr, n, ld, stride, B, validate=validate, device=device, events=events,
+                                         on_device=on_device)
+    del keep
+    return (orders, ev, nev) if events else orders
+
+
 def split_weights(D: np.ndarray, ordering: np.ndarray, device: int = 0, allow_inexact: bool = False):
     """Non-negative least-squares weights of the circular splits of `ordering` over
     `fnn_split_weights_f64` (the optimum the reference's live path computes, FastNN.java:401-454, in its

@@ -1,0 +1,190 @@
+// fnn_batch.hip -- many small problems in one call: k_small runs one whole Canonical Neighbor-Net problem per workgroup
+// out of LDS (the phase bodies and the host side of the call are fnn_small.h).
+//
+// The kernel is a thin wrapper: it carves the dynamic LDS into the view, loads the matrix and hands the phases to
+// small_problem() with an executor whose barrier is __syncthreads().  No cross-workgroup communication, no atomics on the
+// event path, vector stores and plain C++ only.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <string>
+#include <vector>
+
+#include "fnn_small.h"
+
+namespace fnn {
+
+struct GpuExec {
+    template <class F>
+    __device__ __forceinline__ void all(F f) {
+        f((int)threadIdx.x, (int)blockDim.x);
+        __syncthreads();
+    }
+    // the scan's minimum under the total order (Q, i, j): DPP-free wave reduction by shuffles, one record per wave in LDS
+    __device__ __forceinline__ void scan(const SmallView& V, int32_t m, int32_t c) {
+        SmallCand b = small_scan_thread((int)threadIdx.x, (int)blockDim.x, V, m, c);
+        for (int off = 32; off > 0; off >>= 1) {
+            SmallCand o;
+            o.q = __shfl_down(b.q, off);
+            o.i = __shfl_down(b.i, off);
+            o.j = __shfl_down(b.j, off);
+            if (small_before(o, b)) b = o;
+        }
+        if ((threadIdx.x & 63) == 0) V.wred[threadIdx.x >> 6] = b;
+        __syncthreads();
+    }
+};
+
+// grid: one workgroup per problem of the chunk; dynamic LDS: small_layout(n).bytes
+__global__ __launch_bounds__(1024) void k_small(const double* __restrict__ D, int32_t n, int64_t ld, int64_t stride, int32_t vec,
+                                                int32_t* __restrict__ meta, Agg3Rec* __restrict__ log, Event* __restrict__ ev) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char small_lds[];
+    const SmallView V = small_view(small_lds, n);
+    const int64_t b = blockIdx.x;
+    small_load((int)threadIdx.x, (int)blockDim.x, V, D + b * stride, ld, vec);  // (the first phase's barrier covers the load)
+    GpuExec ex;
+    small_problem(ex, V, ev ? ev + b * n : nullptr, meta + b * SMALL_META_INTS, log + b * n);
+}
+
+// the lowest index of a problem whose matrix fails the check, through atomicMin on one word
+__global__ __launch_bounds__(256) void k_small_validate(const double* __restrict__ D, int32_t n, int64_t ld, int64_t stride, int32_t* first_bad) {
+    const int64_t b = blockIdx.x;
+    if (small_validate_thread((int)threadIdx.x, (int)blockDim.x, D + b * stride, n, ld)) atomicMin(first_bad, (int32_t)blockIdx.x);
+}
+
+struct SmallHipBackend {
+    std::vector<void*> bufs;
+    hipStream_t stream = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    std::string last;
+    int32_t* d_bad = nullptr;
+    int prev_device = -1;  // the caller's current device, restored when the call ends
+
+    ~SmallHipBackend() {
+        for (void* p : bufs) (void)hipFree(p);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (stream) (void)hipStreamDestroy(stream);
+        if (prev_device >= 0) (void)hipSetDevice(prev_device);
+    }
+    const std::string& err() const { return last; }
+    bool ok(hipError_t e, const char* what) {
+        if (e == hipSuccess) return true;
+        last = std::string(what) + ": " + hipGetErrorString(e);
+        return false;
+    }
+    int32_t open(int32_t device) {
+        int cnt = 0;
+        if (!ok(hipGetDeviceCount(&cnt), "hipGetDeviceCount")) return FNN_EHIP;
+        if (device < 0 || device >= cnt) { last = "no HIP device " + std::to_string(device) + " (there is no CPU fallback)"; return FNN_EHIP; }
+        int cur = -1;
+        if (hipGetDevice(&cur) == hipSuccess && cur != device) prev_device = cur;
+        if (!ok(hipSetDevice(device), "hipSetDevice") || !ok(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "hipStreamCreate") ||
+            !ok(hipEventCreate(&e0), "hipEventCreate") || !ok(hipEventCreate(&e1), "hipEventCreate"))
+            return FNN_EHIP;
+        return FNN_OK;
+    }
+    void* alloc(size_t bytes) {
+        void* p = nullptr;
+        if (!ok(hipMalloc(&p, bytes ? bytes : 1), "hipMalloc")) return nullptr;
+        bufs.push_back(p);
+        return p;
+    }
+    int32_t h2d(void* dst, const void* src, size_t bytes) {
+        return ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream), "hipMemcpy") && ok(hipStreamSynchronize(stream), "upload") ? FNN_OK : FNN_EHIP;
+    }
+    int32_t d2h(void* dst, const void* src, size_t bytes) {
+        return ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream), "hipMemcpy") && ok(hipStreamSynchronize(stream), "download") ? FNN_OK : FNN_EHIP;
+    }
+    int32_t validate(const double* dD, int32_t n, int64_t ld, int64_t stride, int64_t cnt, int64_t* bad) {
+        if (!d_bad && !(d_bad = (int32_t*)alloc(sizeof(int32_t)))) return FNN_EHIP;
+        int32_t h = INT_MAX;
+        if (h2d(d_bad, &h, sizeof(h)) != FNN_OK) return FNN_EHIP;
+        hipLaunchKernelGGL(k_small_validate, dim3((unsigned)cnt), dim3(256), 0, stream, dD, n, ld, stride, d_bad);
+        if (!ok(hipGetLastError(), "k_small_validate")) return FNN_EHIP;
+        if (d2h(&h, d_bad, sizeof(h)) != FNN_OK) return FNN_EHIP;
+        *bad = h == INT_MAX ? -1 : h;
+        return FNN_OK;
+    }
+    int32_t run(const double* dD, int32_t n, int64_t ld, int64_t stride, int64_t cnt, int32_t threads, int32_t lds_bytes,
+                int32_t* d_meta, Agg3Rec* d_log, Event* d_ev, double* t_kernel_s) {
+        // more than 64 KiB of dynamic LDS has to be asked for
+        if (!ok(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_small), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
+                "hipFuncSetAttribute"))
+            return FNN_EHIP;
+        const int32_t vec = (ld == n && stride % 2 == 0 && reinterpret_cast<uintptr_t>(dD) % 16 == 0) ? 1 : 0;
+        if (!ok(hipEventRecord(e0, stream), "hipEventRecord")) return FNN_EHIP;
+        hipLaunchKernelGGL(k_small, dim3((unsigned)cnt), dim3((unsigned)threads), (size_t)lds_bytes, stream, dD, n, ld, stride, vec, d_meta, d_log, d_ev);
+        if (!ok(hipGetLastError(), "k_small launch")) return FNN_EHIP;
+        if (!ok(hipEventRecord(e1, stream), "hipEventRecord") || !ok(hipEventSynchronize(e1), "k_small")) return FNN_EHIP;
+        float ms = 0.f;
+        if (!ok(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime")) return FNN_EHIP;
+        *t_kernel_s = (double)ms * 1e-3;
+        return FNN_OK;
+    }
+    // n above the LDS limit: the one-problem engine, one handle for the whole call
+    int32_t fallback(const std::string& W, const double* D, bool on_device, int32_t n, int64_t ld, int64_t stride, int64_t batch,
+                     const fnn_opts& opts, int32_t* orders, fnn_event* events, int32_t* nev, fnn_batch_stats& st) {
+        fnn_opts o = opts;
+        if (events) o.record_events = 1;
+        fnn_handle* h = nullptr;
+        int32_t rc = fnn_create(n, &o, &h);
+        if (rc != FNN_OK) return rc;
+        for (int64_t b = 0; b < batch && rc == FNN_OK; b++) {
+            fnn_stats fs;
+            rc = on_device ? fnn_set_matrix_device(h, D + b * stride, ld) : fnn_set_rows(h, 0, n, D + b * stride, ld);
+            if (rc == FNN_OK) rc = fnn_run(h, orders + b * (n + 1), &fs);
+            if (rc != FNN_OK) { g_last_error = W + "problem " + std::to_string(b) + ": " + g_last_error; break; }
+            nev[b] = (int32_t)fs.n_events;
+            st.n_events += fs.n_events;
+            if (events) {
+                std::memset(events + b * n, 0, sizeof(fnn_event) * (size_t)n);
+                const int64_t got = fnn_get_events(h, events + b * n, n);
+                if (got < 0 || got != fs.n_events) {
+                    rc = got < 0 ? (int32_t)got : FNN_ESTATE;
+                    g_last_error = W + "problem " + std::to_string(b) + ": the engine returned " + std::to_string(got) + " events for a run of " +
+                                   std::to_string(fs.n_events);
+                    break;
+                }
+            }
+            st.n_fallback++;
+        }
+        const std::string keep = g_last_error;
+        fnn_destroy(h);
+        g_last_error = keep;
+        return rc;
+    }
+};
+
+}  // namespace fnn
+
+#define FNN_BATCH_TRY(body)                                                   \
+    try {                                                                     \
+        body                                                                  \
+    } catch (const std::bad_alloc&) {                                         \
+        return fnn::fail(FNN_ENOMEM, "out of host memory");                   \
+    } catch (const std::exception& e) {                                       \
+        return fnn::fail(FNN_ESTATE, std::string("exception: ") + e.what()); \
+    }
+
+extern "C" {
+
+int32_t fnn_batch_lds_max_n(void) { return fnn::SMALL_LDS_MAX_N; }
+
+int32_t fnn_canonical_order_batch_f64(const double* D, int32_t n, int64_t ld, int64_t stride, int64_t batch, const fnn_opts* opts,
+                                      int32_t* orders_out, fnn_event* events_out, int32_t* nevents_out, fnn_batch_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::SmallHipBackend be;
+        return fnn::small_batch(be, "fnn_canonical_order_batch_f64", D, false, n, ld, stride, batch, opts, orders_out, events_out, nevents_out, stats);
+    )
+}
+
+int32_t fnn_canonical_order_batch_device_f64(const double* d_D, int32_t n, int64_t ld, int64_t stride, int64_t batch, const fnn_opts* opts,
+                                             int32_t* orders_out, fnn_event* events_out, int32_t* nevents_out, fnn_batch_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::SmallHipBackend be;
+        return fnn::small_batch(be, "fnn_canonical_order_batch_device_f64", d_D, true, n, ld, stride, batch, opts, orders_out, events_out, nevents_out, stats);
+    )
+}
+
+}  // extern "C"

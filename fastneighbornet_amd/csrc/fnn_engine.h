@@ -38,6 +38,58 @@ inline int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 // workgroups that may write a pair of partial sums into Dev::upart (k_update's grid)
 inline size_t upart_capacity(int32_t n) { size_t g = (size_t)(n > 0 ? n : 1) / 256 + 2; return g < 64 ? 64 : g; }
 
+// expandNodes (NetMakerOriginal.java:246-325) from a merge log: `log` holds one record per agg3way call in the order of the
+// calls, `last3` the ids of the nodes at reference positions 0, 1, 2 when the loop ended, num_nodes the ids issued.  Shared by
+// the one-problem engine and the batched small-problem path (fnn_small.h).  Returns NULL, or what is wrong with the log.
+inline const char* expand_merge_log(int32_t n, int32_t num_nodes, const Agg3Rec* log, size_t nlog, const int32_t last3[3],
+                                    int32_t* ordering) {
+    // ids run up to num_nodes; index 0 unused
+    size_t N = (size_t)num_nodes + 1;
+    std::vector<int32_t> next(N, 0), prev(N, 0), ch1(N, 0), ch2(N, 0), nbr(N, 0);
+    for (size_t k = 0; k < nlog; k++) {
+        const Agg3Rec& r = log[k];
+        int32_t u = r.u_id, v = r.u_id + 1;
+        if (u <= 0 || (size_t)v >= N) return "corrupt merge log";
+        ch1[(size_t)u] = r.x_id; ch2[(size_t)u] = r.y_id;  // :610-611
+        ch1[(size_t)v] = r.y_id; ch2[(size_t)v] = r.z_id;  // :615-616
+        nbr[(size_t)u] = v; nbr[(size_t)v] = u;            // :647-648
+    }
+    int32_t x = last3[0], y = last3[1], z = last3[2];
+    next[(size_t)x] = y; next[(size_t)y] = z; next[(size_t)z] = x;
+    prev[(size_t)x] = z; prev[(size_t)y] = x; prev[(size_t)z] = y;
+    for (size_t k = nlog; k-- > 0;) {  // while (!amalgs.empty()) pop
+        int32_t u = log[k].u_id;
+        int32_t v = nbr[(size_t)u];
+        x = ch1[(size_t)u]; y = ch2[(size_t)u]; z = ch2[(size_t)v];
+        if (v != next[(size_t)u]) {
+            int32_t t = u; u = v; v = t;
+            t = x; x = z; z = t;
+        }
+        prev[(size_t)x] = prev[(size_t)u];
+        next[(size_t)prev[(size_t)x]] = x;
+        next[(size_t)x] = y;
+        prev[(size_t)y] = x;
+        next[(size_t)y] = z;
+        prev[(size_t)z] = y;
+        next[(size_t)z] = next[(size_t)v];
+        prev[(size_t)next[(size_t)z]] = z;
+    }
+    int64_t guard = 0;
+    while (x != 1) {
+        x = next[(size_t)x];
+        if (++guard > (int64_t)N) return "ring does not contain taxon 1";
+    }
+    int32_t a = x, t = 0;
+    ordering[0] = 0;
+    do {
+        if (t >= n) return "ring longer than ntax";
+        ordering[++t] = a;
+        a = next[(size_t)a];
+    } while (a != x);
+    if (t != n) return "ring shorter than ntax";
+    return nullptr;
+}
+
 template <class B>
 class Engine {
   public:
@@ -585,50 +637,8 @@ class Engine {
     }
 
     int32_t expand(int32_t* ordering) {
-        // ids run up to num_nodes; index 0 unused
-        size_t N = (size_t)hst.num_nodes + 1;
-        std::vector<int32_t> next(N, 0), prev(N, 0), ch1(N, 0), ch2(N, 0), nbr(N, 0);
-        for (const Agg3Rec& r : agglog) {
-            int32_t u = r.u_id, v = r.u_id + 1;
-            if (u <= 0 || (size_t)v >= N) return fail(FNN_ESTATE, "fnn_finish: corrupt merge log");
-            ch1[(size_t)u] = r.x_id; ch2[(size_t)u] = r.y_id;  // :610-611
-            ch1[(size_t)v] = r.y_id; ch2[(size_t)v] = r.z_id;  // :615-616
-            nbr[(size_t)u] = v; nbr[(size_t)v] = u;            // :647-648
-        }
-        int32_t x = last3[0], y = last3[1], z = last3[2];
-        next[(size_t)x] = y; next[(size_t)y] = z; next[(size_t)z] = x;
-        prev[(size_t)x] = z; prev[(size_t)y] = x; prev[(size_t)z] = y;
-        for (size_t k = agglog.size(); k-- > 0;) {  // while (!amalgs.empty()) pop
-            int32_t u = agglog[k].u_id;
-            int32_t v = nbr[(size_t)u];
-            x = ch1[(size_t)u]; y = ch2[(size_t)u]; z = ch2[(size_t)v];
-            if (v != next[(size_t)u]) {
-                int32_t t = u; u = v; v = t;
-                t = x; x = z; z = t;
-            }
-            prev[(size_t)x] = prev[(size_t)u];
-            next[(size_t)prev[(size_t)x]] = x;
-            next[(size_t)x] = y;
-            prev[(size_t)y] = x;
-            next[(size_t)y] = z;
-            prev[(size_t)z] = y;
-            next[(size_t)z] = next[(size_t)v];
-            prev[(size_t)next[(size_t)z]] = z;
-        }
-        int64_t guard = 0;
-        while (x != 1) {
-            x = next[(size_t)x];
-            if (++guard > (int64_t)N) return fail(FNN_ESTATE, "fnn_finish: ring does not contain taxon 1");
-        }
-        int32_t a = x, t = 0;
-        ordering[0] = 0;
-        do {
-            if (t >= n) return fail(FNN_ESTATE, "fnn_finish: ring longer than ntax");
-            ordering[++t] = a;
-            a = next[(size_t)a];
-        } while (a != x);
-        if (t != n) return fail(FNN_ESTATE, "fnn_finish: ring shorter than ntax");
-        return FNN_OK;
+        const char* why = expand_merge_log(n, hst.num_nodes, agglog.data(), agglog.size(), last3, ordering);
+        return why ? fail(FNN_ESTATE, std::string("fnn_finish: ") + why) : FNN_OK;
     }
 
     int32_t run(int32_t* order_out, fnn_stats* out) {

@@ -235,6 +235,39 @@ int32_t fnn_get_exchange_times(fnn_handle* h, double* ms2, int64_t* launches2);
 int32_t fnn_canonical_order_f64(const double* D, int32_t n, int64_t ld, const fnn_opts* opts,
                                 int32_t* order_out, fnn_stats* stats);
 
+/* ---- many small problems: one call, one workgroup per problem ------------------------------------
+ * `batch` Canonical runs of the same size n in one call (bootstrap replicates, per-gene matrices, sliding windows).  Problem b
+ * is the n x n matrix at D + b * stride with row stride ld doubles (ld >= n, stride >= n * ld; padding is never read).
+ * For 4 <= n <= fnn_batch_lds_max_n() one kernel launch per chunk runs every problem of the chunk in its own workgroup,
+ * entirely out of LDS: same arithmetic contract as above, so every order, every event and every scan
+ * minimum is what fnn_canonical_order_f64 gives for that matrix.  Larger n goes, problem by problem, through one fnn_handle that
+ * the call creates once (n_fallback counts them); n <= 3 gives identities without touching the device; batch == 0 is FNN_OK.
+ * opts: device and validate as for fnn_create - with validate set, the first problem (lowest index) whose matrix is not
+ * symmetric, not finite or has a non-zero diagonal fails the whole call with FNN_EINVAL and is named in fnn_last_error();
+ * mode FNN_MODE_RELAXED is accepted (it equals Canonical up to 1024 taxa); the events are recorded when events_out is given
+ * (opts->record_events, which tells a handle to KEEP a trajectory for fnn_get_events, has no handle to act on here: the
+ * array is the request; in the fallback the call sets it itself when events_out is given).  A problem whose kernel reached a branch that cannot be reached fails the call
+ * with FNN_EHIP, named likewise.  Whatever fails, the output arrays are untouched: they are written when all problems are done.
+ * orders_out: batch x (n + 1), each row as fnn_run's; events_out: NULL or batch x n records, row b holding nevents_out[b] events
+ * (zero-filled behind them); nevents_out: NULL or batch.  The matrices travel in chunks of at most 2 GiB (FNN_BATCH_CHUNK=<problems>
+ * overrides the chunk size, for tests; FNN_BATCH_THREADS=256|512|1024 overrides the workgroup size chosen from n, for
+ * tools/batch_perf.py).  The call runs on opts->device and leaves the caller's current HIP device as it found it.  The device variant reads D from device memory in place; like fnn_set_matrix_device it
+ * is not ordered against the stream that produced D: synchronise the producer first. */
+typedef struct fnn_batch_stats {
+    int64_t n_problems, n_lds, n_fallback, n_events;   /* problems run in LDS / through the one-problem engine; events over all */
+    int32_t lds_max_n, block_threads, lds_bytes, chunks;
+    double  t_upload_s, t_kernel_s, t_total_s;
+    int64_t reserved[4];
+} fnn_batch_stats;
+int32_t fnn_batch_lds_max_n(void);
+int32_t fnn_canonical_order_batch_f64(const double* D, int32_t n, int64_t ld, int64_t stride, int64_t batch,
+                                      const fnn_opts* opts, int32_t* orders_out /* batch x (n+1) */,
+                                      fnn_event* events_out /* NULL or batch x n */, int32_t* nevents_out /* NULL or batch */,
+                                      fnn_batch_stats* stats /* may be NULL */);
+int32_t fnn_canonical_order_batch_device_f64(const double* d_D, int32_t n, int64_t ld, int64_t stride, int64_t batch,
+                                             const fnn_opts* opts, int32_t* orders_out, fnn_event* events_out,
+                                             int32_t* nevents_out, fnn_batch_stats* stats);
+
 /* ---- several GPUs of one node (one process per GPU): ONE problem on all ranks -----------------
  * Every rank holds the whole matrix (8 GiB at n = 32768, 3 % of an MI355X) and runs the whole event chain
  * itself (the ranks stay in step because every decision is a deterministic function of identical state), so no
