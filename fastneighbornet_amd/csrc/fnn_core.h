@@ -184,6 +184,7 @@ struct State {
     Tgt tgt[MAX_TGT];
 };
 
+struct UpdPre;
 struct Dev {
     double* D;       // slot-ordered matrix, row stride ld
     int64_t ld;
@@ -242,7 +243,15 @@ struct Dev {
     State* st;
     Event* evlog;    // n records (if record_events)
     Agg3Rec* agglog; // n records
+    UpdPre* upre;    // the decide step's record for k_update: packed plan + prefetched involved block (at the END of Dev: see rl_mail).
+                     // It lies right behind the TICKET_WORDS words of `ticket`, in the same allocation: k_track and k_decide reach it
+                     // through `ticket` (upre_behind_ticket) - one more kernel-argument pointer live across k_track costs it a spilled
+                     // vector register
 };
+constexpr int TICKET_WORDS = 32 * 72;
+static_assert(TICKET_WORDS * sizeof(uint32_t) % 128 == 0, "UpdPre (alignas(128)) starts where the ticket words end");
+// (the ONE place that knows where the record lies: Engine::create sets Dev::upre from it)
+FNN_HD UpdPre* upre_behind_ticket(const Dev& d) { return reinterpret_cast<UpdPre*>(d.ticket + TICKET_WORDS); }
 
 // Chain buffers (addends of the sequential sums, indexed by reference position e) are
 // stored chunk-interleaved: the chain kernel gives thread t of a 1024-thread workgroup the
@@ -1804,6 +1813,84 @@ FNN_HD PlanView plan_view(const State& st, Uni uni) {  // uni(x): x as a wave-un
     return v;
 }
 struct UniId { FNN_HD int32_t operator()(int32_t x) const { return x; } };
+
+// The same plan as a record in memory, written ONCE per event by the decide step (fnn_hip.hip: build_targets_wave, lane-parallel)
+// instead of being decoded from the control block by every wave of every column workgroup of the update: operands are already
+// indices into S.  upd_plan_pack / upd_plan_view are the generic forms (the tests check view(pack(st)) == plan_view(st)).
+struct UpdPlan {
+    int64_t event;  // State::n_events when the plan was made
+    int32_t u_id;   // ... and the id of the node the event creates (State::cur.u_id): the tag the update compares, see k_update
+    int32_t m_old, P_old, ev_finish, nS, ntgt;
+    int32_t tU, tV, ix, ixn, iy, iyn, pad[2];
+    int32_t S[MAX_S];
+    int32_t tdst[MAX_TGT], tkind[MAX_TGT], ta[MAX_TGT], tb[MAX_TGT], tc[MAX_TGT], td[MAX_TGT];
+};
+static_assert(sizeof(UpdPlan) == 4 * (16 + MAX_S + 6 * MAX_TGT), "UpdPlan is read as whole dwords");
+FNN_HD int32_t upd_plan_index(const State& st, int32_t slot) {  // index of an involved slot in S (-1: none)
+    if (slot < 0) return -1;
+    for (int i = 0; i < MAX_S && i < st.nS; i++) if (st.S[i] == slot) return i;  // (the slots of S are distinct)
+    return -1;
+}
+FNN_HD UpdPlan upd_plan_pack(const State& st) {
+    UpdPlan p;
+    p.event = st.n_events; p.u_id = st.cur.u_id;
+    p.m_old = st.m_old; p.P_old = st.P_old; p.ev_finish = st.ev_finish; p.nS = st.nS; p.ntgt = st.ntgt;
+    p.tU = st.tU; p.tV = st.tV; p.pad[0] = p.pad[1] = 0;
+    const int32_t twoP = 2 * st.P_old;
+    p.ix = upd_plan_index(st, st.xs); p.ixn = st.xs < twoP ? upd_plan_index(st, st.xs ^ 1) : -1;
+    p.iy = upd_plan_index(st, st.ys); p.iyn = st.ys < twoP ? upd_plan_index(st, st.ys ^ 1) : -1;
+    for (int i = 0; i < MAX_S; i++) p.S[i] = st.S[i];
+    for (int i = 0; i < MAX_TGT; i++) {
+        const Tgt& t = st.tgt[i];
+        p.tdst[i] = t.dst; p.tkind[i] = t.kind;
+        p.ta[i] = upd_plan_index(st, t.a); p.tb[i] = upd_plan_index(st, t.b);
+        p.tc[i] = upd_plan_index(st, t.c); p.td[i] = upd_plan_index(st, t.d);
+    }
+    return p;
+}
+FNN_HD PlanView upd_plan_view(const UpdPlan& p) {
+    PlanView v;
+    v.m_old = p.m_old; v.P_old = p.P_old; v.ev_finish = p.ev_finish; v.nS = p.nS; v.ntgt = p.ntgt; v.tU = p.tU; v.tV = p.tV;
+    v.ix = p.ix; v.ixn = p.ixn; v.iy = p.iy; v.iyn = p.iyn;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < MAX_S; i++) v.S[i] = p.S[i];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < MAX_TGT; i++) {
+        v.tdst[i] = p.tdst[i]; v.tkind[i] = p.tkind[i];
+        v.ta[i] = p.ta[i]; v.tb[i] = p.tb[i]; v.tc[i] = p.tc[i]; v.td[i] = p.td[i];
+    }
+    return v;
+}
+// Dev::upre: what the decide step leaves for the update besides the control block.  Every part that another writer owns sits
+// on 128-byte lines of its own (no address is written by two workgroups of one launch with plain stores):
+//   plan                  the deciding workgroup's wave 0, read by the column workgroups of k_update
+//   event .. tl           the involved block, prefetched by the same wave beside the symbolic replay: blk[i * MAX_S + j] =
+//                         D[S[i]][S[j]], sxl[i] = Sx[S[i]], tl[i] = T[S[i]] as special_block_load would read them.  Bit i of
+//                         `mask`: S[i] is a node of the cluster whose exact row sum the chain workgroup of the SAME k_track launch
+//                         is still computing - sxl[i] is not valid, the update takes `usx` instead
+//   usx                   the chain workgroup's result (chain_workgroup), beside Sx[chain_U], Sx[chain_U + 1]
+//   pD .. pld             the host, once per run
+//   cnt                   k_update's workgroup of the involved slots: {events that consumed a record, ... with a non-zero mask,
+//                         records refused as stale, reserved} (fnn_debug_update_pre)
+struct UpdPre {
+    alignas(128) UpdPlan plan;
+    alignas(128) int64_t event;
+    int32_t u_id, mask;
+    alignas(128) double blk[MAX_S * MAX_S];
+    double sxl[MAX_S], tl[MAX_S];
+    alignas(128) double usx;
+    alignas(128) int64_t cnt[4];
+    // where the prefetch reads: Dev::D, Sx, T and ld once more, written by the host (Engine::begin).  The deciding workgroup
+    // takes them from here, through `ticket`: as kernel arguments they would stay live across all of k_track for the tail's sake
+    alignas(128) const double* pD;
+    const double* pSx;
+    const double* pT;
+    int64_t pld;
+};
 
 // the value of recipe t at the column whose involved-row entries R(i) returns (i: index into S)
 template <class RowVal>

@@ -162,7 +162,7 @@ class Engine {
             !(dev.cstamp = (int32_t*)be.alloc(sizeof(int32_t) * (3 * nn + 8))) ||
             !(dev.tpairs = (int32_t*)be.alloc(sizeof(int32_t) * LA_REC_INTS * LA_PCAP)) ||
             !(dev.fresh = (int32_t*)be.alloc(sizeof(int32_t) * 3 * LA_KMAX)) ||
-            !(dev.ticket = (uint32_t*)be.alloc(sizeof(uint32_t) * 32 * 72)) ||
+            !(dev.ticket = (uint32_t*)be.alloc(sizeof(uint32_t) * TICKET_WORDS + sizeof(UpdPre))) ||
             !(dev.lacnt = (int32_t*)be.alloc(256)) ||
             !(dev.ticks = (int64_t*)be.alloc(sizeof(int64_t) * TICK_WORDS)) ||
             !(dev.lalog = (double*)be.alloc(sizeof(double) * 5 * LA_LOGCAP)) ||
@@ -181,6 +181,7 @@ class Engine {
             !(dev.evlog = (Event*)be.alloc(sizeof(Event) * (nn + 8))) ||
             !(dev.agglog = (Agg3Rec*)be.alloc(sizeof(Agg3Rec) * (nn + 8))))
             return fail(FNN_ENOMEM, "fnn_create: device allocation failed (" + be.err() + ")");
+        dev.upre = upre_behind_ticket(dev);
         dev.H = nullptr;
         if (!opts.disable_screen && !relaxed() && n >= be.screen_min_n()) {  // (Relaxed mode: no windows, plain scans at the end)
             if (!(dev.H = (uint16_t*)be.alloc(sizeof(uint16_t) * (size_t)nrows * (size_t)ldh)))
@@ -267,7 +268,8 @@ class Engine {
     }
     // A non-zero State::error.  Codes 20 and 22 are the fixed capacities of the Relaxed search (fnn_core.h "Relaxed mode": a tie
     // list holds RL_TIES rows, a step keeps RL_MINS mutual pairs), which valid inputs can exceed; every other code is an
-    // internal-consistency check.
+    // internal-consistency check (the newest: 15, k_update met a decide-step record of another event than the control block's -
+    // fnn_core.h: UpdPre - and applied nothing; fnn_debug_update_pre counts them).
     int32_t fail_device_code(int32_t code, const std::string& where = "") {
         if (code == 20 || code == 22)
             return fail(FNN_ECAPACITY, "Relaxed mode: a row of the selection criterion attains its minimum at more than " + std::to_string(RL_TIES) +
@@ -393,8 +395,15 @@ class Engine {
             return fail(FNN_EHIP, "fnn_begin: state upload failed (" + be.err() + ")");
         if (be.memset(dev.islot, 0xFF, sizeof(int32_t) * (3 * (size_t)(n > 0 ? n : 1) + 8)) != FNN_OK ||
             be.memset(dev.cstamp, 0, sizeof(int32_t) * (3 * (size_t)(n > 0 ? n : 1) + 8)) != FNN_OK ||
-            be.memset(dev.ticket, 0, sizeof(uint32_t) * 32 * 72) != FNN_OK || be.memset(dev.lacnt, 0, 256) != FNN_OK || be.memset(dev.ticks, 0, sizeof(int64_t) * TICK_WORDS) != FNN_OK)
+            be.memset(dev.ticket, 0, sizeof(uint32_t) * TICKET_WORDS) != FNN_OK || be.memset(dev.lacnt, 0, 256) != FNN_OK || be.memset(dev.ticks, 0, sizeof(int64_t) * TICK_WORDS) != FNN_OK ||
+            be.memset(dev.upre, 0, sizeof(UpdPre)) != FNN_OK)
             return fail(FNN_EHIP, "fnn_begin: memset failed (" + be.err() + ")");
+        {
+            UpdPre where{};  // (only its last line goes up: the addresses the decide step's prefetch reads from)
+            where.pD = dev.D; where.pSx = dev.Sx; where.pT = dev.T; where.pld = dev.ld;
+            if (be.h2d(&dev.upre->pD, &where.pD, sizeof(UpdPre) - offsetof(UpdPre, pD)) != FNN_OK)
+                return fail(FNN_EHIP, "fnn_begin: upload failed (" + be.err() + ")");
+        }
         if (n > 3) {
             // max |D| (error bounds of the screening pass and of the certified 4-candidate choice), the bf16 copy if wanted
             if (be.launch_prep_screen(dev, nrows) != FNN_OK)

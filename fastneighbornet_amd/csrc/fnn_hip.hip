@@ -1332,7 +1332,20 @@ __device__ __forceinline__ double block_chain_sum2(const double* __restrict__ bu
 //     (build_targets_wave: lane i holds involved slot S[i] and its symbolic row; searches are
 //     ballots, the micro-ops run with wave-uniform control through readlane and lane-conditional
 //     moves).  All of it on an LDS copy of the control block that the workgroup copies in and out.
-__device__ __forceinline__ void build_targets_wave(State& st) {
+// Waves 0 and 1 of the deciding workgroup call it; together they leave Dev::upre for the update (fnn_core.h: UpdPre):
+//   * wave 0, after the replay: the plan as the column threads use it (UpdPlan: every operand an index into S, found by compares
+//     against the <= 8 lanes that hold S - once per event instead of once per wave of every column workgroup);
+//   * wave 1, which would otherwise wait at the barrier: the involved block.  It finds S by itself (the same few ballots), issues
+//     the loads of special_block_load and stores them at a fixed address, beside the replay: the update's workgroup of the
+//     involved slots fetches them with its control block instead of in a second, dependent round trip.  (In wave 0, held across
+//     the replay, the two doubles per lane cost k_track a spilled vector register.)  Nothing writes D, Sx or T between this
+//     step and k_update: the rest of this launch writes the control block, tickets and records; the helper workgroups of the
+//     exact ComputeRx sums and rx_fill_thread write chain buffers only; the scan kernels of a window event return at once.  Two
+//     exceptions, both known here: Sx of the cluster whose exact row sum the chain workgroup of this launch is still computing
+//     (pendU, pendU + 1; < 0: none) is not read - its index goes into UpdPre::mask and the update takes UpdPre::usx - and T of
+//     the previous event's new cluster (tpU, tpU + 1) has just been summed by wave 1: taken from tfin, not from memory.
+struct PreSrc { const double *pD, *pSx, *pT; int64_t pld; };  // UpdPre::pD .. pld in the deciding workgroup's LDS
+__device__ __forceinline__ void build_targets_wave(State& st, const Dev& d, const PreSrc& src, const int32_t pendU, const int32_t tpU, const double* tfin) {
     const int lane = threadIdx.x & 63;
     const int nops = __builtin_amdgcn_readfirstlane(st.nops);
     const int U = __builtin_amdgcn_readfirstlane(st.U), m = __builtin_amdgcn_readfirstlane(st.m);
@@ -1358,6 +1371,23 @@ __device__ __forceinline__ void build_targets_wave(State& st) {
             add_slot(__builtin_amdgcn_readlane(opw, 8 * i + 4));
             add_slot(__builtin_amdgcn_readlane(opw, 8 * i + 5));
         }
+    }
+    UpdPre* const up = upre_behind_ticket(d);
+    if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 1) {
+        // the involved block: lane l fetches entry (l / 8, l % 8), lanes 8 i and 8 i + 1 also Sx and T of S[i]
+        const int pi = lane >> 3, pj = lane & 7;
+        const int32_t psi = __shfl(Sl, pi, 64), psj = __shfl(Sl, pj, 64);
+        const bool prow = pi < nS;
+        const bool ppend = prow && pendU >= 0 && (psi == pendU || psi == pendU + 1);
+        const bool ptfin = prow && tpU >= 0 && (psi == tpU || psi == tpU + 1);
+        double pe = 0.0, pa = 0.0;
+        if (prow && pj < nS) pe = src.pD[(int64_t)psi * src.pld + psj];
+        if (prow && pj == 0 && !ppend) pa = src.pSx[psi];
+        if (prow && pj == 1) pa = ptfin ? tfin[psi == tpU ? 0 : 1] : src.pT[psi];
+        up->blk[lane] = pe;
+        if (pj == 0) up->sxl[pi] = pa;
+        if (pj == 1) up->tl[pi] = pa;
+        return;
     }
     struct Sym { int kind, a, b, c, d; };
     int sk = T_COPY, sa = Sl, sb = -1, sc = -1, sd = -1;  // this lane's symbolic row
@@ -1424,6 +1454,38 @@ __device__ __forceinline__ void build_targets_wave(State& st) {
         if (ntgt > MAX_TGT) st.error = 7;
         else if (err) st.error = err;
     }
+    // ---- the record for the update
+    int32_t ia = -1, ib = -1, ic = -1, id = -1;  // this lane's own operands as indices into S
+#pragma unroll
+    for (int j = 0; j < MAX_S; j++) {
+        const int32_t s = __builtin_amdgcn_readlane(Sl, j);  // (>= 0 for j < nS: an absent operand, -1, matches none)
+        if (j < nS) { ia = s == sa ? j : ia; ib = s == sb ? j : ib; ic = s == sc ? j : ic; id = s == sd ? j : id; }
+    }
+    if (keep && pos < MAX_TGT) {
+        up->plan.tdst[pos] = Sl; up->plan.tkind[pos] = sk;
+        up->plan.ta[pos] = ia; up->plan.tb[pos] = ib; up->plan.tc[pos] = ic; up->plan.td[pos] = id;
+    }
+    if (lane < MAX_S) up->plan.S[lane] = Sl;
+    {
+        const int xs = __builtin_amdgcn_readfirstlane(st.xs), ys = __builtin_amdgcn_readfirstlane(st.ys);
+        const int P_old = __builtin_amdgcn_readfirstlane(st.P_old), m_old = __builtin_amdgcn_readfirstlane(st.m_old);
+        auto uidx = [&](int sl) {  // a wave-uniform slot as an index into S
+            const unsigned long long hit = __ballot(lane < nS && Sl == sl);
+            return hit ? (int)__builtin_ctzll(hit) : -1;
+        };
+        const int ix = uidx(xs), ixn = xs < 2 * P_old ? uidx(xs ^ 1) : -1;
+        const int iy = uidx(ys), iyn = ys < 2 * P_old ? uidx(ys ^ 1) : -1;
+        const int32_t pmask = (int32_t)__ballot(lane < nS && pendU >= 0 && (Sl == pendU || Sl == pendU + 1));  // bit i: S[i] awaits its exact row sum
+        if (lane == 0) {
+            UpdPlan& p = up->plan;
+            p.event = st.n_events; p.u_id = st.cur.u_id;
+            p.m_old = m_old; p.P_old = P_old; p.ev_finish = ev_finish; p.nS = nS; p.ntgt = ntgt < MAX_TGT ? ntgt : MAX_TGT;
+            p.tU = um ? __builtin_popcountll(km & ((1ULL << __builtin_ctzll(um)) - 1ULL)) : -1;
+            p.tV = vm ? __builtin_popcountll(km & ((1ULL << __builtin_ctzll(vm)) - 1ULL)) : -1;
+            p.ix = ix; p.ixn = ixn; p.iy = iy; p.iyn = iyn;
+            up->event = st.n_events; up->u_id = st.cur.u_id; up->mask = pmask;
+        }
+    }
 }
 
 
@@ -1472,6 +1534,7 @@ struct DecideLds {
     double quad[16];           // D over {a, a^1, b, b^1} x {a, a^1, b, b^1}
     double tz[4];              // T of a, a^1, b, b^1
     double tfin[2];            // T of the previous event's new cluster, just summed
+    PreSrc src;                // where wave 1 prefetches the involved block from, fetched beside the first round trip
     double rx[4];
     Quad qd;
 };
@@ -1554,7 +1617,7 @@ __device__ __forceinline__ void rx_helper_workgroup(const Dev& d, ChainLds<CH_EP
 
 // HELP: the kernel was launched with the helper workgroups (its own instantiation: the variant without them carries none of
 // that code - inlined into k_track it cost the hot path ten spilled registers and 2 % of the run on inputs without ties)
-template <bool HELP>
+template <bool HELP, bool TAIL>
 __device__ __forceinline__ void decide_step(const Dev& d, DecideLds& S, ChainLds<CH_EPT>& L, Cand best, unsigned jobtag) {
     State& lst = S.lst;
     Dev dl = d;
@@ -1573,6 +1636,7 @@ __device__ __forceinline__ void decide_step(const Dev& d, DecideLds& S, ChainLds
     const bool need = S.need != 0;
     const int32_t m = lst.m, P = lst.P;
     const int32_t tpU = lst.tp_n > 0 ? lst.tp_U : -2;
+    const int32_t pendU = (TAIL && lst.chain_pending) ? lst.chain_U : -1;  // (pick, below, clears chain_pending)
     // ONE round trip: wave 0 fetches the table entries the plan can touch, the 4 x 4 block of the matrix over the two
     // clusters' nodes and their T; wave 1 sums the partial sums of T of the previous event's new cluster
     if (wv == 0) {
@@ -1608,6 +1672,10 @@ __device__ __forceinline__ void decide_step(const Dev& d, DecideLds& S, ChainLds
             }
         }
     } else if (wv == 1) {
+        if (lane == 0) {
+            const UpdPre* const up = upre_behind_ticket(d);
+            S.src.pD = up->pD; S.src.pSx = up->pSx; S.src.pT = up->pT; S.src.pld = up->pld;
+        }
         const int np = lst.tp_n;
         if (np > 0) {
             double tu = 0.0, tv = 0.0;
@@ -1666,7 +1734,7 @@ __device__ __forceinline__ void decide_step(const Dev& d, DecideLds& S, ChainLds
     if (HELP && !want_exact && tid == 0) job_post(d, jobtag, 0u);  // the helpers may leave
     if (!lst.ev_active) return;  // the loop has ended
     if (lst.ev_finish) {         // the special finish: planned inside pick; only the symbolic replay is left
-        if (tid < 64) build_targets_wave(lst);
+        if (tid < 128) build_targets_wave(lst, d, S.src, pendU, tpU, S.tfin);
         __syncthreads();
         return;
     }
@@ -1718,7 +1786,7 @@ __device__ __forceinline__ void decide_step(const Dev& d, DecideLds& S, ChainLds
     }
     __syncthreads();
     DEC_TICK(3);
-    if (tid < 64) build_targets_wave(lst);
+    if (tid < 128) build_targets_wave(lst, d, S.src, pendU, tpU, S.tfin);
     __syncthreads();
     DEC_TICK(4);
     if (tid == 0 && S.tkon) {
@@ -2140,7 +2208,7 @@ __global__ __launch_bounds__(CH_T) void k_decide(Dev d, const Cand* src, int nre
     if (threadIdx.x == 0) S.tkon = 0;
     Cand best = reduce_records(d, src, st->rl_active ? 1 : nrecs, shc);  // (Relaxed mode: the search's one record)
     __syncthreads();
-    decide_step<HELP>(d, S, L, best, jobtag);
+    decide_step<HELP, false>(d, S, L, best, jobtag);  // (the pending row sum, if any, was delivered by an earlier launch)
     __syncthreads();
     if (threadIdx.x == 0) S.lst.rl_active = 0;
     __syncthreads();
@@ -2177,6 +2245,9 @@ __device__ __forceinline__ void chain_workgroup(const Dev& d, ChainLds<CH_EPT>& 
         // SAME launch (the deciding workgroup) waits on that flag before it reads them; every later kernel sees them anyway
         __hip_atomic_store(reinterpret_cast<uint64_t*>(d.Sx + cU), __builtin_bit_cast(uint64_t, usx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(reinterpret_cast<uint64_t*>(d.Sx + cU + 1), __builtin_bit_cast(uint64_t, usx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // ... and once more at a fixed address (a line this workgroup alone writes): the decide step of this launch prefetches
+        // the involved slots' Sx for k_update before this sum is ready, and k_update takes it from here (UpdPre::mask)
+        __hip_atomic_store(reinterpret_cast<uint64_t*>(&upre_behind_ticket(d)->usx), __builtin_bit_cast(uint64_t, usx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __threadfence();
         __hip_atomic_store(d.ticket + TRK_FLAG, evtag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2688,7 +2759,7 @@ __global__ __launch_bounds__(TRK_THREADS) void k_track(Dev d, int force_base, in
     TRK_TICK(6);
     // the window has certified the minimum: Cx / Cy, the 4-candidate choice and the merge plan follow at once
     // (the launch sequence of a window event has no decide kernel); otherwise the event scans (or stalls)
-    if (lst.la_hit) decide_step<HELP>(d, S, L, best, jobtag);
+    if (lst.la_hit) decide_step<HELP, true>(d, S, L, best, jobtag);
     else if (HELP && threadIdx.x == 0) job_post(d, jobtag, 0u);  // (the event scans or stalls: nothing for the helpers)
     TRK_TICK(7);
     if (prof) {
@@ -2712,34 +2783,67 @@ __global__ __launch_bounds__(TRK_THREADS) void k_track(Dev d, int force_base, in
 // after every event.  Returns this lane's addends {row-sum addend, T terms of u, v} of the add phase.
 __global__ __launch_bounds__(256) void k_update(Dev d, int defer, int ticks) {
     __shared__ double shp[4][4];
-    __shared__ State lst;  // every workgroup fetches the control block ONCE, with one coalesced load
+    __shared__ State lst;  // the workgroup of the involved slots fetches the control block ONCE, with one coalesced load
     State* st = d.st;
+    const bool special = blockIdx.x == gridDim.x - 1;
+    // The column workgroups' plan comes ready-made from the decide step (UpdPlan), with three words of the control block.  The
+    // addresses are wave-uniform and the loads stand before everything that may write memory (the clock reads of the diagnostics
+    // count as such for the compiler): scalar loads straight into scalar registers, no trip through LDS, no decoding.
+    const UpdPlan pl = d.upre->plan;
+    const int32_t g_active = st->ev_active, g_stall = st->stall, g_u_id = st->cur.u_id;
     // diagnostic (FNN_TICKS=1): 100 MHz stamps of thread 0 of the special workgroup (slots 0-3) and of bulk workgroup 0 (4-7)
     long long tk0 = 0;
-    const bool prof = ticks != 0 && threadIdx.x == 0 && (blockIdx.x == gridDim.x - 1 || blockIdx.x == 0);
-    const int tkb = blockIdx.x == gridDim.x - 1 ? 0 : 4;
+    const bool prof = ticks != 0 && threadIdx.x == 0 && (special || blockIdx.x == 0);
+    const int tkb = special ? 0 : 4;
 #define UPD_TICK(slot) do { if (prof) { const long long now_ = (long long)wall_clock64(); d.ticks[8 + tkb + (slot)] += now_ - tk0; tk0 = now_; } } while (0)
     if (prof) tk0 = (long long)wall_clock64();
     // (... and, per workgroup, the sums of its start and end stamps over the events: which workgroup ends last, and how much later)
     const long long wg_t0 = (ticks != 0 && threadIdx.x == 0) ? (long long)wall_clock64() : 0;
-    state_in(lst, st);
-    __syncthreads();
-    if (!lst.ev_active || lst.stall) return;
-    UPD_TICK(0);
     double dsum = 0.0, dabs = 0.0, tu = 0.0, tv = 0.0;
-    const bool special = blockIdx.x == gridDim.x - 1;
-    if (special) {
-        // the <= 8 involved slots: their S x S block of the matrix, their row sums and their T are copied to LDS,
-        // the reference's per-node bodies run on the copy in phases (subtract, one per micro-op, add: up to 8
-        // dependent steps at LDS latency), and the block goes back in one sweep.  The control block is worked on
-        // in LDS too (the phases read the plan from it; the last wave closes the event on it) and goes back whole:
-        // the bulk workgroups only read fields that this workgroup does not change.
+    if (!special) {
+        // ONE thread per column (node): bulk_column.  A launch without a decide step (stalled, or the loop has ended) finds the
+        // PREVIOUS event's record: it returns on ev_active / stall as before.  The record's tag is the id of the node its event
+        // creates, compared with the control block's (State::cur.u_id; the event number is in the record too, but the workgroup
+        // of the involved slots advances State::n_events in this very launch): a mismatch applies nothing here - that workgroup
+        // reports it.
+        if (!g_active || g_stall || pl.u_id != g_u_id) return;
+        UPD_TICK(0);
+        const PlanView pv = upd_plan_view(pl);
+        UPD_TICK(1);
+        bulk_column(d, pv, (int32_t)(blockIdx.x * 256 + threadIdx.x), d.chain, dsum, dabs, tu, tv);
+        UPD_TICK(2);
+    } else {
+        // the <= 8 involved slots: their S x S block of the matrix, their row sums and their T come from the decide step's
+        // prefetch (UpdPre: a fixed address, fetched beside the control block), the reference's per-node bodies run on the copy
+        // in LDS in phases (subtract, one per micro-op, add: up to 8 dependent steps at LDS latency), and the block goes back
+        // in one sweep.  The control block is worked on in LDS too (the phases read the plan from it; the last wave closes the
+        // event on it) and goes back whole: the bulk workgroups only read fields that this workgroup does not change.
         __shared__ double blk[MAX_S * MAX_S], sxl[MAX_S], tl[MAX_S];
         __shared__ int32_t berr;
+        UpdPre* const up = d.upre;
+        const int t = (int)threadIdx.x;
+        double pre = 0.0;
+        if (t < MAX_S * MAX_S) pre = up->blk[t];
+        else if (t < MAX_S * MAX_S + MAX_S) pre = up->sxl[t - MAX_S * MAX_S];
+        else if (t < MAX_S * MAX_S + 2 * MAX_S) pre = up->tl[t - MAX_S * MAX_S - MAX_S];
+        const int64_t pevent = up->event;
+        const int32_t pu_id = up->u_id, pmask = up->mask;
+        const double pusx = up->usx;
+        state_in(lst, st);
+        __syncthreads();
+        if (!lst.ev_active || lst.stall) return;
+        if (pevent != lst.n_events || pu_id != lst.cur.u_id) {  // (not expected: an event decided without leaving its record)
+            if (t == 0) { st->error = 15; up->cnt[2] += 1; }
+            return;
+        }
+        UPD_TICK(0);
         Dev dl = d;
         dl.st = &lst;
-        if (threadIdx.x == 0) berr = 0;
-        if (threadIdx.x < MAX_S * MAX_S) special_block_load(dl, blk, sxl, tl, (int32_t)threadIdx.x);
+        if (t == 0) berr = 0;
+        if (t < MAX_S * MAX_S) blk[t] = pre;
+        else if (t < MAX_S * MAX_S + MAX_S) sxl[t - MAX_S * MAX_S] = ((pmask >> (t - MAX_S * MAX_S)) & 1) ? pusx : pre;
+        else if (t < MAX_S * MAX_S + 2 * MAX_S) tl[t - MAX_S * MAX_S - MAX_S] = pre;
+        if (t == 128) { up->cnt[0] += 1; if (pmask) up->cnt[1] += 1; }
         __syncthreads();
         UPD_TICK(1);
         if (threadIdx.x < 64) {  // (the other waves only keep the barriers company)
@@ -2773,12 +2877,6 @@ __global__ __launch_bounds__(256) void k_update(Dev d, int defer, int ticks) {
         }
         __syncthreads();
         state_out(st, lst);
-    } else {
-        // ONE thread per column (node): bulk_column
-        const PlanView pv = plan_view(lst, UniLane{});
-        UPD_TICK(1);
-        bulk_column(d, pv, (int32_t)(blockIdx.x * 256 + threadIdx.x), d.chain, dsum, dabs, tu, tv);
-        UPD_TICK(2);
     }
     // per-workgroup partial sums (tree order): of the new cluster's row-sum addends and their magnitudes (for
     // the next event's sweep while the exact sequential sum is on its way) and of T of its two nodes
@@ -3513,6 +3611,12 @@ int32_t fnn_debug_plan_ticks(fnn_handle* h, int64_t* out4) {
     FNN_NEED(h);
     if (!out4) return fnn::fail(FNN_EINVAL, "fnn_debug_plan_ticks: out4 is NULL");
     if (h->eng.be.d2h(out4, h->eng.dev.ticks + 20, sizeof(int64_t) * 4) != FNN_OK) return FNN_EHIP;
+    return FNN_OK;
+}
+int32_t fnn_debug_update_pre(fnn_handle* h, int64_t* out4) {
+    FNN_NEED(h);
+    if (!out4) return fnn::fail(FNN_EINVAL, "fnn_debug_update_pre: out4 is NULL");
+    if (h->eng.be.sync() != FNN_OK || h->eng.be.d2h(out4, &h->eng.dev.upre->cnt[0], sizeof(int64_t) * 4) != FNN_OK) return FNN_EHIP;
     return FNN_OK;
 }
 int32_t fnn_set_scan_timing(fnn_handle* h, int32_t enable) {

@@ -212,6 +212,10 @@ int32_t fnn_debug_decide_ticks(fnn_handle* h, int64_t* out4);
 /* ... and inside the merge plan (wave 0; all decide steps of the run, k_decide's included): {the <= 4 candidates' values and the choice,
  * the chosen nodes' ids, the slot operations of the merge (swaps / agg3way plans / moves), the window's bookkeeping for the new cluster}. */
 int32_t fnn_debug_plan_ticks(fnn_handle* h, int64_t* out4);
+/* Diagnostic: the record the decide step leaves for k_update (packed plan + prefetched block of the involved slots), counted over
+ * the events since fnn_begin: {events whose update consumed a record, ... of which took the pending exact row sum of the newest
+ * cluster from the chain workgroup's word instead of the prefetch, records refused as stale (expected 0; the run fails), reserved}. */
+int32_t fnn_debug_update_pre(fnn_handle* h, int64_t* out4);
 /* ... and k_update per workgroup: out768[w] = sum over the events of workgroup w's start stamp, out768[256 + w] = of its end stamp,
  * out768[512 + w] = the number of events it took part in (w = 255: the workgroup of the involved slots; bulk workgroups >= 254
  * share slot 254): which workgroup ends last, and by how much. */
