@@ -35,6 +35,20 @@ inline double now_s() {
 }
 
 inline int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+// Environment switches.  env_int: a switch that is set to an integer in [lo, hi] replaces *field, anything else leaves it alone;
+// env_flag: a switch that is set gives *field its truth value ("0": false).  Both say whether they replaced the field.
+inline bool env_int(const char* name, int64_t lo, int64_t hi, int32_t* field) {
+    const char* e = std::getenv(name);
+    const int v = e ? std::atoi(e) : 0;
+    if (!e || v < lo || v > hi) return false;
+    *field = v;
+    return true;
+}
+inline bool env_flag(const char* name, bool* field) {
+    const char* e = std::getenv(name);
+    if (e) *field = std::atoi(e) != 0;
+    return e != nullptr;
+}
 // workgroups that may write a pair of partial sums into Dev::upart (k_update's grid)
 inline size_t upart_capacity(int32_t n) { size_t g = (size_t)(n > 0 ? n : 1) / 256 + 2; return g < 64 ? 64 : g; }
 
@@ -117,6 +131,67 @@ class Engine {
     int fault_error_rank = -1, fault_error_event = -1;  // test hook FNN_FAULT_ERROR="rank:event": an error code on one rank only
 
     bool relaxed() const { return opts.mode == FNN_MODE_RELAXED; }
+    int32_t n1() const { return n > 0 ? n : 1; }
+
+    // ---- The device buffers, every one of them: a new buffer is ONE line of buffers().  create() and comm_set() allocate in the
+    // order of the table (the order and the byte counts fix the device addresses, and with them the HBM channels a buffer's
+    // rows fall on: tests/emu/fnn_engine_buffers_main.cpp --print shows both), begin() fills, destroy() frees.
+    enum When { ALWAYS = 1, RELAXED = 2, SCREEN = 4, RANKS = 8 };  // Relaxed mode / the screening copy / several ranks (comm_set)
+    struct Buf {
+        void* slot;    // where its pointer lives: a member of dev, or d_status
+        size_t bytes;
+        int when;
+        int fill;      // the byte begin() fills it with; -1: begin() leaves it as it is
+        void* get() const { void* p; std::memcpy(&p, slot, sizeof p); return p; }
+        void put(void* p) const { std::memcpy(slot, &p, sizeof p); }
+    };
+    template <class T>
+    static Buf buf(T*& p, size_t count, int when = ALWAYS, int fill = -1) { return Buf{&p, sizeof(T) * count, when, fill}; }
+    std::vector<Buf> buffers() {
+        const size_t nn = (size_t)n1(), per = nn + 8, units = (size_t)screen_unit_count(n1()), bb = (size_t)wx_block_bytes(world);
+        return {
+            buf(dev.D, (size_t)nrows * (size_t)ld),
+            buf(dev.Sx, per), buf(dev.sid, per), buf(dev.spos, per), buf(dev.pslot, per),
+            buf(dev.chain, CHAIN_BUFS * (size_t)dev.cstride),
+            buf(dev.recs, be.max_records(n)),
+            buf(dev.rchk, 2048 + 8),
+            buf(dev.T, per),
+            buf(dev.srec, 2 * units + 16), buf(dev.stile, 2 * units / 4 + 16), buf(dev.shit, units + 16),
+            buf(dev.clist, SCR_CAP),
+            buf(dev.islot, 3 * nn + 8, ALWAYS, 0xFF), buf(dev.cstamp, 3 * nn + 8, ALWAYS, 0),
+            buf(dev.tpairs, (size_t)LA_REC_INTS * LA_PCAP),
+            buf(dev.fresh, 3 * LA_KMAX),
+            // (the ticket words and, right behind them in the same allocation, the decide step's record: upre_behind_ticket)
+            buf(dev.ticket, TICKET_WORDS + sizeof(UpdPre) / sizeof(uint32_t), ALWAYS, 0),
+            buf(dev.lacnt, 64, ALWAYS, 0),
+            buf(dev.ticks, TICK_WORDS, ALWAYS, 0),
+            buf(dev.lalog, 5 * LA_LOGCAP),
+            // k_update (deferred close) leaves {sum, sum of magnitudes} per workgroup: ceil(m / 256) + 1 workgroups;
+            // -> sized from the update grid like rxpart
+            buf(dev.upart, 4 * upart_capacity(n)),
+            buf(dev.gsend, GATHER_RECS),
+            buf(dev.rperm, per, RELAXED), buf(dev.rl_stamp, per, RELAXED, 0), buf(dev.rl_cnt, per, RELAXED),
+            buf(dev.rl_list, RL_TIES * per, RELAXED), buf(dev.rl_val, per, RELAXED), buf(dev.rl_mail, RL_MAIL_WORDS, RELAXED, 0),
+            buf(dev.grecv, GATHER_RECS * 64),
+            buf(dev.st, 1), buf(dev.evlog, per), buf(dev.agglog, per),
+            buf(dev.H, (size_t)nrows * (size_t)ldh, SCREEN),
+            buf(dev.wsend, bb, RANKS), buf(dev.wrecv, bb * (size_t)world, RANKS), buf(d_status, 64, RANKS),
+        };
+    }
+    static_assert(sizeof(UpdPre) % sizeof(uint32_t) == 0, "the ticket allocation is counted in ticket words");
+    // the buffers of the classes in `which`, in table order; stops at the first that cannot be had (destroy() frees the others)
+    bool alloc_buffers(int which) {
+        for (const Buf& b : buffers())
+            if (b.when & which) {
+                b.put(be.alloc(b.bytes));
+                if (!b.get()) return false;
+            }
+        return true;
+    }
+    void free_buffers(int which) {
+        for (const Buf& b : buffers())
+            if (b.when & which) { be.free(b.get()); b.put(nullptr); }
+    }
 
     int32_t create(int32_t n_, const fnn_opts* o) {
         if (n_ < 0) return fail(FNN_EINVAL, "fnn_create: n < 0");
@@ -129,64 +204,28 @@ class Engine {
         // padded geometry: rows to a multiple of the scan tile height, row stride to a
         // multiple of the tile width plus 32 doubles so that column sweeps (stride ld)
         // do not hammer one HBM channel
-        nrows = round_up(n > 0 ? n : 1, B::kRowPad);
-        ld = round_up(n > 0 ? n : 1, B::kColPad) + 32;
+        nrows = round_up(n1(), B::kRowPad);
+        ld = round_up(n1(), B::kColPad) + 32;
         // the bf16 copy has its own row stride (FNN_LDH_PAD: shifts between 64 B and 4.5 KB per row were measured in the
         // screening pass at n = 32768 - all within 4.5-4.85 TB/s; a 512-B shift reached 5.1 TB/s only together with a
         // 2-KB shift of the fp64 rows, which slows the event chain by 7 %: no robust gain, so both use the same padding)
         ldh = ld;
-        if (const char* e = std::getenv("FNN_LDH_PAD")) { int v = std::atoi(e); if (v >= 32 && v % 8 == 0 && v <= 65536) ldh = round_up(n > 0 ? n : 1, B::kColPad) + v; }
+        int32_t pad = 0;
+        if (env_int("FNN_LDH_PAD", 32, 65536, &pad) && pad % 8 == 0) ldh = round_up(n1(), B::kColPad) + pad;
         dev.n = n;
         dev.fault_event = -1;
         dev.ld = ld;
         dev.ldh = ldh;
-        dev.cstride = round_up(n > 0 ? n : 1, CH_SC);
+        dev.cstride = round_up(n1(), CH_SC);
         dev.rank = 0;
         dev.world = 1;
         dev.gather = 0;
-        size_t nn = (size_t)(n > 0 ? n : 1);
-        if (!(dev.D = (double*)be.alloc(sizeof(double) * (size_t)nrows * (size_t)ld)) ||
-            !(dev.Sx = (double*)be.alloc(sizeof(double) * (nn + 8))) ||
-            !(dev.sid = (int32_t*)be.alloc(sizeof(int32_t) * (nn + 8))) ||
-            !(dev.spos = (int32_t*)be.alloc(sizeof(int32_t) * (nn + 8))) ||
-            !(dev.pslot = (int32_t*)be.alloc(sizeof(int32_t) * (nn + 8))) ||
-            !(dev.chain = (double*)be.alloc(sizeof(double) * CHAIN_BUFS * (size_t)dev.cstride)) ||
-            !(dev.recs = (Cand*)be.alloc(sizeof(Cand) * be.max_records(n))) ||
-            !(dev.rchk = (uint64_t*)be.alloc(sizeof(uint64_t) * (2048 + 8))) ||
-            !(dev.T = (double*)be.alloc(sizeof(double) * (nn + 8))) ||
-            !(dev.srec = (float*)be.alloc(sizeof(float) * (2 * (size_t)screen_unit_count(n > 0 ? n : 1) + 16))) ||
-            !(dev.stile = (float*)be.alloc(sizeof(float) * (2 * (size_t)screen_unit_count(n > 0 ? n : 1) / 4 + 16))) ||
-            !(dev.shit = (uint64_t*)be.alloc(sizeof(uint64_t) * ((size_t)screen_unit_count(n > 0 ? n : 1) + 16))) ||
-            !(dev.clist = (int32_t*)be.alloc(sizeof(int32_t) * SCR_CAP)) ||
-            !(dev.islot = (int32_t*)be.alloc(sizeof(int32_t) * (3 * nn + 8))) ||
-            !(dev.cstamp = (int32_t*)be.alloc(sizeof(int32_t) * (3 * nn + 8))) ||
-            !(dev.tpairs = (int32_t*)be.alloc(sizeof(int32_t) * LA_REC_INTS * LA_PCAP)) ||
-            !(dev.fresh = (int32_t*)be.alloc(sizeof(int32_t) * 3 * LA_KMAX)) ||
-            !(dev.ticket = (uint32_t*)be.alloc(sizeof(uint32_t) * TICKET_WORDS + sizeof(UpdPre))) ||
-            !(dev.lacnt = (int32_t*)be.alloc(256)) ||
-            !(dev.ticks = (int64_t*)be.alloc(sizeof(int64_t) * TICK_WORDS)) ||
-            !(dev.lalog = (double*)be.alloc(sizeof(double) * 5 * LA_LOGCAP)) ||
-            // k_update (deferred close) leaves {sum, sum of magnitudes} per workgroup: ceil(m / 256) + 1 workgroups;
-            // -> sized from the update grid like rxpart
-            !(dev.upart = (double*)be.alloc(sizeof(double) * 4 * upart_capacity(n))) ||
-            !(dev.gsend = (Cand*)be.alloc(sizeof(Cand) * GATHER_RECS)) ||
-            (relaxed() && (!(dev.rperm = (int32_t*)be.alloc(sizeof(int32_t) * (nn + 8))) ||
-                           !(dev.rl_stamp = (int32_t*)be.alloc(sizeof(int32_t) * (nn + 8))) ||
-                           !(dev.rl_cnt = (int32_t*)be.alloc(sizeof(int32_t) * (nn + 8))) ||
-                           !(dev.rl_list = (int32_t*)be.alloc(sizeof(int32_t) * RL_TIES * (nn + 8))) ||
-                           !(dev.rl_val = (double*)be.alloc(sizeof(double) * (nn + 8))) ||
-                           !(dev.rl_mail = (uint64_t*)be.alloc(sizeof(uint64_t) * RL_MAIL_WORDS)))) ||
-            !(dev.grecv = (Cand*)be.alloc(sizeof(Cand) * GATHER_RECS * 64)) ||
-            !(dev.st = (State*)be.alloc(sizeof(State))) ||
-            !(dev.evlog = (Event*)be.alloc(sizeof(Event) * (nn + 8))) ||
-            !(dev.agglog = (Agg3Rec*)be.alloc(sizeof(Agg3Rec) * (nn + 8))))
+        if (!alloc_buffers(ALWAYS | (relaxed() ? RELAXED : 0)))
             return fail(FNN_ENOMEM, "fnn_create: device allocation failed (" + be.err() + ")");
         dev.upre = upre_behind_ticket(dev);
-        dev.H = nullptr;
-        if (!opts.disable_screen && !relaxed() && n >= be.screen_min_n()) {  // (Relaxed mode: no windows, plain scans at the end)
-            if (!(dev.H = (uint16_t*)be.alloc(sizeof(uint16_t) * (size_t)nrows * (size_t)ldh)))
-                return fail(FNN_ENOMEM, "fnn_create: device allocation of the bf16 copy failed (" + be.err() + ")");
-        }
+        // (Relaxed mode: no windows, plain scans at the end)
+        if (!opts.disable_screen && !relaxed() && n >= be.screen_min_n() && !alloc_buffers(SCREEN))
+            return fail(FNN_ENOMEM, "fnn_create: device allocation of the bf16 copy failed (" + be.err() + ")");
         // zero the padding once so that stray loads never see signalling patterns
         if (be.memset(dev.D, 0, sizeof(double) * (size_t)nrows * (size_t)ld) != FNN_OK)
             return fail(FNN_EHIP, "fnn_create: memset failed (" + be.err() + ")");
@@ -194,8 +233,7 @@ class Engine {
     }
 
     void destroy() {
-        be.free(dev.D); be.free(dev.Sx); be.free(dev.sid); be.free(dev.spos); be.free(dev.pslot);
-        be.free(dev.chain); be.free(dev.recs); be.free(dev.rchk); be.free(dev.T); be.free(dev.gsend); be.free(dev.grecv); be.free(dev.wsend); be.free(dev.wrecv); be.free(d_status); d_status = nullptr; be.free(dev.H); be.free(dev.srec); be.free(dev.stile); be.free(dev.clist); be.free(dev.shit); be.free(dev.islot); be.free(dev.cstamp); be.free(dev.tpairs); be.free(dev.fresh); be.free(dev.ticket); be.free(dev.lacnt); be.free(dev.rperm); be.free(dev.rl_stamp); be.free(dev.rl_cnt); be.free(dev.rl_list); be.free(dev.rl_val); be.free(dev.rl_mail); be.free(dev.ticks); be.free(dev.lalog); be.free(dev.upart); be.free(dev.st); be.free(dev.evlog); be.free(dev.agglog);
+        free_buffers(~0);
         dev = Dev{};
         be.close();
     }
@@ -341,15 +379,12 @@ class Engine {
             hst.rl_first = 0;      // (:177-183 done here: identity permutation, top = ntax - 1)
             hst.rl_top = n - 1;
             {
-                std::vector<int32_t> iota((size_t)(n > 0 ? n : 1));
+                std::vector<int32_t> iota((size_t)n1());
                 for (size_t i = 0; i < iota.size(); i++) iota[i] = (int32_t)i;
                 if (be.h2d(dev.rperm, iota.data(), sizeof(int32_t) * iota.size()) != FNN_OK)
                     return fail(FNN_EHIP, "fnn_begin: upload failed (" + be.err() + ")");
             }
             hst.rl_rng = JavaRandom::scramble(((uint64_t)opts.relaxed_seed_hi << 32) | (uint64_t)opts.relaxed_seed_lo);
-            if (be.memset(dev.rl_stamp, 0, sizeof(int32_t) * ((size_t)(n > 0 ? n : 1) + 8)) != FNN_OK ||
-                be.memset(dev.rl_mail, 0, sizeof(uint64_t) * RL_MAIL_WORDS) != FNN_OK)
-                return fail(FNN_EHIP, "fnn_begin: memset failed (" + be.err() + ")");
         }
         // lookahead windows (fnn_core.h "Lookahead"): single rank with a screening copy
         {
@@ -364,10 +399,10 @@ class Engine {
             int32_t target = opts.lookahead_pairs > 0 ? opts.lookahead_pairs : 49152;
             hst.la_kbase = 16;
             hst.la_kdiv = 512;
-            if (const char* e = std::getenv("FNN_LA_KBASE")) { int v = std::atoi(e); if (v >= 1 && v <= 64) hst.la_kbase = v; }
-            if (const char* e = std::getenv("FNN_LA_KDIV")) { int v = std::atoi(e); if (v >= 64) hst.la_kdiv = v; }
-            if (const char* e = std::getenv("FNN_LA_K")) K = std::atoi(e);
-            if (const char* e = std::getenv("FNN_LA_TARGET")) target = std::atoi(e);
+            env_int("FNN_LA_KBASE", 1, 64, &hst.la_kbase);
+            env_int("FNN_LA_KDIV", 64, INT_MAX, &hst.la_kdiv);
+            env_int("FNN_LA_K", INT_MIN, INT_MAX, &K);
+            env_int("FNN_LA_TARGET", INT_MIN, INT_MAX, &target);
             if (K > LA_KMAX) K = LA_KMAX;
             if (target < 1) target = 1;
             if (target > LA_PCAP) target = LA_PCAP;
@@ -389,15 +424,13 @@ class Engine {
             ev_counter = 0;
             sched_at = 0;
             hst.la_pcap = LA_PCAP;
-            if (const char* e = std::getenv("FNN_LA_PCAP")) { int v = std::atoi(e); if (v >= 1 && v <= LA_PCAP) hst.la_pcap = v; }
+            env_int("FNN_LA_PCAP", 1, LA_PCAP, &hst.la_pcap);
         }
         if (be.h2d(dev.st, &hst, sizeof(State)) != FNN_OK)
             return fail(FNN_EHIP, "fnn_begin: state upload failed (" + be.err() + ")");
-        if (be.memset(dev.islot, 0xFF, sizeof(int32_t) * (3 * (size_t)(n > 0 ? n : 1) + 8)) != FNN_OK ||
-            be.memset(dev.cstamp, 0, sizeof(int32_t) * (3 * (size_t)(n > 0 ? n : 1) + 8)) != FNN_OK ||
-            be.memset(dev.ticket, 0, sizeof(uint32_t) * TICKET_WORDS) != FNN_OK || be.memset(dev.lacnt, 0, 256) != FNN_OK || be.memset(dev.ticks, 0, sizeof(int64_t) * TICK_WORDS) != FNN_OK ||
-            be.memset(dev.upre, 0, sizeof(UpdPre)) != FNN_OK)
-            return fail(FNN_EHIP, "fnn_begin: memset failed (" + be.err() + ")");
+        for (const Buf& b : buffers())  // (the buffers a run must find cleared; one that this handle does not have is NULL)
+            if (b.fill >= 0 && b.get() && be.memset(b.get(), b.fill, b.bytes) != FNN_OK)
+                return fail(FNN_EHIP, "fnn_begin: memset failed (" + be.err() + ")");
         {
             UpdPre where{};  // (only its last line goes up: the addresses the decide step's prefetch reads from)
             where.pD = dev.D; where.pSx = dev.Sx; where.pT = dev.T; where.pld = dev.ld;
@@ -446,15 +479,9 @@ class Engine {
         dev.world = world_;
         dev.rank = rank_;
         dev.gather = comm_mode != 0 ? 1 : 0;
-        be.free(dev.wsend); be.free(dev.wrecv); be.free(d_status);
-        dev.wsend = dev.wrecv = nullptr;
-        d_status = nullptr;
-        if (comm_mode != 0) {
-            const size_t bb = (size_t)wx_block_bytes(world_);
-            if (!(dev.wsend = (uint8_t*)be.alloc(bb)) || !(dev.wrecv = (uint8_t*)be.alloc(bb * (size_t)world_)) ||
-                !(d_status = (int32_t*)be.alloc(sizeof(int32_t) * 64)))
-                return fail(FNN_ENOMEM, "fnn_comm_init: device allocation failed (" + be.err() + ")");
-        }
+        free_buffers(RANKS);
+        if (comm_mode != 0 && !alloc_buffers(RANKS))
+            return fail(FNN_ENOMEM, "fnn_comm_init: device allocation failed (" + be.err() + ")");
         fault_error_rank = fault_error_event = -1;
         if (const char* e = std::getenv("FNN_FAULT_ERROR")) {  // test hook: "rank:event"
             if (std::sscanf(e, "%d:%d", &fault_error_rank, &fault_error_event) != 2) fault_error_rank = fault_error_event = -1;
@@ -483,7 +510,8 @@ class Engine {
         bool sched = !dev.la || no_windows || cnt <= 1 || cnt >= sched_at;
         if (force_sched >= 0) sched = force_sched != 0;
         if (sched) sched_at = cnt + (hst.la_Kcur > 0 ? hst.la_Kcur : hst.la_K) + 1;
-        if (comm_mode == 0) return be.launch_event(dev, m_bound, sched) == FNN_OK ? FNN_OK : fail(FNN_EHIP, "launch failed (" + be.err() + ")");
+        const int32_t mb = m_bound < 1 ? 1 : m_bound;
+        if (comm_mode == 0) return launched(be.launch_event(dev, mb, sched));
         if (dev.wx) {
             // Several ranks with lookahead windows.  Every rank holds the whole matrix and runs the whole event chain
             // itself; the ranks stay in step because every decision is a deterministic function of identical state.
@@ -491,40 +519,35 @@ class Engine {
             // exchange: candidate records of the exact rescans + the pairs each rank emitted for the new window.
             Dev solo = dev;
             solo.world = 1; solo.rank = 0; solo.gather = 0; solo.wx = 0;  // (solo.strict stays on)
-            if (!sched || !be.use_screen(dev, m_bound))  // a window event, or the end game's small plain scans: no exchange
-                return be.launch_event(solo, m_bound, sched) == FNN_OK ? FNN_OK : fail(FNN_EHIP, "launch failed (" + be.err() + ")");
-            if (be.launch_wx_scan(dev, m_bound) != FNN_OK) return fail(FNN_EHIP, "launch failed (" + be.err() + ")");
+            if (!sched || !be.use_screen(dev, mb))  // a window event, or the end game's small plain scans: no exchange
+                return launched(be.launch_event(solo, mb, sched));
+            int32_t rc = launched(be.launch_wx_scan(dev, mb));
             const size_t bb = (size_t)wx_block_bytes(world);
-            if (comm_mode == 1) {
-                if (be.allgather_wx_on_stream(dev, bb) != FNN_OK) return fail(FNN_ERCCL, "all-gather failed (" + be.err() + ")");
-            } else {
-                std::vector<uint8_t> mine(bb), all(bb * (size_t)world);
-                if (be.sync() != FNN_OK || be.d2h(mine.data(), dev.wsend, bb) != FNN_OK)
-                    return fail(FNN_EHIP, "exchange block download failed (" + be.err() + ")");
-                if (!host_fn || host_fn(host_ctx, mine.data(), all.data(), (int32_t)bb) != 0)
-                    return fail(FNN_ERCCL, "host all-gather callback failed");
-                if (be.h2d(dev.wrecv, all.data(), all.size()) != FNN_OK)
-                    return fail(FNN_EHIP, "exchange block upload failed (" + be.err() + ")");
-            }
-            if (be.launch_wx_rest(dev, m_bound) != FNN_OK) return fail(FNN_EHIP, "launch failed (" + be.err() + ")");
-            return FNN_OK;
+            if (rc == FNN_OK)  // (over RCCL under the backend's exchange class: fnn_get_exchange_times reports these, and only these)
+                rc = comm_mode == 1 ? gathered(be.allgather_wx_on_stream(dev, bb)) : exchange_by_host(dev.wsend, dev.wrecv, bb, "exchange block");
+            return rc == FNN_OK ? launched(be.launch_wx_rest(dev, mb)) : rc;
         }
         // Several ranks without windows (no screening copy: small problems, or lookahead off): every event scans
         // 1/world of the tiles on each rank and exchanges the candidate records
         int32_t nper = 1;
-        if (be.launch_event_scan(dev, m_bound, &nper) != FNN_OK) return fail(FNN_EHIP, "launch failed (" + be.err() + ")");
-        if (comm_mode == 1) {
-            if (be.allgather_on_stream(dev, nper) != FNN_OK) return fail(FNN_ERCCL, "all-gather failed (" + be.err() + ")");
-        } else {
-            std::vector<Cand> mine((size_t)nper), all((size_t)nper * (size_t)world);
-            if (be.sync() != FNN_OK || be.d2h(mine.data(), dev.gsend, sizeof(Cand) * (size_t)nper) != FNN_OK)
-                return fail(FNN_EHIP, "candidate download failed (" + be.err() + ")");
-            if (!host_fn || host_fn(host_ctx, mine.data(), all.data(), (int32_t)(sizeof(Cand) * (size_t)nper)) != 0)
-                return fail(FNN_ERCCL, "host all-gather callback failed");
-            if (be.h2d(dev.grecv, all.data(), sizeof(Cand) * all.size()) != FNN_OK)
-                return fail(FNN_EHIP, "candidate upload failed (" + be.err() + ")");
-        }
-        if (be.launch_event_rest(dev, m_bound, nper * world) != FNN_OK) return fail(FNN_EHIP, "launch failed (" + be.err() + ")");
+        int32_t rc = launched(be.launch_event_scan(dev, mb, &nper));
+        const size_t cb = sizeof(Cand) * (size_t)nper;
+        if (rc == FNN_OK)
+            rc = comm_mode == 1 ? gathered(be.allgather_bytes_on_stream(dev.gsend, dev.grecv, cb)) : exchange_by_host(dev.gsend, dev.grecv, cb, "candidate");
+        return rc == FNN_OK ? launched(be.launch_event_rest(dev, mb, nper * world)) : rc;
+    }
+    int32_t launched(int32_t rc) { return rc == FNN_OK ? FNN_OK : fail(FNN_EHIP, "launch failed (" + be.err() + ")"); }
+    int32_t gathered(int32_t rc) { return rc == FNN_OK ? FNN_OK : fail(FNN_ERCCL, "all-gather failed (" + be.err() + ")"); }
+    // The exchange between ranks through the host callback (tests): every rank's `bytes` bytes at `send` (device), in rank order,
+    // into every rank's `recv` (device).  The stream is drained first.  (Over RCCL the callers enqueue the backend's all-gather.)
+    int32_t exchange_by_host(const void* send, void* recv, size_t bytes, const char* what) {
+        std::vector<uint8_t> mine(bytes), all(bytes * (size_t)world);
+        if (be.sync() != FNN_OK || be.d2h(mine.data(), send, bytes) != FNN_OK)
+            return fail(FNN_EHIP, std::string(what) + " download failed (" + be.err() + ")");
+        if (!host_fn || host_fn(host_ctx, mine.data(), all.data(), (int32_t)bytes) != 0)
+            return fail(FNN_ERCCL, "host all-gather callback failed");
+        if (be.h2d(recv, all.data(), all.size()) != FNN_OK)
+            return fail(FNN_EHIP, std::string(what) + " upload failed (" + be.err() + ")");
         return FNN_OK;
     }
 
@@ -567,7 +590,7 @@ class Engine {
     int32_t agglomerate() {
         if (!begun) return fail(FNN_ESTATE, "agglomerate: call fnn_begin first");
         double t0 = now_s();
-        if (const char* e = std::getenv("FNN_BATCH")) { int v = std::atoi(e); if (v >= 1 && v <= 4096) batch = v; }
+        env_int("FNN_BATCH", 1, 4096, &batch);
         while (!ended) {
             // with lookahead windows on, k_update closes the events and the exact row sum of the new
             // cluster is computed inside the next event's k_track (flushed before the host looks)
@@ -576,9 +599,10 @@ class Engine {
                 int32_t rce = enqueue_event();
                 if (rce != FNN_OK) return rce;
             }
-            if (be.defer_chain && be.launch_chain_flush(dev) != FNN_OK) return fail(FNN_EHIP, "launch failed (" + be.err() + ")");
+            int32_t rc = be.defer_chain ? launched(be.launch_chain_flush(dev)) : FNN_OK;
+            if (rc != FNN_OK) return rc;
             be.defer_chain = false;
-            int32_t rc = enqueue_status_exchange();
+            rc = enqueue_status_exchange();
             if (rc != FNN_OK) return rc;
             if (be.sync() != FNN_OK) return fail(FNN_EHIP, "fnn_run: sync failed (" + be.err() + ")");
             rc = pull_state_ranks();

@@ -3034,7 +3034,7 @@ struct HipBackend {
     static constexpr int64_t kRowPad = SCAN_TH;
     static constexpr int64_t kColPad = SCR_TW;   // whole screening tiles (and scan tiles) stay in bounds
     // below this many taxa the fp32 copy is not even allocated (FNN_SCREEN_MIN_N, tests)
-    int32_t screen_min_n() const { if (const char* e = std::getenv("FNN_SCREEN_MIN_N")) { int v = std::atoi(e); if (v >= 8) return v; } return 4096; }
+    int32_t screen_min_n() const { int32_t v = 4096; env_int("FNN_SCREEN_MIN_N", 8, INT_MAX, &v); return v; }
     // events with fewer live nodes use the plain fp64 scan.  Windows in the end game pay while the matrix is not yet
     // averaged out: measured, n = 4096 gains 6 % with a floor of 512-1024 (17 events per window there), n = 32768 LOSES
     // 4 % with 1024 (after 30 000 merges the criterion values lie so close together that a window holds ~1 event).
@@ -3086,7 +3086,7 @@ struct HipBackend {
         rx_exact_seen = n_rx_exact;
     }
     unsigned track_tag = 0;      // tag of a k_track launch in the helpers' JOB word
-    bool skip_unsched_scans = true; // FNN_UNSCHED_SCANS=1: keep the (mostly idle) scan kernels in unscheduled events
+    bool unsched_scans = false; // FNN_UNSCHED_SCANS=1: keep the (mostly idle) scan kernels in unscheduled events
     int track_group = TRK_GROUP;  // k_track: workgroups per first-level arrival counter (FNN_TRACK_GROUP)
     bool defer_chain = false; // set by the engine: k_update closes the event, the exact u.Sx sum runs inside the next k_track
     bool scan_nt = true;    // non-temporal matrix loads in the scan (FNN_SCAN_NT)
@@ -3117,25 +3117,25 @@ struct HipBackend {
         std::memcpy(uid.internal, id, sizeof(uid.internal));
         (void)hipSetDevice(device);
         int rc = p_ncclCommInitRank(&rccl_comm, world, uid, rank);
-        if (rc != 0) {
-            comm_err = std::string("ncclCommInitRank: ") + (p_ncclGetErrorString ? p_ncclGetErrorString(rc) : "error");
-            rccl_comm = nullptr;
-            return FNN_ERCCL;
-        }
-        return FNN_OK;
+        if (rc != 0) rccl_comm = nullptr;
+        return rc == 0 ? FNN_OK : nccl_failed("ncclCommInitRank", rc);
     }
-    // (the ranks' status words before a host round trip, fnn_engine.h: enqueue_status_exchange)
-    int32_t allgather_bytes_on_stream(const void* send, void* recv, size_t bytes_per_rank) {
-        if (!rccl_comm) { comm_err = "RCCL communicator not initialised"; return FNN_ERCCL; }
-        int rc = p_ncclAllGather(send, recv, bytes_per_rank, /*ncclInt8*/ 0, rccl_comm, stream);
-        if (rc != 0) { comm_err = std::string("ncclAllGather: ") + (p_ncclGetErrorString ? p_ncclGetErrorString(rc) : "error"); return FNN_ERCCL; }
-        return FNN_OK;
+    int32_t nccl_failed(const char* call, int rc) {
+        comm_err = std::string(call) + ": " + (p_ncclGetErrorString ? p_ncclGetErrorString(rc) : "error");
+        return FNN_ERCCL;
     }
-    int32_t allgather_on_stream(const Dev& d, int nper) {
+    // Every rank's `bytes` bytes at `send`, in rank order, into `recv`, on the stream: the candidate records of an event without
+    // windows and the ranks' status words before a host round trip (fnn_engine.h: enqueue_event, enqueue_status_exchange) ...
+    int32_t allgather_bytes_on_stream(const void* send, void* recv, size_t bytes) {
         if (!rccl_comm) { comm_err = "RCCL communicator not initialised"; return FNN_ERCCL; }
-        int rc = p_ncclAllGather(d.gsend, d.grecv, sizeof(Cand) * (size_t)nper, /*ncclInt8*/ 0, rccl_comm, stream);
-        if (rc != 0) { comm_err = std::string("ncclAllGather: ") + (p_ncclGetErrorString ? p_ncclGetErrorString(rc) : "error"); return FNN_ERCCL; }
-        return FNN_OK;
+        const int rc = p_ncclAllGather(send, recv, bytes, /*ncclInt8*/ 0, rccl_comm, stream);
+        return rc == 0 ? FNN_OK : nccl_failed("ncclAllGather", rc);
+    }
+    // ... and the exchange blocks of a base scan: the same, as class TC_GATHER when every kernel is timed (fnn_get_exchange_times)
+    int32_t allgather_wx_on_stream(const Dev& d, size_t bytes) {
+        int32_t rc = FNN_ERCCL;
+        timed(TC_GATHER, timing == 2 && rccl_comm != nullptr, [&] { rc = allgather_bytes_on_stream(d.wsend, d.wrecv, bytes); });  // (no event records without a communicator)
+        return rc;
     }
 
     int32_t open(int32_t dev) {
@@ -3147,22 +3147,23 @@ struct HipBackend {
         if (!HIPOK(hipSetDevice(device))) return fail(FNN_EHIP, "hipSetDevice failed (" + err() + ")");
         if (!HIPOK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)))
             return fail(FNN_EHIP, "hipStreamCreate failed (" + err() + ")");
-        if (const char* e = std::getenv("FNN_SCAN_GRID")) { int v = std::atoi(e); if (v >= 1 && v <= 65535) scan_grid = v; }
-        if (const char* e = std::getenv("FNN_SCAN_NT")) scan_nt = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FNN_TICKS")) ticks = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FNN_UNSCHED_GRID")) { int v = std::atoi(e); if (v >= 1 && v <= 65535) unsched_grid = v; }
-        if (const char* e = std::getenv("FNN_UNSCHED_SCANS")) skip_unsched_scans = std::atoi(e) == 0;
-        if (const char* e = std::getenv("FNN_EMIT_GRID")) { int v = std::atoi(e); if (v >= 1 && v <= 65535) emit_grid = v; }
-        if (const char* e = std::getenv("FNN_RX_HELPERS")) rx_helpers_cfg = std::atoi(e) != 0 ? TRK_NHELP : 0;
-        if (const char* e = std::getenv("FNN_TRACK_GROUP")) { int v = std::atoi(e); if (v >= 2 && v <= 1024) track_group = v; }
-        if (const char* e = std::getenv("FNN_TRACK_GRID")) { int v = std::atoi(e); if (v >= 1 && v <= 1024) track_grid = v; }
+        bool help = true;
+        env_int("FNN_SCAN_GRID", 1, 65535, &scan_grid);
+        env_flag("FNN_SCAN_NT", &scan_nt);
+        env_flag("FNN_TICKS", &ticks);
+        env_int("FNN_UNSCHED_GRID", 1, 65535, &unsched_grid);
+        env_flag("FNN_UNSCHED_SCANS", &unsched_scans);
+        env_int("FNN_EMIT_GRID", 1, 65535, &emit_grid);
+        if (env_flag("FNN_RX_HELPERS", &help)) rx_helpers_cfg = help ? TRK_NHELP : 0;
+        env_int("FNN_TRACK_GROUP", 2, 1024, &track_group);
+        env_int("FNN_TRACK_GRID", 1, 1024, &track_grid);
         // the first-level arrival counters sit at d.ticket + 32 (g + 1), g < ceil(grid / group); word 32 * 65 is TRK_FLAG, 32 * 67
         // TRK_BAD and the array holds 32 * 72 words: at most 64 groups (the two switches are development aids, but an
         // inconsistent pair must not run the atomics into the flag words or out of bounds)
         static_assert(TRK_FLAG == 32 * 65 && TRK_BAD == 32 * 67, "ticket layout: groups 1..64, then the flag words");
         while ((track_grid + track_group - 1) / track_group > 64) track_group *= 2;
-        if (const char* e = std::getenv("FNN_RELAXED_GRID")) { int v = std::atoi(e); if (v >= 1 && v <= RL_GMAX) relaxed_grid = v; }
-        if (const char* e = std::getenv("FNN_SCREEN_MIN_M")) { int v = std::atoi(e); if (v >= 8) { screen_min_m = v; screen_min_m_fixed = true; } }
+        env_int("FNN_RELAXED_GRID", 1, RL_GMAX, &relaxed_grid);
+        screen_min_m_fixed = env_int("FNN_SCREEN_MIN_M", 8, INT_MAX, &screen_min_m);
         opened = true;
         return FNN_OK;
     }
@@ -3250,6 +3251,15 @@ struct HipBackend {
             (void)hipEventRecord(e1, stream);
         } else launch();
     }
+    // One kernel on the engine's stream, between two event records of class `cls` when `on`.  A plain template around
+    // hipLaunchKernelGGL: the event loop enqueues some 100 000 of these per run, so nothing here allocates, erases a type or
+    // calls through a table.  A launch that failed is found by launched(), once per launch_* method.
+    template <class K, class... A>
+    void launch(int cls, bool on, K kernel, dim3 grid, dim3 block, const A&... args) {
+        timed(cls, on, [&]() { hipLaunchKernelGGL(kernel, grid, block, 0, stream, args...); });
+    }
+    int32_t launched() { return HIPOK(hipGetLastError()) ? FNN_OK : FNN_EHIP; }
+    int32_t launched_and_done() { return HIPOK(hipGetLastError()) && HIPOK(hipStreamSynchronize(stream)) ? FNN_OK : FNN_EHIP; }
     int32_t sync() {
         if (!HIPOK(hipStreamSynchronize(stream))) return FNN_EHIP;
         if (timing) drain_timing();
@@ -3279,8 +3289,8 @@ struct HipBackend {
 
     int32_t launch_synth(const Dev& d, uint64_t seed, int32_t dist) {
         dim3 g((unsigned)((d.n + 255) / 256), (unsigned)d.n);
-        hipLaunchKernelGGL(k_synth, g, dim3(256), 0, stream, d, seed, dist);
-        return HIPOK(hipGetLastError()) && HIPOK(hipStreamSynchronize(stream)) ? FNN_OK : FNN_EHIP;
+        launch(TC_OTHER, false, k_synth, g, dim3(256), d, seed, dist);
+        return launched_and_done();
     }
     int32_t unpack_rows(const Dev& d, const double* src, int64_t p0, int64_t entries, int32_t row0, int32_t cnt) {
         if (entries > stage_cap) {
@@ -3292,23 +3302,23 @@ struct HipBackend {
         }
         if (!HIPOK(hipMemcpyAsync(d_stage, src, sizeof(double) * (size_t)entries, hipMemcpyHostToDevice, stream))) return FNN_EHIP;
         dim3 g((unsigned)((d.n + 255) / 256), (unsigned)cnt);
-        hipLaunchKernelGGL(k_unpack, g, dim3(256), 0, stream, d, (const double*)d_stage, p0, row0);
-        return HIPOK(hipGetLastError()) && HIPOK(hipStreamSynchronize(stream)) ? FNN_OK : FNN_EHIP;
+        launch(TC_OTHER, false, k_unpack, g, dim3(256), d, (const double*)d_stage, p0, row0);
+        return launched_and_done();
     }
     int32_t launch_mirror(const Dev& d) {
         if (d_stage) (void)hipFree(d_stage);
         d_stage = nullptr;
         stage_cap = 0;
         unsigned t = (unsigned)((d.n + 31) / 32);
-        hipLaunchKernelGGL(k_mirror, dim3(t, t), dim3(256), 0, stream, d);
-        return HIPOK(hipGetLastError()) && HIPOK(hipStreamSynchronize(stream)) ? FNN_OK : FNN_EHIP;
+        launch(TC_OTHER, false, k_mirror, dim3(t, t), dim3(256), d);
+        return launched_and_done();
     }
     int32_t launch_validate(const Dev& d, int32_t* bad) {
         if (!d_bad && !HIPOK(hipMalloc((void**)&d_bad, sizeof(int)))) return FNN_EHIP;
         if (!HIPOK(hipMemsetAsync(d_bad, 0, sizeof(int), stream))) return FNN_EHIP;
         unsigned t = (unsigned)((d.n + 31) / 32);
-        hipLaunchKernelGGL(k_validate, dim3(t, t), dim3(256), 0, stream, d, d_bad);
-        if (!HIPOK(hipGetLastError())) return FNN_EHIP;
+        launch(TC_OTHER, false, k_validate, dim3(t, t), dim3(256), d, d_bad);
+        if (launched() != FNN_OK) return FNN_EHIP;
         int hb = 0;
         if (!HIPOK(hipMemcpyAsync(&hb, d_bad, sizeof(int), hipMemcpyDeviceToHost, stream)) ||
             !HIPOK(hipStreamSynchronize(stream)))
@@ -3318,14 +3328,14 @@ struct HipBackend {
     }
     int32_t launch_prep_screen(const Dev& d, int64_t nrows) {
         const int64_t want = (nrows * d.ld + 255) / 256;
-        hipLaunchKernelGGL(k_prep_screen, dim3((unsigned)(want < 8192 ? (want > 0 ? want : 1) : 8192)), dim3(256), 0, stream, d, nrows);
-        return HIPOK(hipGetLastError()) ? FNN_OK : FNN_EHIP;
+        launch(TC_OTHER, false, k_prep_screen, dim3((unsigned)(want < 8192 ? (want > 0 ? want : 1) : 8192)), dim3(256), d, nrows);
+        return launched();
     }
     int32_t launch_init(const Dev& d) {
         reset_timing();
         rx_exact_seen = 0; rx_helpers = 0;  // (a new run: the device's counter starts again)
-        hipLaunchKernelGGL(k_init, grid1(d.n), dim3(256), 0, stream, d);
-        return HIPOK(hipGetLastError()) ? FNN_OK : FNN_EHIP;
+        launch(TC_OTHER, false, k_init, grid1(d.n), dim3(256), d);
+        return launched();
     }
 
     dim3 scan_dims(const Dev& d, int32_t m_bound) const {
@@ -3346,113 +3356,84 @@ struct HipBackend {
         // (an unscheduled event is launched without scan kernels: if its window cannot serve it, the
         //  device stalls - this and the following such events do nothing - until the host, which
         //  looks at the state every batch, launches an event with a scan)
-        const bool has_scan = sched || !screen || !skip_unsched_scans;
-        if (d.la) timed(TC_TRACK, tall, [&]() {
-            track_tag = (track_tag % 0x7FFFFFEu) + 1u;  // (never 0: the JOB word starts out as 0)
+        const bool has_scan = sched || !screen || unsched_scans;
+        if (d.la) {
+            const bool help = rx_helpers > 0;
             const int fb = (sched || !screen) ? 1 : 0, hs = has_scan ? 1 : 0, tk = ticks ? 1 : 0;
-            if (rx_helpers > 0) hipLaunchKernelGGL(k_track<true>, dim3(track_grid + 1 + TRK_NHELP), dim3(TRK_THREADS), 0, stream, d, fb, fb, hs, track_group, tk, track_tag);
-            else hipLaunchKernelGGL(k_track<false>, dim3(track_grid + 1), dim3(TRK_THREADS), 0, stream, d, fb, fb, hs, track_group, tk, track_tag);
-        });
-        int nrecs;
-        if (screen && !has_scan) nrecs = 0;  // (a window event: the tail of k_track decides; no decide kernel follows)
-        else if (screen) {
+            track_tag = (track_tag % 0x7FFFFFEu) + 1u;  // (never 0: the JOB word starts out as 0)
+            launch(TC_TRACK, tall, help ? k_track<true> : k_track<false>, dim3(track_grid + 1 + (help ? TRK_NHELP : 0)), dim3(TRK_THREADS),
+                   d, fb, fb, hs, track_group, tk, track_tag);
+        }
+        if (screen && !has_scan) return 0;  // (a window event: the tail of k_track decides; no decide kernel follows)
+        if (screen) {
+            // [!SCHED][!NT] (named in the order in which the code object has always held the four)
+            static constexpr decltype(&k_screen<true, true>) variants[2][2] = {{k_screen<true, true>, k_screen<false, true>},
+                                                                               {k_screen<true, false>, k_screen<false, false>}};
             int nt = (tri_tile_count(m_bound, SCR_TH, SCR_R) + d.world - 1) / d.world;
             const int want = sched ? scan_grid : unsched_grid;
-            dim3 gs((unsigned)(nt < want ? (nt > 0 ? nt : 1) : want));
-            timed(TC_SCREEN, tscan, [&]() {
-                if (sched) {
-                    if (scan_nt) hipLaunchKernelGGL((k_screen<true, true>), gs, dim3(256), 0, stream, d);
-                    else hipLaunchKernelGGL((k_screen<false, true>), gs, dim3(256), 0, stream, d);
-                } else {
-                    if (scan_nt) hipLaunchKernelGGL((k_screen<true, false>), gs, dim3(256), 0, stream, d);
-                    else hipLaunchKernelGGL((k_screen<false, false>), gs, dim3(256), 0, stream, d);
-                }
-            });
-            if (d.la) timed(TC_EMIT, tall, [&]() { hipLaunchKernelGGL(k_emit, dim3(emit_grid), dim3(256), 0, stream, d); });
-            timed(TC_RESOLVE, tall, [&]() { hipLaunchKernelGGL(k_resolve, dim3(RES_BLOCKS), dim3(1024), 0, stream, d); });
-            nrecs = RES_BLOCKS;
+            launch(TC_SCREEN, tscan, variants[!sched][!scan_nt], dim3((unsigned)(nt < want ? (nt > 0 ? nt : 1) : want)), dim3(256), d);
+            if (d.la) launch(TC_EMIT, tall, k_emit, dim3(emit_grid), dim3(256), d);
+            launch(TC_RESOLVE, tall, k_resolve, dim3(RES_BLOCKS), dim3(1024), d);
             if (tscan) scan_launches++;
-        } else {
-            dim3 gs = scan_dims(d, m_bound);
-            // Relaxed mode: the search first; the scan returns at once if it found the pair (it runs when fewer
-            // nodes are live than the bound the host knows, i.e. at the switch to the full scans)
-            if (relaxed_min > 0 && m_bound > relaxed_min)
-                timed(TC_OTHER, tall, [&]() {
-                    // one workgroup streams ~40 GB/s: from ~12 000 live nodes on the row pass is spread over several
-                    // (a hand-over between workgroups costs ~3 us per row minimum)
-                    int g = relaxed_grid > 0 ? relaxed_grid : (m_bound >= 12288 ? m_bound / 4096 : 1);
-                    if (g > RL_GMAX) g = RL_GMAX;
-                    hipLaunchKernelGGL(k_relaxed, dim3(g), dim3(RL_T), 0, stream, d, ticks ? 1 : 0);
-                });
-            timed(TC_SCAN, tscan, [&]() {
-                if (scan_nt) hipLaunchKernelGGL(k_scan<true>, gs, dim3(SCAN_THREADS), 0, stream, d);
-                else hipLaunchKernelGGL(k_scan<false>, gs, dim3(SCAN_THREADS), 0, stream, d);
-            });
-            nrecs = (int)gs.x;
-            if (tscan) plain_launches++;
+            return RES_BLOCKS;
         }
-        return nrecs;
+        // Relaxed mode: the search first; the scan returns at once if it found the pair (it runs when fewer
+        // nodes are live than the bound the host knows, i.e. at the switch to the full scans)
+        if (relaxed_min > 0 && m_bound > relaxed_min) {
+            // one workgroup streams ~40 GB/s: from ~12 000 live nodes on the row pass is spread over several
+            // (a hand-over between workgroups costs ~3 us per row minimum)
+            int g = relaxed_grid > 0 ? relaxed_grid : (m_bound >= 12288 ? m_bound / 4096 : 1);
+            launch(TC_OTHER, tall, k_relaxed, dim3(g > RL_GMAX ? RL_GMAX : g), dim3(RL_T), d, ticks ? 1 : 0);
+        }
+        const dim3 gs = scan_dims(d, m_bound);
+        launch(TC_SCAN, tscan, scan_nt ? k_scan<true> : k_scan<false>, gs, dim3(SCAN_THREADS), d);
+        if (tscan) plain_launches++;
+        return (int)gs.x;
     }
     // everything after the scan; `src` holds the nrecs candidate records to reduce (0: a window event, already
     // decided by the tail of k_track - or stalled)
     void enqueue_rest(const Dev& d, int32_t m_bound, const Cand* src, int nrecs) {
-        dim3 g1 = grid1(m_bound);
-        const bool tall = timing == 2;
-        if (nrecs > 0) timed(TC_DECIDE, tall, [&]() {
+        const bool tall = timing == 2, help = rx_helpers > 0;
+        if (nrecs > 0) {
             track_tag = (track_tag % 0x7FFFFFEu) + 1u;
-            if (rx_helpers > 0) hipLaunchKernelGGL(k_decide<true>, dim3(1 + TRK_NHELP), dim3(CH_T), 0, stream, d, src, nrecs, track_tag);
-            else hipLaunchKernelGGL(k_decide<false>, dim3(1), dim3(CH_T), 0, stream, d, src, nrecs, track_tag);
-        });
-        timed(TC_UPDATE, tall, [&]() { hipLaunchKernelGGL(k_update, dim3(g1.x + 1), dim3(256), 0, stream, d, defer_chain ? 1 : 0, ticks ? 1 : 0); });
-        if (!defer_chain) timed(TC_OTHER, tall, [&]() { hipLaunchKernelGGL(k_finalize, dim3(1), dim3(CH_T), 0, stream, d); });
+            launch(TC_DECIDE, tall, help ? k_decide<true> : k_decide<false>, dim3(1 + (help ? TRK_NHELP : 0)), dim3(CH_T), d, src, nrecs, track_tag);
+        }
+        launch(TC_UPDATE, tall, k_update, dim3(grid1(m_bound).x + 1), dim3(256), d, defer_chain ? 1 : 0, ticks ? 1 : 0);
+        if (!defer_chain) launch(TC_OTHER, tall, k_finalize, dim3(1), dim3(CH_T), d);
     }
-    // single GPU: the whole event
+    // single GPU: the whole event.  (m_bound >= 1 in all of these: Engine::enqueue_event sees to it)
     int32_t launch_event(const Dev& d, int32_t m_bound, bool sched) {
-        if (m_bound < 1) m_bound = 1;
-        int nrecs = enqueue_scan(d, m_bound, sched);
-        enqueue_rest(d, m_bound, (const Cand*)d.recs, nrecs);
-        return HIPOK(hipGetLastError()) ? FNN_OK : FNN_EHIP;
+        enqueue_rest(d, m_bound, (const Cand*)d.recs, enqueue_scan(d, m_bound, sched));
+        return launched();
     }
     // a pending deferred row sum, before the host reads the state
     int32_t launch_chain_flush(const Dev& d) {
-        hipLaunchKernelGGL(k_chain_flush, dim3(1), dim3(CH_T), 0, stream, d);
-        return HIPOK(hipGetLastError()) ? FNN_OK : FNN_EHIP;
+        launch(TC_OTHER, false, k_chain_flush, dim3(1), dim3(CH_T), d);
+        return launched();
     }
     // several GPUs: scan of this rank's tiles ... (all-gather of the candidate records) ... the rest
     int32_t launch_event_scan(const Dev& d, int32_t m_bound, int32_t* nper) {
-        if (m_bound < 1) m_bound = 1;
-        int nrecs = enqueue_scan(d, m_bound, true);
-        if (nrecs == RES_BLOCKS && use_screen(d, m_bound)) {
-            *nper = nrecs;  // k_resolve has written its per-workgroup records straight into d.gsend
-        } else {
-            hipLaunchKernelGGL(k_reduce_local, dim3(1), dim3(1024), 0, stream, d, nrecs);
+        const int nrecs = enqueue_scan(d, m_bound, true);
+        *nper = nrecs;  // (a screened scan: k_resolve has written its per-workgroup records straight into d.gsend)
+        if (nrecs != RES_BLOCKS || !use_screen(d, m_bound)) {
+            launch(TC_OTHER, false, k_reduce_local, dim3(1), dim3(1024), d, nrecs);
             *nper = 1;
         }
-        return HIPOK(hipGetLastError()) ? FNN_OK : FNN_EHIP;
+        return launched();
     }
     // several ranks with lookahead windows: a base scan's sharded part ... (exchange) ... merge + the rest
     int32_t launch_wx_scan(const Dev& d, int32_t m_bound) {
-        if (m_bound < 1) m_bound = 1;
         (void)enqueue_scan(d, m_bound, true);
-        return HIPOK(hipGetLastError()) ? FNN_OK : FNN_EHIP;
-    }
-    int32_t allgather_wx_on_stream(const Dev& d, size_t bytes) {
-        if (!rccl_comm) { comm_err = "RCCL communicator not initialised"; return FNN_ERCCL; }
-        int rc = 0;
-        timed(TC_GATHER, timing == 2, [&] { rc = p_ncclAllGather(d.wsend, d.wrecv, bytes, /*ncclInt8*/ 0, rccl_comm, stream); });
-        if (rc != 0) { comm_err = std::string("ncclAllGather: ") + (p_ncclGetErrorString ? p_ncclGetErrorString(rc) : "error"); return FNN_ERCCL; }
-        return FNN_OK;
+        return launched();
     }
     int32_t launch_wx_rest(const Dev& d, int32_t m_bound) {
-        if (m_bound < 1) m_bound = 1;
-        timed(TC_MERGE, timing == 2, [&] { hipLaunchKernelGGL(k_merge, dim3(1), dim3(1024), 0, stream, d); });
+        launch(TC_MERGE, timing == 2, k_merge, dim3(1), dim3(1024), d);
         enqueue_rest(d, m_bound, (const Cand*)d.grecv, d.world * GATHER_RECS);
-        return HIPOK(hipGetLastError()) ? FNN_OK : FNN_EHIP;
+        return launched();
     }
     int32_t launch_event_rest(const Dev& d, int32_t m_bound, int32_t ntotal) {
-        if (m_bound < 1) m_bound = 1;
         enqueue_rest(d, m_bound, (const Cand*)d.grecv, ntotal);
-        return HIPOK(hipGetLastError()) ? FNN_OK : FNN_EHIP;
+        return launched();
     }
 };
 
@@ -3577,42 +3558,22 @@ int64_t fnn_debug_window_log(fnn_handle* h, double* out, int64_t max_records) {
     if (out && k > 0 && h->eng.be.d2h(out, h->eng.dev.lalog, sizeof(double) * 5 * (size_t)k) != FNN_OK) return FNN_EHIP;
     return k;
 }
-int32_t fnn_debug_event_ticks(fnn_handle* h, int64_t* out8) {
+// Dev::ticks (FNN_TICKS=1), by first word.  The kernels write these words with literal subscripts - k_track d.ticks[q], k_update
+// d.ticks[8 + ..], k_decide d.ticks[16 + q], decide_plan (fnn_core.h: FNN_PLAN_TICK) d.ticks[20 + k], k_relaxed d.ticks[24 .. 27],
+// k_update per workgroup d.ticks[32 + ..] in three runs of TICK_WG words: change the two sides together.
+enum { TICK_TRACK = 0, TICK_UPDATE = 8, TICK_DECIDE = 16, TICK_PLAN = 20, TICK_RELAXED = 24, TICK_UPDATE_WG = 32 };
+static_assert(TICK_UPDATE_WG + 3 * fnn::TICK_WG == fnn::TICK_WORDS, "the per-workgroup words end Dev::ticks");
+static int32_t read_ticks(fnn_handle* h, int64_t* out, int first, int words, const char* null_out) {
     FNN_NEED(h);
-    if (!out8) return fnn::fail(FNN_EINVAL, "fnn_debug_event_ticks: out8 is NULL");
-    if (h->eng.be.d2h(out8, h->eng.dev.ticks, sizeof(int64_t) * 8) != FNN_OK) return FNN_EHIP;
-    return FNN_OK;
+    if (!out) return fnn::fail(FNN_EINVAL, null_out);
+    return h->eng.be.d2h(out, h->eng.dev.ticks + first, sizeof(int64_t) * (size_t)words) == FNN_OK ? FNN_OK : FNN_EHIP;
 }
-int32_t fnn_debug_update_ticks(fnn_handle* h, int64_t* out8) {
-    FNN_NEED(h);
-    if (!out8) return fnn::fail(FNN_EINVAL, "fnn_debug_update_ticks: out8 is NULL");
-    if (h->eng.be.d2h(out8, h->eng.dev.ticks + 8, sizeof(int64_t) * 8) != FNN_OK) return FNN_EHIP;
-    return FNN_OK;
-}
-int32_t fnn_debug_relaxed_ticks(fnn_handle* h, int64_t* out4) {
-    FNN_NEED(h);
-    if (!out4) return fnn::fail(FNN_EINVAL, "fnn_debug_relaxed_ticks: out4 is NULL");
-    if (h->eng.be.d2h(out4, h->eng.dev.ticks + 24, sizeof(int64_t) * 4) != FNN_OK) return FNN_EHIP;
-    return FNN_OK;
-}
-int32_t fnn_debug_decide_ticks(fnn_handle* h, int64_t* out4) {
-    FNN_NEED(h);
-    if (!out4) return fnn::fail(FNN_EINVAL, "fnn_debug_decide_ticks: out4 is NULL");
-    if (h->eng.be.d2h(out4, h->eng.dev.ticks + 16, sizeof(int64_t) * 4) != FNN_OK) return FNN_EHIP;
-    return FNN_OK;
-}
-int32_t fnn_debug_update_wg_ticks(fnn_handle* h, int64_t* out768) {
-    FNN_NEED(h);
-    if (!out768) return fnn::fail(FNN_EINVAL, "fnn_debug_update_wg_ticks: out768 is NULL");
-    if (h->eng.be.d2h(out768, h->eng.dev.ticks + 32, sizeof(int64_t) * 3 * fnn::TICK_WG) != FNN_OK) return FNN_EHIP;
-    return FNN_OK;
-}
-int32_t fnn_debug_plan_ticks(fnn_handle* h, int64_t* out4) {
-    FNN_NEED(h);
-    if (!out4) return fnn::fail(FNN_EINVAL, "fnn_debug_plan_ticks: out4 is NULL");
-    if (h->eng.be.d2h(out4, h->eng.dev.ticks + 20, sizeof(int64_t) * 4) != FNN_OK) return FNN_EHIP;
-    return FNN_OK;
-}
+int32_t fnn_debug_event_ticks(fnn_handle* h, int64_t* out8) { return read_ticks(h, out8, TICK_TRACK, 8, "fnn_debug_event_ticks: out8 is NULL"); }
+int32_t fnn_debug_update_ticks(fnn_handle* h, int64_t* out8) { return read_ticks(h, out8, TICK_UPDATE, 8, "fnn_debug_update_ticks: out8 is NULL"); }
+int32_t fnn_debug_relaxed_ticks(fnn_handle* h, int64_t* out4) { return read_ticks(h, out4, TICK_RELAXED, 4, "fnn_debug_relaxed_ticks: out4 is NULL"); }
+int32_t fnn_debug_decide_ticks(fnn_handle* h, int64_t* out4) { return read_ticks(h, out4, TICK_DECIDE, 4, "fnn_debug_decide_ticks: out4 is NULL"); }
+int32_t fnn_debug_update_wg_ticks(fnn_handle* h, int64_t* out768) { return read_ticks(h, out768, TICK_UPDATE_WG, 3 * fnn::TICK_WG, "fnn_debug_update_wg_ticks: out768 is NULL"); }
+int32_t fnn_debug_plan_ticks(fnn_handle* h, int64_t* out4) { return read_ticks(h, out4, TICK_PLAN, 4, "fnn_debug_plan_ticks: out4 is NULL"); }
 int32_t fnn_debug_update_pre(fnn_handle* h, int64_t* out4) {
     FNN_NEED(h);
     if (!out4) return fnn::fail(FNN_EINVAL, "fnn_debug_update_pre: out4 is NULL");
