@@ -35,6 +35,7 @@
 #include <dlfcn.h>
 
 #include <cmath>
+#include <limits>
 #include <new>
 
 #include "fnn_chain.h"
@@ -859,7 +860,18 @@ struct ChainLds {
     uint64_t wk[CH_T / 64];
     int32_t wr[CH_T / 64];
     int32_t fail;
+    // per wave: binade of the piece its last thread leaves open / its first thread continues (CH_NOHEAD: none); its event threads
+    int32_t wtail[CH_T / 64], whead[CH_T / 64];
+    uint64_t emask[CH_T / 64];
+    uint64_t open_k;  // the piece left open at the end of a super-chunk
+    int32_t open_E;
 };
+constexpr int32_t CH_NOHEAD = INT32_MIN;
+// Below this many addends the chain sum takes the short form (chain_short_sum): one wave, strictly in order.  Measured
+// (profiles/r07): 2.9 us at 256 addends, 5.0 us at 1024, 8.1 us at 2040 - 3 ns per addend - against 11.4 / 13.6 / 13.8 us of
+// the record form; the two lines would cross near 4 000 addends, beyond the 64 x CH_EPT = 2048 that one wave holds.
+constexpr int CH_SHORT_M = 2048;
+static_assert(CH_SHORT_M <= 64 * CH_EPT, "the short form is one wave: one chunk per lane");
 
 __device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d) {
     return (uint64_t)__shfl_up((unsigned long long)v, d, 64);
@@ -882,8 +894,12 @@ __device__ __forceinline__ void chain_serial_global(double& s, const double* buf
         if (start + i < m) s += buf[chain_addr(start + i)];
 }
 
-__device__ int g_chain_form = 2;        // diagnostic (FNN_CHAIN_FORM=1): the first form in fnn_test_chain_sum
+__device__ int g_chain_form = 0;        // diagnostic (FNN_CHAIN_FORM, see k_test_chain): which form fnn_test_chain_sum runs
 __device__ int g_chain_stop_after = 0;  // diagnostic: 1 loads+prefix, 2 +automata, 3 +segmented scan (0 = full)
+// diagnostic (fnn_test_chain_sum with FNN_CHAIN_TIME): 100 MHz stamps of thread 0 in the record form - entry, then after the
+// loads, the prefix, the records (parked chunks included), the segmented scan, the walk, and at the end (last super-chunk)
+constexpr int CH_NTICK = 7;
+__device__ long long g_chain_ticks[CH_NTICK];
 
 // MODE 0: the whole sum.  MODE 1: steps 1-3 only (the records stay in L; m <= CH_T * EPT).  MODE 2:
 // step 4 only, on records that are in L already (m <= CH_T * EPT).
@@ -1136,12 +1152,99 @@ __device__ __attribute__((noinline)) double block_chain_sum_rare(const double* _
     return block_chain_sum<EPT>(buf, m, guard_bits, *L, stats);
 }
 
+// ---- scans of the record form on DPP moves (row_shr 1, 2, 4, 8 inside the rows of 16 lanes, then row_bcast 15 / 31 with row
+// masks, as in wave_reduce): hipcc lowers __shfl_up to ds_bpermute, ~100 cycles of LDS-crossbar latency per dependent step.
+// A lane without a source - shifted in from outside its row, or in a row the mask leaves out - receives 0, which is the
+// neutral element of every scan here (+0.0; "no reset, increment 0").
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_or0(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint64_t dpp_or0_u64(uint64_t v) {
+    const uint32_t lo = dpp_or0<CTRL, ROW_MASK>((uint32_t)v), hi = dpp_or0<CTRL, ROW_MASK>((uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+// the value of the lane below (lane 0: 0)
+__device__ __forceinline__ uint32_t lane_below_u32(uint32_t v) {
+    const uint32_t inrow = dpp_or0<0x111, 0xf>(v), across = dpp_or0<0x142, 0xe>(v);  // row_shr:1 | row_bcast:15 into rows 1-3
+    return (threadIdx.x & 15) ? inrow : across;
+}
+__device__ __forceinline__ uint64_t lane_below_u64(uint64_t v) {
+    return ((uint64_t)lane_below_u32((uint32_t)(v >> 32)) << 32) | lane_below_u32((uint32_t)v);
+}
+__device__ __forceinline__ uint64_t sat60(uint64_t t) { return t > (1ULL << 60) ? (1ULL << 60) : t; }
+// inclusive prefix sums (prediction only: the order of the additions is the scan's).  ROWS_ONLY: inside each row of 16 lanes
+template <bool ROWS_ONLY>
+__device__ __forceinline__ double scan_add_f64(double x) {
+#define FNN_SCAN_STEP(CTRL, MASK) x += u2f(dpp_or0_u64<CTRL, MASK>(f2u(x)))
+    FNN_SCAN_STEP(0x111, 0xf); FNN_SCAN_STEP(0x112, 0xf); FNN_SCAN_STEP(0x114, 0xf); FNN_SCAN_STEP(0x118, 0xf);
+    if (!ROWS_ONLY) { FNN_SCAN_STEP(0x142, 0xa); FNN_SCAN_STEP(0x143, 0xc); }
+#undef FNN_SCAN_STEP
+    return x;
+}
+// inclusive segmented scan of (reset, increment): an element with a reset keeps its own increment, any other adds what
+// is open in front of it (saturating at 2^60)
+template <bool ROWS_ONLY>
+__device__ __forceinline__ void scan_seg(int& rr, uint64_t& kk) {
+#define FNN_SCAN_STEP(CTRL, MASK) do { const int pr = (int)dpp_or0<CTRL, MASK>((uint32_t)rr); const uint64_t pk = dpp_or0_u64<CTRL, MASK>(kk); \
+        if (!rr) kk = sat60(pk + kk); rr |= pr; } while (0)
+    FNN_SCAN_STEP(0x111, 0xf); FNN_SCAN_STEP(0x112, 0xf); FNN_SCAN_STEP(0x114, 0xf); FNN_SCAN_STEP(0x118, 0xf);
+    if (!ROWS_ONLY) { FNN_SCAN_STEP(0x142, 0xa); FNN_SCAN_STEP(0x143, 0xc); }
+#undef FNN_SCAN_STEP
+}
+
+// The short form, for at most 64 * EPT addends: ONE wave, lane t holds chunk t.  The scalar loop itself, chunk after chunk:
+// in step t EVERY lane adds its own chunk, addend by addend, to the sum in front of chunk t (lane t - 1's result of the step
+// before, fetched by readlane) - right in lane t, which is the lane the next step reads, and of no interest elsewhere.  The
+// dependent chain is the m additions on vector registers plus two readlanes per chunk; no record, no scan, no walk.
+// (A masked addend is +0.0: s + 0.0 == s bit for bit, because a sum that starts at +0.0 is never -0.0.)
 template <int EPT>
+__device__ __forceinline__ double chain_short_sum(const double* __restrict__ buf, int m, ChainLds<EPT>& L) {
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        double a[EPT];
+        const double* src = buf + 2 * tid;
+#pragma unroll
+        for (int j = 0; j < EPT / 2; j++) {
+            double2 v = make_double2(0.0, 0.0);
+            if (tid * EPT + 2 * j < m) v = *reinterpret_cast<const double2*>(src + j * (2 * CH_T));
+            a[2 * j] = v.x;
+            a[2 * j + 1] = tid * EPT + 2 * j + 1 < m ? v.y : 0.0;
+        }
+        double sv = 0.0;
+        const int nch = (m + EPT - 1) / EPT;
+        for (int t = 0; t < nch; t++) {
+            double s = u2f(readlane_u64(f2u(sv), t > 0 ? t - 1 : 0));
+            if (t == 0) s = 0.0;
+#pragma unroll
+            for (int i = 0; i < EPT; i++) s += a[i];
+            sv = s;
+        }
+        const double res = nch > 0 ? u2f(readlane_u64(f2u(sv), nch > 0 ? nch - 1 : 0)) : 0.0;
+        if (tid == 0) L.s = res;
+    }
+    __syncthreads();
+    return L.s;
+}
+
+// short_below: sums of fewer addends take the short form (0: never).
+// PROF (fnn_test_chain_sum's stamped kernel only): thread 0 stamps the phases into g_chain_ticks.
+template <int EPT, bool PROF = false>
 __device__ __forceinline__ double block_chain_sum2(const double* __restrict__ buf, int m, int guard_bits, ChainLds<EPT>& L,
-                                                   ChainStats* stats) {
+                                                   ChainStats* stats, int short_below = CH_SHORT_M) {
     static_assert(EPT == CH_EPT, "the buffer layout is fixed to CH_EPT addends per thread");
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    if (m < short_below && m <= 64 * EPT) {
+        if (stats && tid == 0) *stats = ChainStats{0, 0, 0, 0};
+        return chain_short_sum<EPT>(buf, m, L);
+    }
     ChainStats cs{0, 0, 0, 0};
+    const bool prof = PROF && stats != nullptr && tid == 0;
+    long long tk[CH_NTICK] = {0, 0, 0, 0, 0, 0, 0};
+#define CH_TICK(k, dep) do { if (prof) { asm volatile("" :: "v"(dep) : "memory"); tk[k] = (long long)wall_clock64(); } } while (0)
+    CH_TICK(0, tid);
     if (tid == 0) { L.s = 0.0; L.fail = 0; }
     for (int base = 0; base < m; base += CH_T * EPT) {
         if (tid == 0) L.slot_count = 0;
@@ -1160,18 +1263,17 @@ __device__ __forceinline__ double block_chain_sum2(const double* __restrict__ bu
 #pragma unroll
         for (int i = 0; i < EPT; i++) l4[i & 3] += a[i];
         const double loc = (l4[0] + l4[1]) + (l4[2] + l4[3]);  // (prediction only: any order)
-        double inc = loc;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double t = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += t;
-        }
+        CH_TICK(1, loc);
+        const double inc = scan_add_f64<false>(loc);
         if (lane == 63) L.wtot[w] = inc;
         __syncthreads();
-        double wpre = 0.0;
-        for (int k = 0; k < w; k++) wpre += L.wtot[k];
+        // (the 16 waves' totals: one scan inside a row of 16 lanes, by every wave for itself)
+        const double wsc = scan_add_f64<true>(lane < CH_T / 64 ? L.wtot[lane & (CH_T / 64 - 1)] : 0.0);
+        const double wbelow = u2f(readlane_u64(f2u(wsc), wu > 0 ? wu - 1 : 0));
+        const double wpre = wu > 0 ? wbelow : 0.0;
         const double s_in = L.s;
         const double A0 = s_in + (wpre + (inc - loc));
+        CH_TICK(2, A0);
         // 2. the record of the chunk.  The common case - every addend a tie-free constant of ONE predicted binade - is
         //    decided by the thread itself; any other chunk is parked in LDS and its record is worked out by a wave,
         //    lane-parallel (chain_record_wave), so that no wave runs through a 32-step search for one of its threads
@@ -1199,57 +1301,66 @@ __device__ __forceinline__ double block_chain_sum2(const double* __restrict__ bu
         __syncthreads();
         {
             const int ns = L.slot_count < CH_NSLOT ? L.slot_count : CH_NSLOT;
-            for (int sl = w; sl < ns; sl += CH_T / 64) {
-                const double al = lane < EPT ? L.vals[sl][lane < EPT ? lane : 0] : 0.0;
-                const ChRec pr = chain_record_wave(al, L.pend_cnt[sl], L.pend_A0[sl], guard_bits != 0);
-                if (lane == 0) L.prec[sl] = pr;
+            if (ns > 0) {  // (the same for every thread: nothing writes slot_count before the next super-chunk)
+                for (int sl = w; sl < ns; sl += CH_T / 64) {
+                    const double al = lane < EPT ? L.vals[sl][lane < EPT ? lane : 0] : 0.0;
+                    const ChRec pr = chain_record_wave(al, L.pend_cnt[sl], L.pend_A0[sl], guard_bits != 0);
+                    if (lane == 0) L.prec[sl] = pr;
+                }
+                __syncthreads();
+                if (slot >= 0) r = L.prec[slot];
             }
         }
-        __syncthreads();
-        if (slot >= 0) r = L.prec[slot];
-        // 3. segmented scan of the constant pieces: element (reset, value); tailE = binade of the piece a thread leaves open
+        CH_TICK(3, r.kind);
+        // 3. segmented scan of the constant pieces: element (reset, value); tailE = binade of the piece a thread leaves open.
+        //    A CONST chunk whose binade differs from the piece open in front of it resets (ebreak).  The first lane of a wave
+        //    learns that piece only with the waves' summaries: inside the wave it scans as if it continued, and its reset
+        //    (eb0) is applied to the wave's summary and to every lane of the wave afterwards - it can only precede theirs
         const int32_t tailE = r.kind == CHR_CONST ? r.E0 : (r.kind == CHR_SPLIT ? r.E1 : -2);
-        int32_t prevTail = __shfl_up(tailE, 1, 64);
-        L.E[tid] = tailE;
-        __syncthreads();
-        if (lane == 0) prevTail = tid > 0 ? L.E[tid - 1] : -2;
-        const bool ebreak = r.kind == CHR_CONST && prevTail != r.E0;
-        int rr = (r.kind == CHR_SPLIT || r.kind == CHR_SERIAL || ebreak) ? 1 : 0;
+        int32_t prevTail = (int32_t)lane_below_u32((uint32_t)tailE);
+        int rr = (r.kind == CHR_SPLIT || r.kind == CHR_SERIAL || (lane != 0 && r.kind == CHR_CONST && prevTail != r.E0)) ? 1 : 0;
         uint64_t kk = r.kind == CHR_CONST ? r.c0 : (r.kind == CHR_SPLIT ? (r.E1 >= 0 ? r.c1 : 0) : 0);
-        const int r_own = rr;
-        const uint64_t k_own = kk;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int pr = __shfl_up(rr, d, 64);
-            const uint64_t pk = shfl_up_u64(kk, d);
-            if (lane >= d) {
-                if (!rr) { const uint64_t t = pk + kk; kk = t > (1ULL << 60) ? (1ULL << 60) : t; }
-                rr |= pr;
-            }
-        }
-        if (lane == 63) { L.wr[w] = rr; L.wk[w] = kk; }
+        scan_seg<false>(rr, kk);
+        if (lane == 63) { L.wr[w] = rr; L.wk[w] = kk; L.wtail[w] = tailE; }
+        if (lane == 0) L.whead[w] = r.kind == CHR_CONST ? r.E0 : CH_NOHEAD;
         __syncthreads();
-        uint64_t X = 0;
-        for (int q = 0; q < w; q++) { const uint64_t t = X + L.wk[q]; X = L.wr[q] ? L.wk[q] : (t > (1ULL << 60) ? (1ULL << 60) : t); }
-        uint64_t after;
-        { const uint64_t t = X + kk; after = rr ? kk : (t > (1ULL << 60) ? (1ULL << 60) : t); }
-        uint64_t xin = shfl_up_u64(after, 1);
+        // the waves' summaries, in lanes 0 .. 15 of every wave: one more segmented scan inside a row
+        int sr = 0;
+        uint64_t sk = 0;
+        int32_t hq = CH_NOHEAD, tq = -2;
+        if (lane < CH_T / 64) {
+            sr = L.wr[lane]; sk = L.wk[lane]; hq = L.whead[lane];
+            if (lane > 0) tq = L.wtail[lane - 1];
+        }
+        const bool ebq = hq != CH_NOHEAD && tq != hq;
+        sr |= ebq ? 1 : 0;
+        const bool eb0 = ((__ballot(ebq) >> wu) & 1ULL) != 0ULL;
+        scan_seg<true>(sr, sk);
+        const uint64_t xbelow = readlane_u64(sk, wu > 0 ? wu - 1 : 0);
+        const uint64_t X = wu > 0 ? xbelow : 0;  // what is open in front of this wave
+        const int32_t tbelow = readlane_i32(tq, wu);
+        if (lane == 0) prevTail = tbelow;
+        const bool ebreak = r.kind == CHR_CONST && prevTail != r.E0;
+        const uint64_t after = (rr || eb0) ? kk : sat60(X + kk);
+        uint64_t xin = lane_below_u64(after);
         if (lane == 0) xin = X;
-        (void)r_own; (void)k_own;
         // what the walker needs of an event thread: kind, binade and value of what is open in front of it, its own pieces
         const bool evt = r.kind == CHR_SPLIT || r.kind == CHR_SERIAL || (ebreak && xin != 0);
-        __syncthreads();  // (L.E is re-used below)
+        const int lastT = ((m - base < CH_T * EPT ? m - base : CH_T * EPT) - 1) / EPT;
+        const unsigned long long evm = __ballot(evt && tid <= lastT);
+        // (the walker of the previous super-chunk has finished with these arrays: the barrier behind the walk)
         L.E[tid] = prevTail;
         L.flags[tid] = r.kind | (evt ? 4 : 0);
         L.slot[tid] = r.kind == CHR_SERIAL ? slot : r.E0;
         L.own[tid] = r.c0;
         L.sc[tid] = xin;
         L.spv[tid] = r.sp;
-        const int lastT = ((m - base < CH_T * EPT ? m - base : CH_T * EPT) - 1) / EPT;
-        if (tid == lastT) { L.wk[0] = after; L.wr[0] = tailE; }  // (the piece left open at the end of this super-chunk)
+        if (lane == 0) L.emask[w] = evm;
+        if (tid == lastT) { L.open_k = after; L.open_E = tailE; }  // (the piece left open at the end of this super-chunk)
         __syncthreads();
         if (r.kind == CHR_SERIAL && tid <= lastT) cs.mixed++;
-        // 4. the walk: only the event threads, in order
+        CH_TICK(4, tid);
+        // 4. the walk: only the lane groups that hold an event thread, and in them only the event threads, in order
         if (w == 0) {
             uint64_t sb = readfirstlane_u64(f2u(s_in));
             bool ok = true;
@@ -1258,13 +1369,16 @@ __device__ __forceinline__ double block_chain_sum2(const double* __restrict__ bu
                 if (mono_apply_pattern(sb, E, c, c)) cs.runs++;
                 else ok = false;
             };
-            for (int ww = 0; ww < CH_T / 64 && ok; ww++) {
-                if (ww * 64 > lastT) break;
+            const uint64_t gm = lane < CH_T / 64 ? L.emask[lane & (CH_T / 64 - 1)] : 0ULL;
+            unsigned long long groups = __ballot(gm != 0ULL);
+            while (groups && ok) {
+                const int ww = __builtin_ctzll(groups);
+                groups &= groups - 1;
+                unsigned long long em = readlane_u64(gm, ww);
                 const int id = ww * 64 + lane;
                 const int rf = L.flags[id], rEin = L.E[id], rs = L.slot[id];
                 const uint64_t rc0 = L.own[id], rx = L.sc[id];
                 const double rsp = L.spv[id];
-                unsigned long long em = __ballot((rf & 4) != 0 && id <= lastT);
                 while (em && ok) {
                     const int e = __builtin_ctzll(em);
                     em &= em - 1;
@@ -1273,7 +1387,7 @@ __device__ __forceinline__ double block_chain_sum2(const double* __restrict__ bu
                     if (kind == CHR_CONST) apply(Ein, x);  // (a change of binade without a special addend in between)
                     else if (kind == CHR_SPLIT) {
                         const int E0 = sl;
-                        if (E0 >= 0 && E0 == Ein) { const uint64_t t = x + c0; apply(E0, t > (1ULL << 60) ? (1ULL << 60) : t); }
+                        if (E0 >= 0 && E0 == Ein) apply(E0, sat60(x + c0));
                         else { apply(Ein, x); if (E0 >= 0) apply(E0, c0); }
                         if (!ok) break;
                         const double sv = u2f(sb) + u2f(readlane_u64(f2u(rsp), e));
@@ -1291,13 +1405,18 @@ __device__ __forceinline__ double block_chain_sum2(const double* __restrict__ bu
                     }
                 }
             }
-            if (ok) apply((int)L.wr[0], L.wk[0]);
+            if (ok) apply((int)L.open_E, L.open_k);
             if (lane == 0) { L.s = u2f(sb); if (!ok) L.fail = 1; }
         }
         __syncthreads();
+        CH_TICK(5, tid);
         if (L.fail) break;
     }
     __syncthreads();
+    CH_TICK(6, tid);
+    if (prof)
+        for (int k = 0; k < CH_NTICK; k++) g_chain_ticks[k] = tk[k];
+#undef CH_TICK
     if (L.fail) {  // (rare: a mispredicted binade; the first form redoes the whole sum with its own fallbacks)
         ChainStats c1{0, 0, 0, 0};
         const double r1 = block_chain_sum_rare<EPT>(buf, m, guard_bits, &L, stats ? &c1 : nullptr);
@@ -2241,15 +2360,19 @@ __device__ __forceinline__ void chain_workgroup(const Dev& d, ChainLds<CH_EPT>& 
     const unsigned evtag = (unsigned)st->n_events;
     const double usx = block_chain_sum2<CH_EPT>(d.chain, cm, CH_GUARD_BITS, L, nullptr);
     if (threadIdx.x == 0) {
-        // u.Sx and u.nbr.Sx (NetMakerOriginal.java:532, 535): write-through, drained, then the flag - the exact re-sweep of the
-        // SAME launch (the deciding workgroup) waits on that flag before it reads them; every later kernel sees them anyway
+        // u.Sx and u.nbr.Sx (NetMakerOriginal.java:532, 535): write-through, drained, then the flag as a write-through store
+        // by the same lane - the exact re-sweep of the SAME launch (the deciding workgroup) polls that flag, fences on its
+        // own side and only then reads them; every later kernel sees them anyway.  No release fence here: a release is a
+        // write-back of the L2's dirty lines, and every byte handed over has left the L2 already (the form of rec_publish;
+        // MI355X_MICROARCH "Valid forms": write-through payload, s_waitcnt vmcnt(0) in the storing wave, agent-scope flag
+        // store after it, an agent acquire in the consumer between its poll and its loads).  This workgroup writes nothing
+        // else to global memory.
         __hip_atomic_store(reinterpret_cast<uint64_t*>(d.Sx + cU), __builtin_bit_cast(uint64_t, usx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(reinterpret_cast<uint64_t*>(d.Sx + cU + 1), __builtin_bit_cast(uint64_t, usx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // ... and once more at a fixed address (a line this workgroup alone writes): the decide step of this launch prefetches
         // the involved slots' Sx for k_update before this sum is ready, and k_update takes it from here (UpdPre::mask)
         __hip_atomic_store(reinterpret_cast<uint64_t*>(&upre_behind_ticket(d)->usx), __builtin_bit_cast(uint64_t, usx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __threadfence();
         __hip_atomic_store(d.ticket + TRK_FLAG, evtag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
@@ -2719,8 +2842,9 @@ __global__ __launch_bounds__(TRK_THREADS) void k_track(Dev d, int force_base, in
     TRK_TICK(5);
     if (ta.approx && !giveup) {
         // |Q~ - Q| <= eps_u + the roundings of (c-2) D - Sp - Sq, each <= 2^-53 of a term <= (c + 2n) Dmax
-        const double dmax = __builtin_bit_cast(double, st->dmax_bits);
-        const double margin = 2.0 * eps_u + 192.0 * 1.1102230246251565e-16 * ((double)st->n + 4.0) * dmax + 1e-300;
+        // (dmax_bits and n from the LDS copy: constant during a run, and no trip to memory behind the fan-in's atomics)
+        const double dmax = __builtin_bit_cast(double, lst.dmax_bits);
+        const double margin = 2.0 * eps_u + 192.0 * 1.1102230246251565e-16 * ((double)lst.n + 4.0) * dmax + 1e-300;
         const bool certain = (bestu.q - margin > best.q) || (bestu.q == inf_f64());
         if (!certain) {
             // a swept pair may be the minimum: wait for the chain workgroup, sweep again with the exact sum
@@ -2944,10 +3068,12 @@ __global__ __launch_bounds__(CH_T) void k_finalize(Dev d) {
 }
 
 // diagnostic entry: the block chain sum on an arbitrary buffer (tests)
-template <int EPT>
+template <int EPT, bool PROF>
 __global__ __launch_bounds__(CH_T) void k_test_chain(const double* buf, int m, int guard_bits, double* out, ChainStats* stats) {
     __shared__ ChainLds<EPT> L;
-    double r = g_chain_form == 1 ? block_chain_sum<EPT>(buf, m, guard_bits, L, stats) : block_chain_sum2<EPT>(buf, m, guard_bits, L, stats);
+    // (FNN_CHAIN_FORM: 1 the first form, 2 the record form at any size, 3 the short form wherever it fits; otherwise as the engine)
+    const int short_below = g_chain_form == 2 ? 0 : (g_chain_form == 3 ? 64 * EPT + 1 : CH_SHORT_M);
+    double r = g_chain_form == 1 ? block_chain_sum<EPT>(buf, m, guard_bits, L, stats) : block_chain_sum2<EPT, PROF>(buf, m, guard_bits, L, stats, short_below);
     if (threadIdx.x == 0) *out = r;
 }
 
@@ -3361,7 +3487,11 @@ struct HipBackend {
             const bool help = rx_helpers > 0;
             const int fb = (sched || !screen) ? 1 : 0, hs = has_scan ? 1 : 0, tk = ticks ? 1 : 0;
             track_tag = (track_tag % 0x7FFFFFEu) + 1u;  // (never 0: the JOB word starts out as 0)
-            launch(TC_TRACK, tall, help ? k_track<true> : k_track<false>, dim3(track_grid + 1 + (help ? TRK_NHELP : 0)), dim3(TRK_THREADS),
+            // With force_base the kernel serves no window: its chain workgroup and thread 0 of tracking workgroup 0 (la_prepare_base)
+            // are all that works, so the sequence carries ONE tracking workgroup (and the helpers, which count from G) instead of
+            // track_grid workgroups of 1024 threads that return at once.  No ticket is drawn on that path (tgroup is not read).
+            const int tgrid = fb ? 1 : track_grid;
+            launch(TC_TRACK, tall, help ? k_track<true> : k_track<false>, dim3(tgrid + 1 + (help ? TRK_NHELP : 0)), dim3(TRK_THREADS),
                    d, fb, fb, hs, track_group, tk, track_tag);
         }
         if (screen && !has_scan) return 0;  // (a window event: the tail of k_track decides; no decide kernel follows)
@@ -3671,7 +3801,8 @@ int32_t fnn_test_chain_sum(int32_t device, const double* host_buf, int32_t m, in
     if ((e = hipSetDevice(device)) != hipSuccess) return fnn::fail(FNN_EHIP, hipGetErrorString(e));
     // the kernel reads the chunk-interleaved layout the engine's producers write
     const size_t cap = (size_t)fnn::round_up(m > 0 ? m : 1, fnn::CH_SC);
-    std::vector<double> perm(cap, 0.0);
+    // (NaN behind the last addend: a load or a lane that is not masked by m shows in the sum)
+    std::vector<double> perm(cap, std::numeric_limits<double>::quiet_NaN());
     for (int32_t i = 0; i < m; i++) perm[(size_t)fnn::chain_addr(i)] = host_buf[i];
     double* dbuf = nullptr; double* dout = nullptr; fnn::ChainStats* dst = nullptr;
     if (hipMalloc((void**)&dbuf, sizeof(double) * cap) != hipSuccess || hipMalloc((void**)&dout, 8) != hipSuccess ||
@@ -3684,23 +3815,36 @@ int32_t fnn_test_chain_sum(int32_t device, const double* host_buf, int32_t m, in
         int stop = 0;
         if (const char* ev = std::getenv("FNN_CHAIN_STOP")) stop = std::atoi(ev);
         (void)hipMemcpyToSymbol(HIP_SYMBOL(fnn::g_chain_stop_after), &stop, sizeof(int));
-        int form = stop ? 1 : 2;
+        int form = stop ? 1 : 0;
         if (const char* ev = std::getenv("FNN_CHAIN_FORM")) form = std::atoi(ev);
         (void)hipMemcpyToSymbol(HIP_SYMBOL(fnn::g_chain_form), &form, sizeof(int));
+        const long long zero[fnn::CH_NTICK] = {0};
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(fnn::g_chain_ticks), zero, sizeof(zero));
     }
-    hipLaunchKernelGGL(fnn::k_test_chain<fnn::CH_EPT>, dim3(1), dim3(fnn::CH_T), 0, 0, dbuf, m, guard_bits, dout, dst);
+    hipLaunchKernelGGL((fnn::k_test_chain<fnn::CH_EPT, false>), dim3(1), dim3(fnn::CH_T), 0, 0, dbuf, m, guard_bits, dout, dst);
     e = hipDeviceSynchronize();
     if (std::getenv("FNN_CHAIN_TIME")) {  // development aid: average duration of the kernel
         hipEvent_t e0, e1;
         (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
         (void)hipEventRecord(e0, 0);
         for (int i = 0; i < 50; i++)
-            hipLaunchKernelGGL(fnn::k_test_chain<fnn::CH_EPT>, dim3(1), dim3(fnn::CH_T), 0, 0, dbuf, m, guard_bits, dout, dst);
+            hipLaunchKernelGGL((fnn::k_test_chain<fnn::CH_EPT, false>), dim3(1), dim3(fnn::CH_T), 0, 0, dbuf, m, guard_bits, dout, dst);
         (void)hipEventRecord(e1, 0);
         (void)hipEventSynchronize(e1);
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, e0, e1);
         std::fprintf(stderr, "[fnn] k_test_chain m=%d: %.2f us per launch\n", m, ms * 1e3 / 50);
+        // the phase split comes from ONE more launch, of the stamped instantiation (the timed launches carry no stamps)
+        hipLaunchKernelGGL((fnn::k_test_chain<fnn::CH_EPT, true>), dim3(1), dim3(fnn::CH_T), 0, 0, dbuf, m, guard_bits, dout, dst);
+        (void)hipDeviceSynchronize();
+        long long tk[fnn::CH_NTICK] = {0};
+        if (hipMemcpyFromSymbol(tk, HIP_SYMBOL(fnn::g_chain_ticks), sizeof(tk)) == hipSuccess && tk[fnn::CH_NTICK - 1] > tk[0]) {
+            // (record form only; 10 ns per tick)
+            static const char* const name[fnn::CH_NTICK - 1] = {"loads", "prefix", "records", "segscan", "walk", "tail"};
+            std::fprintf(stderr, "[fnn] k_test_chain m=%d phases (us):", m);
+            for (int k = 0; k + 1 < fnn::CH_NTICK; k++) std::fprintf(stderr, " %s %.2f", name[k], (double)(tk[k + 1] - tk[k]) * 1e-2);
+            std::fprintf(stderr, "\n");
+        }
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     }
     fnn::ChainStats hs{0, 0, 0, 0};
@@ -3711,6 +3855,8 @@ int32_t fnn_test_chain_sum(int32_t device, const double* host_buf, int32_t m, in
     if (stats4) { stats4[0] = hs.runs; stats4[1] = hs.mixed; stats4[2] = hs.run_fail; stats4[3] = hs.thread_fail; }
     return FNN_OK;
 }
+
+int32_t fnn_test_chain_short_below(void) { return fnn::CH_SHORT_M; }
 
 int32_t fnn_stream_probe(int32_t device, int64_t bytes, int32_t reps, double* gbps_out) {
     if (bytes < (1 << 20) || reps < 1 || !gbps_out) return fnn::fail(FNN_EINVAL, "fnn_stream_probe: bad arguments");

@@ -376,6 +376,9 @@ int32_t fnn_split_weights_release_cache(void);
  * = {runs applied, chunks added one by one, rejected runs, rejected chunks}. */
 int32_t fnn_test_chain_sum(int32_t device, const double* host_buf, int32_t m, int32_t guard_bits,
                            int32_t ept, double* out, int32_t* stats4);
+/* Diagnostic: sums of fewer addends than this take the short form (one wave, strictly in order; no records, so stats4 is
+ * all zero); from this size on the record form. */
+int32_t fnn_test_chain_short_below(void);
 
 /* Device-side read-only streaming probe: reads `bytes` bytes `reps` times and
  * returns the achieved GB/s (the "measured stream" line next to the nominal
