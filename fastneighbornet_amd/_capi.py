@@ -63,7 +63,7 @@ class FnnSwStats(C.Structure):
 class FnnBatchStats(C.Structure):
     _fields_ = [("n_problems", C.c_int64), ("n_lds", C.c_int64), ("n_fallback", C.c_int64), ("n_events", C.c_int64),
                 ("lds_max_n", C.c_int32), ("block_threads", C.c_int32), ("lds_bytes", C.c_int32), ("chunks", C.c_int32),
-                ("t_upload_s", C.c_double), ("t_kernel_s", C.c_double), ("t_total_s", C.c_double), ("reserved", C.c_int64 * 4)]
+                ("t_upload_s", C.c_double), ("t_kernel_s", C.c_double), ("t_total_s", C.c_double), ("n_global", C.c_int64), ("reserved", C.c_int64 * 3)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
@@ -138,6 +138,8 @@ _BATCH_ARGS = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER
 def bind_batch(a: Api) -> Api:
     """The batch entry points of include/fastnn.h (many small problems, one workgroup each) on `a`."""
     a._fn("batch_lds_max_n", C.c_int32, [])
+    a._fn("batch_global_max_n", C.c_int32, [], optional=True)            # (the CPU driver of the LDS route has neither)
+    a._fn("batch_global_min_batch", C.c_int64, [C.c_int32], optional=True)
     a._fn("canonical_order_batch_f64", C.c_int32, _BATCH_ARGS)
     a._fn("canonical_order_batch_device_f64", C.c_int32, _BATCH_ARGS)
     return a

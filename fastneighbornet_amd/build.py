@@ -13,7 +13,8 @@ SRC_SPLITS = os.path.join(HERE, "csrc", "fnn_splits.hip")  # circular split weig
 SRC_BATCH = os.path.join(HERE, "csrc", "fnn_batch.hip")    # many small problems, one workgroup each
 SOURCES = (SRC, SRC_SPLITS, SRC_BATCH)
 DEPS = [SRC, SRC_SPLITS, SRC_BATCH, os.path.join(HERE, "csrc", "fnn_core.h"), os.path.join(HERE, "csrc", "fnn_engine.h"),
-        os.path.join(HERE, "csrc", "fnn_chain.h"), os.path.join(HERE, "csrc", "fnn_small.h"), os.path.join(ROOT, "include", "fastnn.h")]
+        os.path.join(HERE, "csrc", "fnn_chain.h"), os.path.join(HERE, "csrc", "fnn_small.h"), os.path.join(HERE, "csrc", "fnn_small_global.h"),
+        os.path.join(ROOT, "include", "fastnn.h")]
 
 # -ffp-contract=off: one rounding per fp64 operation on host and device (parity with Java doubles)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
@@ -95,7 +96,7 @@ def build_host(force: bool = False) -> None:
 
 OBJ_DIR = os.path.join(HERE, "csrc", "build")  # objects are kept (git-ignored): a source is recompiled only when it or a header changed
 HEADERS = [os.path.join(HERE, "csrc", "fnn_core.h"), os.path.join(HERE, "csrc", "fnn_engine.h"), os.path.join(HERE, "csrc", "fnn_chain.h"),
-           os.path.join(HERE, "csrc", "fnn_small.h"), os.path.join(ROOT, "include", "fastnn.h")]
+           os.path.join(HERE, "csrc", "fnn_small.h"), os.path.join(HERE, "csrc", "fnn_small_global.h"), os.path.join(ROOT, "include", "fastnn.h")]
 
 
 def toolchain_stamp() -> str:

@@ -107,7 +107,9 @@ def batch_layout(D: np.ndarray):
 
 def canonical_order_batch(D, validate: bool = False, device: int = 0, events: bool = False):
     """Many problems of one size in one call (`fnn_canonical_order_batch_f64`): D has shape (B, n, n).  Up to
-    `fnn_batch_lds_max_n()` taxa every problem runs in a workgroup of its own, out of LDS; larger ones go one by one
+    `fnn_batch_lds_max_n()` taxa (140) every problem runs in a workgroup of its own, out of LDS; up to
+    `fnn_batch_global_max_n()` taxa (1024), given at least `fnn_batch_global_min_batch(n)` problems, likewise with the
+    matrix in a working copy in global memory (D itself is never written); anything else goes problem by problem
     through the one-problem engine.  A numpy array goes to the host entry (its strides are honoured where they amount to a
     row and a problem stride, otherwise it is copied); a torch.float64 tensor on the GPU goes to the device entry after
     torch.cuda.synchronize().  Returns orders[B, n + 1], or (orders, events[B, n], nevents[B]) with events=True."""

@@ -1,16 +1,17 @@
 // fnn_batch.hip -- many small problems in one call: k_small runs one whole Canonical Neighbor-Net problem per workgroup
-// out of LDS (the phase bodies and the host side of the call are fnn_small.h).
+// out of LDS (the phase bodies and the host side of the call are fnn_small.h); k_small_global does
+// the same above the LDS limit with the matrix in a working copy in global memory (fnn_small_global.h).
 //
-// The kernel is a thin wrapper: it carves the dynamic LDS into the view, loads the matrix and hands the phases to
-// small_problem() with an executor whose barrier is __syncthreads().  No cross-workgroup communication, no atomics on the
-// event path, vector stores and plain C++ only.
+// Each kernel is a thin wrapper: it carves the dynamic LDS into the view, loads the matrix and hands the phases to
+// small_problem() / global_problem() with an executor whose barrier is __syncthreads().  No cross-workgroup communication,
+// no atomics on the event path, vector stores and plain C++ only.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <string>
 #include <vector>
 
-#include "fnn_small.h"
+#include "fnn_small_global.h"
 
 namespace fnn {
 
@@ -44,6 +45,46 @@ __global__ __launch_bounds__(1024) void k_small(const double* __restrict__ D, in
     small_load((int)threadIdx.x, (int)blockDim.x, V, D + b * stride, ld, vec);  // (the first phase's barrier covers the load)
     GpuExec ex;
     small_problem(ex, V, ev ? ev + b * n : nullptr, meta + b * SMALL_META_INTS, log + b * n);
+}
+
+// Waves of the workgroup hand matrix entries to each other through GLOBAL memory: a phase's stores must have left the
+// storing wave before the barrier lets another wave load them.  __syncthreads() is a workgroup-scope release, the barrier
+// and a workgroup-scope acquire; for a workgroup on one CU the compiler lowers that release to s_waitcnt lgkmcnt(0) alone
+// (the CU's memory pipeline keeps its waves' accesses in order), so the wait for the vector stores is written out: every
+// wave drains its own stores, then joins the barrier.  It costs nothing in a phase that stored nothing to global memory.
+// (DESIGN.md section 11 records what the kept ISA shows in front of each s_barrier.)
+struct GpuGlobalExec {
+    template <class F>
+    __device__ __forceinline__ void all(F f) {
+        f((int)threadIdx.x, (int)blockDim.x);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    __device__ __forceinline__ void scan_global(const GlobalView& V, int32_t m, int32_t c) {
+        SmallCand b = global_scan_thread((int)threadIdx.x, (int)blockDim.x, V, m, c);
+        for (int off = 32; off > 0; off >>= 1) {
+            SmallCand o;
+            o.q = __shfl_down(b.q, off);
+            o.i = __shfl_down(b.i, off);
+            o.j = __shfl_down(b.j, off);
+            if (small_before(o, b)) b = o;
+        }
+        if ((threadIdx.x & 63) == 0) V.wred[threadIdx.x >> 6] = b;
+        __syncthreads();
+    }
+};
+
+// grid: one workgroup per problem of the chunk; dynamic LDS: small_global_layout(n).bytes.  `work` (neither const nor
+// __restrict__: the workgroup stores to it and loads what it stored) holds the working copies, small_global_pitch(n)
+// doubles apart; src == work: the matrices are there already (host entry), otherwise each is copied in first.
+__global__ __launch_bounds__(1024) void k_small_global(const double* src, int32_t n, int64_t ld, int64_t stride, double* work,
+                                                       int32_t* __restrict__ meta, Agg3Rec* __restrict__ log, Event* __restrict__ ev) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char small_lds[];
+    const int64_t b = blockIdx.x;
+    const GlobalView V = small_global_view(small_lds, work + b * small_global_pitch(n), n);
+    if (src != work) global_copy((int)threadIdx.x, (int)blockDim.x, V, src + b * stride, ld);  // (the first phase's barrier covers the copy)
+    GpuGlobalExec ex;
+    global_problem(ex, V, ev ? ev + b * n : nullptr, meta + b * SMALL_META_INTS, log + b * n);
 }
 
 // the lowest index of a problem whose matrix fails the check, through atomicMin on one word
@@ -122,6 +163,20 @@ struct SmallHipBackend {
         *t_kernel_s = (double)ms * 1e-3;
         return FNN_OK;
     }
+    int32_t run_global(const double* src, int64_t ld, int64_t stride, double* work, int64_t cnt, int32_t n, int32_t threads, int32_t lds_bytes,
+                       int32_t* d_meta, Agg3Rec* d_log, Event* d_ev, double* t_kernel_s) {
+        if (!ok(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_small_global), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
+                "hipFuncSetAttribute"))
+            return FNN_EHIP;
+        if (!ok(hipEventRecord(e0, stream), "hipEventRecord")) return FNN_EHIP;
+        hipLaunchKernelGGL(k_small_global, dim3((unsigned)cnt), dim3((unsigned)threads), (size_t)lds_bytes, stream, src, n, ld, stride, work, d_meta, d_log, d_ev);
+        if (!ok(hipGetLastError(), "k_small_global launch")) return FNN_EHIP;
+        if (!ok(hipEventRecord(e1, stream), "hipEventRecord") || !ok(hipEventSynchronize(e1), "k_small_global")) return FNN_EHIP;
+        float ms = 0.f;
+        if (!ok(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime")) return FNN_EHIP;
+        *t_kernel_s = (double)ms * 1e-3;
+        return FNN_OK;
+    }
     // n above the LDS limit: the one-problem engine, one handle for the whole call
     int32_t fallback(const std::string& W, const double* D, bool on_device, int32_t n, int64_t ld, int64_t stride, int64_t batch,
                      const fnn_opts& opts, int32_t* orders, fnn_event* events, int32_t* nev, fnn_batch_stats& st) {
@@ -170,11 +225,15 @@ struct SmallHipBackend {
 extern "C" {
 
 int32_t fnn_batch_lds_max_n(void) { return fnn::SMALL_LDS_MAX_N; }
+int32_t fnn_batch_global_max_n(void) { return fnn::SMALL_GLOBAL_MAX_N; }
+int64_t fnn_batch_global_min_batch(int32_t n) { return fnn::small_global_min_batch(n); }
 
 int32_t fnn_canonical_order_batch_f64(const double* D, int32_t n, int64_t ld, int64_t stride, int64_t batch, const fnn_opts* opts,
                                       int32_t* orders_out, fnn_event* events_out, int32_t* nevents_out, fnn_batch_stats* stats) {
     FNN_BATCH_TRY(
         fnn::SmallHipBackend be;
+        if (fnn::small_global_route(n, batch))
+            return fnn::small_global_batch(be, "fnn_canonical_order_batch_f64", D, false, n, ld, stride, batch, opts, orders_out, events_out, nevents_out, stats);
         return fnn::small_batch(be, "fnn_canonical_order_batch_f64", D, false, n, ld, stride, batch, opts, orders_out, events_out, nevents_out, stats);
     )
 }
@@ -183,6 +242,8 @@ int32_t fnn_canonical_order_batch_device_f64(const double* d_D, int32_t n, int64
                                              int32_t* orders_out, fnn_event* events_out, int32_t* nevents_out, fnn_batch_stats* stats) {
     FNN_BATCH_TRY(
         fnn::SmallHipBackend be;
+        if (fnn::small_global_route(n, batch))
+            return fnn::small_global_batch(be, "fnn_canonical_order_batch_device_f64", d_D, true, n, ld, stride, batch, opts, orders_out, events_out, nevents_out, stats);
         return fnn::small_batch(be, "fnn_canonical_order_batch_device_f64", d_D, true, n, ld, stride, batch, opts, orders_out, events_out, nevents_out, stats);
     )
 }

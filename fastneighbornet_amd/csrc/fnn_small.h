@@ -487,6 +487,27 @@ FNN_HD void small_problem(Exec& ex, const SmallView& V, Event* gev, int32_t* gme
 // Results go to the caller's arrays only when the whole call has succeeded.
 constexpr int64_t SMALL_CHUNK_BYTES = (int64_t)2 << 30;  // device buffer for matrices per chunk
 
+// One chunk's result records (problems b0 ... b0 + cnt - 1) to orders, event counts and the zero fill behind each problem's
+// last event; shared by the LDS route below and the global-memory route (fnn_small_global.h).
+inline int32_t small_collect(const std::string& W, int32_t n, int64_t b0, int64_t cnt, const int32_t* meta, const Agg3Rec* log,
+                             int32_t* orders, int32_t* nev, fnn_event* evs, fnn_batch_stats& st) {
+    for (int64_t b = 0; b < cnt; b++) {
+        const int32_t* mt = &meta[(size_t)b * SMALL_META_INTS];
+        const std::string P = W + "problem " + std::to_string(b0 + b) + ": ";
+        if (mt[0] != SMALL_OK) return fail(FNN_EHIP, P + "the kernel took an unreachable branch (status " + std::to_string(mt[0]) + ")");
+        const int32_t nn = mt[6];
+        if (mt[1] < 0 || mt[1] > n - 3 || mt[2] < 0 || mt[2] >= n || nn < n || nn > 3 * n) return fail(FNN_EHIP, P + "corrupt result record");
+        for (int k = 3; k < 6; k++) if (mt[k] < 1 || mt[k] > nn) return fail(FNN_EHIP, P + "corrupt result record");
+        const char* why = expand_merge_log(n, nn, &log[(size_t)b * (size_t)n], (size_t)mt[1], mt + 3, &orders[(size_t)(b0 + b) * (size_t)(n + 1)]);
+        if (why) return fail(FNN_ESTATE, P + why);
+        nev[(size_t)(b0 + b)] = mt[2];
+        if (evs)  // (the records past the problem's last event were never written)
+            std::memset(&evs[(size_t)(b0 + b) * (size_t)n + (size_t)mt[2]], 0, sizeof(fnn_event) * (size_t)(n - mt[2]));
+        st.n_events += mt[2];
+    }
+    return FNN_OK;
+}
+
 template <class B>
 int32_t small_batch(B& be, const char* who, const double* D, bool on_device, int32_t n, int64_t ld, int64_t stride, int64_t batch,
                     const fnn_opts* o, int32_t* orders_out, fnn_event* events_out, int32_t* nevents_out, fnn_batch_stats* stats) {
@@ -573,20 +594,8 @@ int32_t small_batch(B& be, const char* who, const double* D, bool on_device, int
                 be.d2h(log.data(), d_log, sizeof(Agg3Rec) * (size_t)n * (size_t)cnt) != FNN_OK ||
                 (d_ev && be.d2h(&evs[(size_t)b0 * (size_t)n], d_ev, sizeof(Event) * (size_t)n * (size_t)cnt) != FNN_OK))
                 return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
-            for (int64_t b = 0; b < cnt; b++) {
-                const int32_t* mt = &meta[(size_t)b * SMALL_META_INTS];
-                const std::string P = W + "problem " + std::to_string(b0 + b) + ": ";
-                if (mt[0] != SMALL_OK) return fail(FNN_EHIP, P + "the kernel took an unreachable branch (status " + std::to_string(mt[0]) + ")");
-                const int32_t nn = mt[6];
-                if (mt[1] < 0 || mt[1] > n - 3 || mt[2] < 0 || mt[2] >= n || nn < n || nn > 3 * n) return fail(FNN_EHIP, P + "corrupt result record");
-                for (int k = 3; k < 6; k++) if (mt[k] < 1 || mt[k] > nn) return fail(FNN_EHIP, P + "corrupt result record");
-                const char* why = expand_merge_log(n, nn, &log[(size_t)b * (size_t)n], (size_t)mt[1], mt + 3, &orders[(size_t)(b0 + b) * (size_t)(n + 1)]);
-                if (why) return fail(FNN_ESTATE, P + why);
-                nev[(size_t)(b0 + b)] = mt[2];
-                if (events_out)  // (the records past the problem's last event were never written)
-                    std::memset(&evs[(size_t)(b0 + b) * (size_t)n + (size_t)mt[2]], 0, sizeof(fnn_event) * (size_t)(n - mt[2]));
-                st.n_events += mt[2];
-            }
+            rc = small_collect(W, n, b0, cnt, meta.data(), log.data(), orders.data(), nev.data(), events_out ? evs.data() : nullptr, st);
+            if (rc != FNN_OK) return rc;
             st.n_lds += cnt;
         }
     }

@@ -244,8 +244,13 @@ int32_t fnn_canonical_order_f64(const double* D, int32_t n, int64_t ld, const fn
  * is the n x n matrix at D + b * stride with row stride ld doubles (ld >= n, stride >= n * ld; padding is never read).
  * For 4 <= n <= fnn_batch_lds_max_n() one kernel launch per chunk runs every problem of the chunk in its own workgroup,
  * entirely out of LDS: same arithmetic contract as above, so every order, every event and every scan
- * minimum is what fnn_canonical_order_f64 gives for that matrix.  Larger n goes, problem by problem, through one fnn_handle that
- * the call creates once (n_fallback counts them); n <= 3 gives identities without touching the device; batch == 0 is FNN_OK.
+ * minimum is what fnn_canonical_order_f64 gives for that matrix.  For fnn_batch_lds_max_n() < n <= fnn_batch_global_max_n()
+ * and batch >= fnn_batch_global_min_batch(n) a second kernel does the same with the matrix in a per-problem working copy in
+ * global memory and everything else in LDS (n_global counts them; block_threads and lds_bytes then describe that kernel);
+ * the caller's matrices are never written: the host entry runs in its own upload buffer, the device entry copies each
+ * problem into a working buffer of the call's (at most 2 GiB, and at least one problem, at a time).  Anything else goes,
+ * problem by problem, through one fnn_handle that the call creates once (n_fallback counts them); n <= 3 gives identities
+ * without touching the device; batch == 0 is FNN_OK.
  * opts: device and validate as for fnn_create - with validate set, the first problem (lowest index) whose matrix is not
  * symmetric, not finite or has a non-zero diagonal fails the whole call with FNN_EINVAL and is named in fnn_last_error();
  * mode FNN_MODE_RELAXED is accepted (it equals Canonical up to 1024 taxa); the events are recorded when events_out is given
@@ -255,15 +260,20 @@ int32_t fnn_canonical_order_f64(const double* D, int32_t n, int64_t ld, const fn
  * orders_out: batch x (n + 1), each row as fnn_run's; events_out: NULL or batch x n records, row b holding nevents_out[b] events
  * (zero-filled behind them); nevents_out: NULL or batch.  The matrices travel in chunks of at most 2 GiB (FNN_BATCH_CHUNK=<problems>
  * overrides the chunk size, for tests; FNN_BATCH_THREADS=256|512|1024 overrides the workgroup size chosen from n, for
+ * tools/batch_perf.py; FNN_BATCH_ROUTE=global sends any 4 <= n <= fnn_batch_global_max_n() and any batch >= 1 to the
+ * global-memory kernel, for tests; FNN_BATCH_ROUTE=engine keeps every n above fnn_batch_lds_max_n() on the handle loop, for
  * tools/batch_perf.py).  The call runs on opts->device and leaves the caller's current HIP device as it found it.  The device variant reads D from device memory in place; like fnn_set_matrix_device it
  * is not ordered against the stream that produced D: synchronise the producer first. */
 typedef struct fnn_batch_stats {
     int64_t n_problems, n_lds, n_fallback, n_events;   /* problems run in LDS / through the one-problem engine; events over all */
     int32_t lds_max_n, block_threads, lds_bytes, chunks;
     double  t_upload_s, t_kernel_s, t_total_s;
-    int64_t reserved[4];
+    int64_t n_global;                                   /* problems run by the global-memory kernel (was reserved[0]) */
+    int64_t reserved[3];
 } fnn_batch_stats;
 int32_t fnn_batch_lds_max_n(void);
+int32_t fnn_batch_global_max_n(void);                   /* the largest n of the global-memory route (1024) */
+int64_t fnn_batch_global_min_batch(int32_t n);          /* the smallest batch that takes it by default at this n */
 int32_t fnn_canonical_order_batch_f64(const double* D, int32_t n, int64_t ld, int64_t stride, int64_t batch,
                                       const fnn_opts* opts, int32_t* orders_out /* batch x (n+1) */,
                                       fnn_event* events_out /* NULL or batch x n */, int32_t* nevents_out /* NULL or batch */,
