@@ -69,6 +69,16 @@ class FnnBatchStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class FnnSwBatchStats(C.Structure):
+    _fields_ = [("n_problems", C.c_int64), ("n_closed_form", C.c_int64), ("n_kernel", C.c_int64), ("n_fallback", C.c_int64),
+                ("max_n", C.c_int32), ("block_threads", C.c_int32), ("lds_bytes", C.c_int32), ("chunks", C.c_int32),
+                ("workspace_bytes", C.c_int64), ("capacity", C.c_int64),
+                ("t_upload_s", C.c_double), ("t_kernel_s", C.c_double), ("t_total_s", C.c_double), ("reserved", C.c_int64 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 EVENT_DTYPE = np.dtype(
     [("m_before", "<i4"), ("c_before", "<i4"), ("cx_id", "<i4"), ("cy_id", "<i4"),
      ("x_id", "<i4"), ("y_id", "<i4"), ("kind", "<i4"), ("u_id", "<i4"),
@@ -166,6 +176,43 @@ def run_batch(a: Api, D, n: int, ld: int, stride: int, batch: int, validate: boo
         e.orders = orders
         raise
     return orders, ev, nev, st
+
+
+_SPLITS_BATCH_ARGS = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _ip, C.c_int32, _dp, C.POINTER(FnnSwStats),
+                      C.POINTER(FnnSwBatchStats)]
+SW_ROUTES = ("closed form", "from below", "reference")
+
+
+def bind_splits_batch(a: Api) -> Api:
+    """The batched split-weight entry points of include/fastnn.h (one workgroup per small problem) on `a`."""
+    a._fn("split_weights_batch_max_n", C.c_int32, [])
+    a._fn("split_weights_batch_min_batch", C.c_int64, [C.c_int32])
+    a._fn("split_weights_batch_f64", C.c_int32, _SPLITS_BATCH_ARGS)
+    a._fn("split_weights_batch_device_f64", C.c_int32, _SPLITS_BATCH_ARGS)
+    return a
+
+
+def run_splits_batch(a: Api, D, n: int, ld: int, stride: int, batch: int, orders, device: int = 0, on_device: bool = False,
+                     allow_inexact: bool = False, fill: float = 0.0):
+    """One batched split-weight call; D = address of problem 0 (host memory, or device memory with on_device), orders =
+    int32 array (batch, n + 1).  Returns (weights[batch, n(n-1)/2], per-problem stats as a numpy record array, call
+    stats); on failure FnnError carries the untouched output array as `.weights` (filled with `fill`)."""
+    orders = np.ascontiguousarray(orders, dtype=np.int32)
+    if orders.shape != (batch, n + 1):
+        raise ValueError(f"orders must have shape ({batch}, {n + 1})")
+    w = np.full((batch, max(n * (n - 1) // 2, 0)), fill, dtype=np.float64)
+    sw = (FnnSwStats * max(batch, 1))()
+    st = FnnSwBatchStats()
+    fn = a.split_weights_batch_device_f64 if on_device else a.split_weights_batch_f64
+    rc = fn(D, n, ld, stride, batch, orders.ctypes.data_as(_ip), device, w.ctypes.data_as(_dp), sw, C.byref(st))
+    if rc == -7 and allow_inexact:   # FNN_EINEXACT: the weights are there; stats say which problems failed their check
+        rc = 0
+    try:
+        a.check(rc)
+    except FnnError as e:
+        e.weights = w
+        raise
+    return w, np.ctypeslib.as_array(sw)[:batch].copy(), st
 
 
 class Handle:

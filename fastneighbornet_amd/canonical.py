@@ -177,6 +177,51 @@ def split_weights(D: np.ndarray, ordering: np.ndarray, device: int = 0, allow_in
     return w, out
 
 
+def split_weights_batch(D, orders, device: int = 0, allow_inexact: bool = False):
+    """Split weights of many problems of one size in one call (`fnn_split_weights_batch_f64`): D has shape (B, n, n), `orders`
+    (B, n + 1) is what `canonical_order_batch` returned for it.  Up to `fnn_split_weights_batch_max_n()` taxa (140) every
+    problem is solved in a workgroup of its own (closed form, else Lawson-Hanson from below); a problem
+    that gives up there, every problem of a larger n, and every call with fewer than `fnn_split_weights_batch_min_batch(n)`
+    problems (the measured crossover: 1 / 4 / 8 / 16 / 32 up to 32 / 64 / 96 / 128 / 140 taxa) goes through the one-problem solver.  A numpy array goes to the
+    host entry (strides honoured as in `canonical_order_batch`), a torch.float64 tensor on the GPU to the device entry after
+    torch.cuda.synchronize().  Returns (W[B, n(n-1)/2], stats): stats is a dict of per-problem numpy arrays (the fields of
+    fnn_sw_stats, and "method" as in `split_weights`); stats["call"] holds the fnn_sw_batch_stats fields.  Raises FnnError as
+    `split_weights` does, the message naming the lowest failing problem; -7 (FNN_EINEXACT) unless allow_inexact."""
+    from . import api
+    a = api()
+    on_device = False
+    if hasattr(D, "is_cuda") and hasattr(D, "data_ptr"):  # a torch tensor
+        import torch
+        if D.dim() != 3 or D.shape[1] != D.shape[2]:
+            raise ValueError("D must have shape (B, n, n)")
+        if D.is_cuda:
+            if D.dtype != torch.float64:
+                raise TypeError("a tensor on the GPU must be torch.float64")
+            D = D.contiguous()
+            torch.cuda.synchronize(D.device)  # the batch call is not ordered against the stream that produced D
+            if D.device.index is not None:
+                device = D.device.index
+            B, n = int(D.shape[0]), int(D.shape[1])
+            ptr, ld, stride, on_device, keep = D.data_ptr(), max(n, 1), max(n * n, 1), True, D
+        else:
+            D = D.numpy()
+    if not on_device:
+        D = np.asarray(D)
+        if D.ndim != 3 or D.shape[1] != D.shape[2]:
+            raise ValueError("D must have shape (B, n, n)")
+        B, n = D.shape[0], D.shape[1]
+        keep, ld, stride = batch_layout(D)
+        ptr = keep.ctypes.data
+    if hasattr(orders, "cpu") and hasattr(orders, "numpy"):
+        orders = orders.cpu().numpy()
+    w, sw, st = _capi.run_splits_batch(a, ptr, n, ld, stride, B, orders, device=device, on_device=on_device, allow_inexact=allow_inexact)
+    del keep
+    out = {k: sw[k].copy() for k in sw.dtype.names if not k.startswith(("reserved", "pad_"))}
+    out["method"] = np.array(_capi.SW_ROUTES, dtype=object)[sw["route"]] if B else np.array([], dtype=object)
+    out["call"] = st.as_dict()
+    return w, out
+
+
 def split_weights_sparse(D: np.ndarray, ordering: np.ndarray, threshold: float = 1e-6, device: int = 0, capacity: int = 0):
     """`fnn_split_weights_sparse_f64`: only the weights above `threshold` (the reference's list, FastNN.java:455-466), as
     (indices[k], weights[k]) in ascending live index.  Returns (indices, weights, stats dict)."""

@@ -379,6 +379,52 @@ int32_t fnn_split_weights_sparse_f64(const double* D, int32_t n, int64_t ld, con
  * pool is also emptied when a device allocation of the solver fails; the order engine's own 10 GiB at 32768 taxa fit beside it.) */
 int32_t fnn_split_weights_release_cache(void);
 
+/* ---- circular split weights of many small problems: one call, one workgroup per problem -----------
+ * The second half of a batched Neighbor-Net run: `batch` problems of the same size n, laid out as for
+ * fnn_canonical_order_batch_f64 (problem b at D + b * stride, row stride ld; ld >= n, stride >= n * ld; padding is never
+ * read, D is never written), with row b of `orderings` (batch x (n + 1), host memory) what the order batch returned for
+ * problem b.  weights_out: batch x n(n-1)/2, row b as fnn_split_weights_f64's weights_out for problem b.
+ * For 2 <= n <= fnn_split_weights_batch_max_n() and batch >= fnn_split_weights_batch_min_batch(n) one kernel launch per
+ * chunk solves every problem of the chunk in a workgroup of its own: the Chepoi-Fichet closed form where it is feasible
+ * (n_closed_form), else Lawson-Hanson from below, one split per step, on an inverse Cholesky factor of the free set that is
+ * appended to and never updated (n_kernel), followed by the same Kuhn-Tucker certificate as the one-problem call, computed
+ * from the weights with the prefix-sum operators alone.  A problem whose free set outgrows the per-problem factor
+ * (`capacity` splits: min(n(n-1)/2, 6 n); FNN_SW_BATCH_CAP=<splits> lowers it, for tests), that exceeds 40 n + 1000 steps
+ * or that ends uncertified gives up inside the kernel and goes, like every problem of a call with n above the limit, through
+ * fnn_split_weights_f64 (n_fallback) - nearly circular metrics take that way.  The optimum is unique, so both ways meet.
+ * stats_out (NULL or batch records): route, certified, kkt_violation, outer_iterations (steps: ONE split enters per step),
+ * entered, departed, n_set_aside, free_set_peak, capacity, nsplits, final_threshold_rel from the kernel for its own problems,
+ * the whole record from the one-problem solver for the others.
+ * batch == 0 is FNN_OK.  n < 2, a bad layout or a row of `orderings` that is not a permutation of 1..n is FNN_EINVAL, and so
+ * is a NaN or an infinity among the distances that an ordering selects (found by the kernel); a one-problem solve that
+ * fails with FNN_ECAPACITY or FNN_EHIP fails the call with that status; fnn_last_error() names the lowest failing problem
+ * and the output arrays are untouched: they are written when all problems are done.  FNN_EINEXACT: the outputs ARE filled,
+ * and at least one problem of the one-problem solver returned weights that failed its check (stats_out[b].certified).
+ * Two calls on the same input give the same bits.  The workspace travels in chunks of at most 2 GiB and at least one problem
+ * (workspace_bytes; FNN_BATCH_CHUNK=<problems> overrides the chunk size, for tests; FNN_BATCH_THREADS=256|512|1024 the
+ * workgroup size chosen from n, for tools/splits_batch_perf.py; FNN_SW_BATCH_ROUTE=kernel sends any batch >= 1 of
+ * n <= fnn_split_weights_batch_max_n() to the kernel, FNN_SW_BATCH_ROUTE=loop keeps every call on the one-problem solver).
+ * fnn_split_weights_batch_min_batch(n) is the measured crossover: 1 up to 32 taxa, 4 up to 64, 8 up to
+ * 96, 16 up to 128, 32 above - a workgroup takes as long for one problem as for 256, the one-problem call costs 15-37 ms.  The call runs on `device` and leaves the caller's current HIP
+ * device as it found it.  The device variant reads D from device memory in place; it is not ordered against the stream that
+ * produced D: synchronise the producer first. */
+typedef struct fnn_sw_batch_stats {
+    int64_t n_problems, n_closed_form, n_kernel, n_fallback;   /* kernel: solved from below inside the workgroup */
+    int32_t max_n, block_threads, lds_bytes, chunks;
+    int64_t workspace_bytes, capacity;                          /* per-call workspace; splits the per-problem factor holds */
+    double  t_upload_s, t_kernel_s, t_total_s;
+    int64_t reserved[4];
+} fnn_sw_batch_stats;
+int32_t fnn_split_weights_batch_max_n(void);
+int64_t fnn_split_weights_batch_min_batch(int32_t n);   /* the smallest batch that takes the kernel by default at this n */
+int32_t fnn_split_weights_batch_f64(const double* D, int32_t n, int64_t ld, int64_t stride, int64_t batch,
+                                    const int32_t* orderings /* batch x (n+1) */, int32_t device,
+                                    double* weights_out /* batch x n(n-1)/2 */,
+                                    fnn_sw_stats* stats_out /* NULL or batch */, fnn_sw_batch_stats* stats /* may be NULL */);
+int32_t fnn_split_weights_batch_device_f64(const double* d_D, int32_t n, int64_t ld, int64_t stride, int64_t batch,
+                                           const int32_t* orderings, int32_t device, double* weights_out,
+                                           fnn_sw_stats* stats_out, fnn_sw_batch_stats* stats);
+
 /* Diagnostic: the exact block-parallel evaluation of the sequential fp64 sum
  * (((0 + b[0]) + b[1]) + ...) used for ComputeRx / u.Sx (NetMakerOriginal.java:551-560,
  * :532), run on an arbitrary host buffer.  ept = addends per thread (32, fixed by the
