@@ -215,6 +215,88 @@ def run_splits_batch(a: Api, D, n: int, ld: int, stride: int, batch: int, orders
     return w, np.ctypeslib.as_array(sw)[:batch].copy(), st
 
 
+_lp = C.POINTER(C.c_int64)
+_RAGGED_ARGS = [C.c_void_p, _lp, _ip, _lp, C.c_int64, C.POINTER(FnnOpts), _ip, C.c_void_p, _ip, C.POINTER(FnnBatchStats)]
+_SPLITS_RAGGED_ARGS = [C.c_void_p, _lp, _ip, _lp, C.c_int64, _ip, C.c_int32, _dp, C.POINTER(FnnSwStats), C.POINTER(FnnSwBatchStats)]
+
+
+def bind_ragged(a: Api) -> Api:
+    """The ragged entry points of include/fastnn.h (problems of different sizes in one call) on `a`."""
+    a._fn("canonical_order_ragged_f64", C.c_int32, _RAGGED_ARGS)
+    a._fn("canonical_order_ragged_device_f64", C.c_int32, _RAGGED_ARGS)
+    a._fn("split_weights_ragged_f64", C.c_int32, _SPLITS_RAGGED_ARGS)
+    a._fn("split_weights_ragged_device_f64", C.c_int32, _SPLITS_RAGGED_ARGS)
+    return a
+
+
+def ragged_layout(offsets, ns, lds):
+    """(offsets, n, ld) as the contiguous int64 / int32 / int64 arrays the ragged calls take; lds may be None."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    ns = np.ascontiguousarray(ns, dtype=np.int32)
+    lds = None if lds is None else np.ascontiguousarray(lds, dtype=np.int64)
+    if offsets.shape != ns.shape or offsets.ndim != 1 or (lds is not None and lds.shape != ns.shape):
+        raise ValueError("offsets, n and ld must be one-dimensional arrays of one length")
+    return offsets, ns, lds
+
+
+def run_ragged(a: Api, D, offsets, ns, lds=None, validate: bool = False, device: int = 0, events: bool = False,
+               on_device: bool = False, fill: int = 0):
+    """One ragged order call; D = the base address (host memory, or device memory with on_device), problem b at
+    D + 8 * offsets[b] with row stride lds[b] (None: ns[b]).  Returns (orders, events or None, nevents[batch], stats): orders and
+    events are lists of per-problem views of the concatenated arrays; on failure FnnError carries the untouched
+    concatenated output array as `.orders` (filled with `fill`)."""
+    offsets, ns, lds = ragged_layout(offsets, ns, lds)
+    batch = len(ns)
+    pos = np.maximum(ns.astype(np.int64), 0)
+    oo = np.concatenate([[0], np.cumsum(pos + 1)])
+    eo = np.concatenate([[0], np.cumsum(pos)])
+    orders = np.full(max(int(oo[-1]), 1), fill, dtype=np.int32)
+    ev = np.zeros(max(int(eo[-1]), 1), dtype=EVENT_DTYPE) if events else None
+    nev = np.full(batch, fill, dtype=np.int32)
+    opts = FnnOpts()
+    opts.device = device
+    opts.validate = 1 if validate else 0
+    st = FnnBatchStats()
+    fn = a.canonical_order_ragged_device_f64 if on_device else a.canonical_order_ragged_f64
+    rc = fn(D, offsets.ctypes.data_as(_lp), ns.ctypes.data_as(_ip), None if lds is None else lds.ctypes.data_as(_lp), batch,
+            C.byref(opts), orders.ctypes.data_as(_ip), ev.ctypes.data if events else None, nev.ctypes.data_as(_ip), C.byref(st))
+    try:
+        a.check(rc)
+    except FnnError as e:
+        e.orders = orders
+        raise
+    return ([orders[oo[b]:oo[b + 1]] for b in range(batch)],
+            [ev[eo[b]:eo[b + 1]] for b in range(batch)] if events else None, nev, st)
+
+
+def run_splits_ragged(a: Api, D, offsets, ns, orders, lds=None, device: int = 0, on_device: bool = False,
+                      allow_inexact: bool = False, fill: float = 0.0):
+    """One ragged split-weight call; layout as run_ragged's, orders = one int32 array of ns[b] + 1 entries per problem.
+    Returns (weights: list of per-problem views of the concatenated array, per-problem stats as a numpy record array, call
+    stats); on failure FnnError carries the untouched concatenated output array as `.weights` (filled with `fill`)."""
+    offsets, ns, lds = ragged_layout(offsets, ns, lds)
+    batch = len(ns)
+    if len(orders) != batch or any(len(o) != n + 1 for o, n in zip(orders, ns)):
+        raise ValueError("orders must hold one array of n[b] + 1 entries per problem")
+    cat = np.ascontiguousarray(np.concatenate([np.asarray(o, dtype=np.int32) for o in orders]) if batch else np.zeros(0, np.int32))
+    pos = np.maximum(ns.astype(np.int64), 0)
+    wo = np.concatenate([[0], np.cumsum(pos * (pos - 1) // 2)])
+    w = np.full(max(int(wo[-1]), 1), fill, dtype=np.float64)
+    sw = (FnnSwStats * max(batch, 1))()
+    st = FnnSwBatchStats()
+    fn = a.split_weights_ragged_device_f64 if on_device else a.split_weights_ragged_f64
+    rc = fn(D, offsets.ctypes.data_as(_lp), ns.ctypes.data_as(_ip), None if lds is None else lds.ctypes.data_as(_lp), batch,
+            cat.ctypes.data_as(_ip), device, w.ctypes.data_as(_dp), sw, C.byref(st))
+    if rc == -7 and allow_inexact:   # FNN_EINEXACT: the weights are there; stats say which problems failed their check
+        rc = 0
+    try:
+        a.check(rc)
+    except FnnError as e:
+        e.weights = w
+        raise
+    return [w[wo[b]:wo[b + 1]] for b in range(batch)], np.ctypeslib.as_array(sw)[:batch].copy(), st
+
+
 class Handle:
     """Thin RAII wrapper over an engine handle of either library."""
 

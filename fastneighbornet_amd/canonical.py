@@ -222,6 +222,93 @@ def split_weights_batch(D, orders, device: int = 0, allow_inexact: bool = False)
     return w, out
 
 
+def ragged_layout(mats):
+    """(base address, offsets, n, ld, on_device, device or None, keep) for a sequence of square matrices of any sizes: numpy
+    arrays (host entry), or torch.float64 tensors that are all on one GPU (device entry, after torch.cuda.synchronize()).
+    A matrix is used where it lies when it is float64 with unit column stride and a row stride of whole doubles (ld >= n);
+    anything else is copied.  Offsets count doubles from the lowest address; `keep` holds what the addresses point into."""
+    mats = list(mats)
+    on_device = bool(mats) and all(hasattr(m, "is_cuda") and m.is_cuda for m in mats)
+    keep, addr, ns, lds, device = [], [], [], [], None
+    if on_device:
+        import torch
+        if len({m.device for m in mats}) != 1:
+            raise ValueError("the tensors must be on one GPU")
+        device = mats[0].device.index
+        for m in mats:
+            if m.dim() != 2 or m.shape[0] != m.shape[1]:
+                raise ValueError("every matrix must be square")
+            if m.dtype != torch.float64:
+                raise TypeError("a tensor on the GPU must be torch.float64")
+            n = int(m.shape[0])
+            if n > 0 and not (m.stride(1) == 1 and m.stride(0) >= n):
+                m = m.contiguous()
+            keep.append(m)
+            addr.append(m.data_ptr())
+            ns.append(n)
+            lds.append(max(int(m.stride(0)), n) if n > 1 else max(n, 1))
+        torch.cuda.synchronize(mats[0].device)  # the call is not ordered against the stream that produced the tensors
+    else:
+        for m in mats:
+            if hasattr(m, "is_cuda") and hasattr(m, "numpy"):
+                m = m.cpu().numpy()
+            m = np.asarray(m)
+            if m.ndim != 2 or m.shape[0] != m.shape[1]:
+                raise ValueError("every matrix must be square")
+            n = m.shape[0]
+            if not (m.dtype == np.float64 and m.dtype.isnative and m.flags.aligned and
+                    (n <= 1 or (m.strides[1] == 8 and m.strides[0] % 8 == 0 and m.strides[0] // 8 >= n))):
+                m = np.ascontiguousarray(m, dtype=np.float64)
+            keep.append(m)
+            addr.append(m.ctypes.data)
+            ns.append(n)
+            lds.append(m.strides[0] // 8 if n > 1 else max(n, 1))
+    base = min(addr) if addr else 0
+    if any((p - base) % 8 for p in addr):  # (numpy and torch allocate doubles on 8-byte boundaries; a view into a byte buffer may not be)
+        raise ValueError("the matrices are not on 8-byte boundaries relative to each other")
+    offsets = np.array([(p - base) // 8 for p in addr], dtype=np.int64)
+    return base, offsets, np.array(ns, dtype=np.int32), np.array(lds, dtype=np.int64), on_device, device, keep
+
+
+def canonical_order_ragged(mats, validate: bool = False, device: int = 0, events: bool = False):
+    """Many problems of DIFFERENT sizes in one call (`fnn_canonical_order_ragged_f64`): `mats` is a
+    sequence of square fp64 matrices, e.g. per-gene matrices over alignments with missing taxa.  Every problem gets exactly
+    the order that `canonical_order_batch` gives it in a batch of its own size; up to `fnn_batch_lds_max_n()` taxa (140) the
+    problems of all sizes share a few kernel launches, larger ones are grouped by size and take that call's route.  numpy
+    arrays go to the host entry; torch.float64 tensors that are all on one GPU go to the device entry.  Returns a list of
+    orders (n_b + 1 entries each), or (orders, events, nevents) with events=True: a list of event arrays, each cut to its
+    problem's event count, and the counts."""
+    from . import api
+    a = api()
+    base, offsets, ns, lds, on_device, dev, keep = ragged_layout(mats)
+    orders, ev, nev, _ = _capi.run_ragged(a, base, offsets, ns, lds, validate=validate, device=device if dev is None else dev,
+                                          events=events, on_device=on_device)
+    del keep
+    orders = [o.copy() for o in orders]
+    return (orders, [e[:k].copy() for e, k in zip(ev, nev)], nev) if events else orders
+
+
+def split_weights_ragged(mats, orders, device: int = 0, allow_inexact: bool = False):
+    """Split weights of many problems of different sizes in one call (`fnn_split_weights_ragged_f64`): `mats` as for
+    `canonical_order_ragged`, `orders` what it returned.  Every problem of up to `fnn_split_weights_batch_max_n()` taxa (140)
+    is solved in a workgroup of its own, with the weights `split_weights_batch` gives it bit for bit, when the call holds at
+    least `fnn_split_weights_batch_min_batch(largest such n)` of them; the rest, and what gives up in the kernel, goes through
+    the one-problem solver.  Returns (weights, stats): a list of weight arrays (n_b (n_b - 1) / 2 each) and a dict of
+    per-problem numpy arrays as `split_weights_batch` returns it, stats["call"] holding the fnn_sw_batch_stats fields.
+    Raises FnnError as `split_weights_batch` does, the message naming the lowest failing problem."""
+    from . import api
+    a = api()
+    base, offsets, ns, lds, on_device, dev, keep = ragged_layout(mats)
+    orders = [o.cpu().numpy() if hasattr(o, "cpu") and hasattr(o, "numpy") else np.asarray(o) for o in orders]
+    w, sw, st = _capi.run_splits_ragged(a, base, offsets, ns, orders, lds, device=device if dev is None else dev, on_device=on_device,
+                                        allow_inexact=allow_inexact)
+    del keep
+    out = {k: sw[k].copy() for k in sw.dtype.names if not k.startswith(("reserved", "pad_"))}
+    out["method"] = np.array(_capi.SW_ROUTES, dtype=object)[sw["route"]] if len(ns) else np.array([], dtype=object)
+    out["call"] = st.as_dict()
+    return [x.copy() for x in w], out
+
+
 def split_weights_sparse(D: np.ndarray, ordering: np.ndarray, threshold: float = 1e-6, device: int = 0, capacity: int = 0):
     """`fnn_split_weights_sparse_f64`: only the weights above `threshold` (the reference's list, FastNN.java:455-466), as
     (indices[k], weights[k]) in ascending live index.  Returns (indices, weights, stats dict)."""

@@ -10,11 +10,14 @@
 // together through an executor: on the GPU (fnn_batch.hip) `all(f)` is f(threadIdx.x, blockDim.x) followed by
 // __syncthreads(); in the CPU driver of the tests (tests/emu/fnn_batch_emu.cpp) it is a loop over tid.  The
 // host side of the batch call (argument checks, chunking, validation, expansion) is small_batch<B>() below,
-// shared by both in the same way Engine<B> is.
+// shared by both in the same way Engine<B> is; small_ragged<B>() behind it is the same for problems of different sizes.
 #ifndef FNN_SMALL_H
 #define FNN_SMALL_H
 
 #include <stdint.h>
+
+#include <algorithm>
+#include <map>
 
 #include "fnn_engine.h"
 
@@ -489,17 +492,24 @@ constexpr int64_t SMALL_CHUNK_BYTES = (int64_t)2 << 30;  // device buffer for ma
 
 // One chunk's result records (problems b0 ... b0 + cnt - 1) to orders, event counts and the zero fill behind each problem's
 // last event; shared by the LDS route below and the global-memory route (fnn_small_global.h).
+// one problem's result record (mt: its SMALL_META_INTS words, log: its merge log) to its order; the caller's index is `b`
+inline int32_t small_collect_one(const std::string& W, int32_t n, int64_t b, const int32_t* mt, const Agg3Rec* log, int32_t* order) {
+    const std::string P = W + "problem " + std::to_string(b) + ": ";
+    if (mt[0] != SMALL_OK) return fail(FNN_EHIP, P + "the kernel took an unreachable branch (status " + std::to_string(mt[0]) + ")");
+    const int32_t nn = mt[6];
+    if (mt[1] < 0 || mt[1] > n - 3 || mt[2] < 0 || mt[2] >= n || nn < n || nn > 3 * n) return fail(FNN_EHIP, P + "corrupt result record");
+    for (int k = 3; k < 6; k++) if (mt[k] < 1 || mt[k] > nn) return fail(FNN_EHIP, P + "corrupt result record");
+    const char* why = expand_merge_log(n, nn, log, (size_t)mt[1], mt + 3, order);
+    if (why) return fail(FNN_ESTATE, P + why);
+    return FNN_OK;
+}
+
 inline int32_t small_collect(const std::string& W, int32_t n, int64_t b0, int64_t cnt, const int32_t* meta, const Agg3Rec* log,
                              int32_t* orders, int32_t* nev, fnn_event* evs, fnn_batch_stats& st) {
     for (int64_t b = 0; b < cnt; b++) {
         const int32_t* mt = &meta[(size_t)b * SMALL_META_INTS];
-        const std::string P = W + "problem " + std::to_string(b0 + b) + ": ";
-        if (mt[0] != SMALL_OK) return fail(FNN_EHIP, P + "the kernel took an unreachable branch (status " + std::to_string(mt[0]) + ")");
-        const int32_t nn = mt[6];
-        if (mt[1] < 0 || mt[1] > n - 3 || mt[2] < 0 || mt[2] >= n || nn < n || nn > 3 * n) return fail(FNN_EHIP, P + "corrupt result record");
-        for (int k = 3; k < 6; k++) if (mt[k] < 1 || mt[k] > nn) return fail(FNN_EHIP, P + "corrupt result record");
-        const char* why = expand_merge_log(n, nn, &log[(size_t)b * (size_t)n], (size_t)mt[1], mt + 3, &orders[(size_t)(b0 + b) * (size_t)(n + 1)]);
-        if (why) return fail(FNN_ESTATE, P + why);
+        const int32_t rc = small_collect_one(W, n, b0 + b, mt, &log[(size_t)b * (size_t)n], &orders[(size_t)(b0 + b) * (size_t)(n + 1)]);
+        if (rc != FNN_OK) return rc;
         nev[(size_t)(b0 + b)] = mt[2];
         if (evs)  // (the records past the problem's last event were never written)
             std::memset(&evs[(size_t)(b0 + b) * (size_t)n + (size_t)mt[2]], 0, sizeof(fnn_event) * (size_t)(n - mt[2]));
@@ -599,6 +609,238 @@ int32_t small_batch(B& be, const char* who, const double* D, bool on_device, int
             st.n_lds += cnt;
         }
     }
+    std::memcpy(orders_out, orders.data(), sizeof(int32_t) * orders.size());
+    if (events_out) std::memcpy(events_out, evs.data(), sizeof(fnn_event) * evs.size());
+    if (nevents_out) std::memcpy(nevents_out, nev.data(), sizeof(int32_t) * nev.size());
+    st.t_total_s = now_s() - t0;
+    if (stats) *stats = st;
+    return FNN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ ragged batches
+// Problems of different sizes in one call.  A workgroup of k_small_ragged / k_small_splits_ragged
+// reads ONE descriptor and runs the unchanged small_problem() / small_splits_problem() on it.  All offsets count
+// elements of the array they point into, from that array's base.
+struct RaggedDesc {
+    int64_t src, ld;         // the matrix: offset from the base pointer and row stride, in doubles
+    int64_t id;              // the caller's index of the problem
+    int64_t meta;            // result record: int32 words (orders), SplitsMeta records (weights)
+    int64_t log, ev;         // orders: merge log (Agg3Rec) and events (Event)
+    int64_t ord, out, work;  // weights: ordering (int32), weights and workspace slice (doubles)
+    int32_t n, vec, cap, pad_;  // vec: dense and 16-byte aligned, read by 16-byte loads; cap: splits the factor holds
+};
+static_assert(sizeof(RaggedDesc) == 88, "descriptor layout");
+
+// One launch: descriptors first ... first + count - 1 of the chunk's sorted array, one block size, one dynamic-LDS size.
+struct RaggedClass { int64_t first, count; int32_t threads, lds_bytes; };
+
+constexpr int32_t RAGGED_CU_THREADS = 2048;  // 32 waves per CU
+constexpr int32_t RAGGED_MAX_CLASSES = 8;
+
+inline int32_t ragged_threads(int32_t n) {
+    if (const char* e = std::getenv("FNN_BATCH_THREADS")) { int v = std::atoi(e); if (v == 256 || v == 512 || v == 1024) return v; }
+    return small_block_threads(n);
+}
+// Workgroups of this shape that one CU holds at a time, rounded down to a power of two: the class key next to the block size.
+inline int32_t ragged_resident(int32_t threads, int32_t lds_bytes) {
+    int32_t r = SMALL_LDS_CAP / lds_bytes;
+    if (r > RAGGED_CU_THREADS / threads) r = RAGGED_CU_THREADS / threads;
+    int32_t p = 1;
+    while (2 * p <= r) p *= 2;
+    return p;
+}
+
+// Sorts a chunk's descriptors by descending n (ties: the caller's index) and cuts them into classes wherever the block
+// size or the residency step changes.  Both are monotone in n, so a class is a range of n: it never straddles 64|65 or
+// 96|97, and a problem is never launched under a reservation that halves the workgroups per CU its own size allows.  A
+// class reserves the LDS of its largest member.  lds_of(desc) = the problem's own dynamic LDS in bytes.
+template <class LdsOf>
+inline void ragged_classes(std::vector<RaggedDesc>& d, LdsOf lds_of, std::vector<RaggedClass>& out) {
+    std::sort(d.begin(), d.end(), [](const RaggedDesc& a, const RaggedDesc& b) { return a.n != b.n ? a.n > b.n : a.id < b.id; });
+    out.clear();
+    int32_t key_t = 0, key_r = 0;
+    for (size_t k = 0; k < d.size(); k++) {
+        const int32_t t = ragged_threads(d[k].n), bytes = lds_of(d[k]), r = ragged_resident(t, bytes);
+        if (out.empty() || t != key_t || r != key_r) {
+            out.push_back(RaggedClass{(int64_t)k, 0, t, bytes});
+            key_t = t; key_r = r;
+        }
+        out.back().count++;
+        if (bytes > out.back().lds_bytes) out.back().lds_bytes = bytes;
+    }
+}
+
+// Consecutive runs of `items` (indices into the caller's arrays), each at most max_count problems and max_bytes bytes of
+// bytes_of(index), at least one problem: cut[c] ... cut[c + 1] - 1 is chunk c.  FNN_BATCH_CHUNK=<problems> is honoured.
+template <class BytesOf>
+inline std::vector<int64_t> ragged_chunks(const std::vector<int64_t>& items, BytesOf bytes_of) {
+    int64_t max_count = INT64_MAX;
+    if (const char* e = std::getenv("FNN_BATCH_CHUNK")) { long long v = std::atoll(e); if (v >= 1) max_count = v; }
+    std::vector<int64_t> cut{0};
+    int64_t bytes = 0, count = 0;
+    for (size_t k = 0; k < items.size(); k++) {
+        const int64_t w = bytes_of(items[k]);
+        if (count > 0 && (count >= max_count || bytes + w > SMALL_CHUNK_BYTES)) { cut.push_back((int64_t)k); bytes = 0; count = 0; }
+        bytes += w; count++;
+    }
+    cut.push_back((int64_t)items.size());
+    return cut;
+}
+
+// fnn_canonical_order_ragged[_device]_f64 over a backend B (HIP: fnn_batch.hip; CPU driver: tests/emu/fnn_ragged_emu.cpp):
+// small_batch's open / alloc / h2d / d2h / err and
+//   validate_ragged(base, d_desc, cnt, &bad)        bad = the lowest caller's index whose matrix fails the check, or -1
+//   run_ragged(base, d_desc, classes, ncls, d_meta, d_log, d_ev, &t_kernel_s)     one launch per class
+//   large(W, D, on_device, n, offs, lds, cnt, opts, run, orders, events, nev, &stats, &bad)
+//       cnt problems of ONE size above the LDS limit through the same-size entry (which picks the global-memory kernel or
+//       the one-problem engine by its own rule); bad = index into offs of the lowest problem that fails the check, or -1;
+//       run == false: the check alone
+// Problem b is the ns[b] x ns[b] matrix at D + offsets[b] with row stride lds[b] (lds == NULL: ns[b]).  Outputs are
+// concatenated in the caller's order, whatever order the device runs the problems in.
+template <class B>
+int32_t small_ragged(B& be, const char* who, const double* D, bool on_device, const int64_t* offsets, const int32_t* ns, const int64_t* lds,
+                     int64_t batch, const fnn_opts* o, int32_t* orders_out, fnn_event* events_out, int32_t* nevents_out, fnn_batch_stats* stats) {
+    const double t0 = now_s();
+    const std::string W = std::string(who) + ": ";
+    fnn_batch_stats st{};
+    st.lds_max_n = SMALL_LDS_MAX_N;
+    if (batch < 0) return fail(FNN_EINVAL, W + "batch < 0");
+    fnn_opts opts{};
+    if (o) opts = *o;
+    if (opts.mode != FNN_MODE_CANONICAL && opts.mode != FNN_MODE_RELAXED) return fail(FNN_EINVAL, W + "unknown mode");
+    if (batch == 0) { if (stats) *stats = st; return FNN_OK; }
+    if (!offsets || !ns || !orders_out) return fail(FNN_EINVAL, W + "NULL argument");
+    auto ld_of = [&](int64_t b) { return lds ? lds[b] : (int64_t)ns[b]; };
+    std::vector<int64_t> oo((size_t)batch + 1, 0), eo((size_t)batch + 1, 0);  // where problem b's order and events start
+    std::vector<int64_t> kern;                                                // kernel range, in the caller's order
+    std::map<int32_t, std::vector<int64_t>> large;                            // above it, by size
+    for (int64_t b = 0; b < batch; b++) {
+        const int32_t n = ns[b];
+        if (n < 0) return fail(FNN_EINVAL, W + "problem " + std::to_string(b) + ": n < 0");
+        if (ld_of(b) < n) return fail(FNN_EINVAL, W + "problem " + std::to_string(b) + ": needs ld >= n");
+        if (n > 0 && !D) return fail(FNN_EINVAL, W + "NULL argument");
+        oo[(size_t)b + 1] = oo[(size_t)b] + n + 1;
+        eo[(size_t)b + 1] = eo[(size_t)b] + n;
+        if (n > SMALL_LDS_MAX_N) large[n].push_back(b);
+        else if (n > 3) kern.push_back(b);
+    }
+    st.n_problems = batch;
+    std::vector<int32_t> orders((size_t)oo[(size_t)batch]);
+    std::vector<fnn_event> evs(events_out ? (size_t)eo[(size_t)batch] : 0);  // (zero: the fill behind each problem's last event)
+    std::vector<int32_t> nev((size_t)batch, 0);
+    for (int64_t b = 0; b < batch; b++)
+        if (ns[b] <= 3)  // NetMakerOriginal.java:133-140: the identity, no device needed
+            for (int32_t i = 0; i <= ns[b]; i++) orders[(size_t)(oo[(size_t)b] + i)] = i;
+    int64_t bad = -1;  // the lowest caller's index that fails the check
+    int32_t rc;
+    if (!kern.empty() || !large.empty()) {
+        rc = be.open(opts.device);
+        if (rc != FNN_OK) return fail(rc, W + be.err());
+    }
+    if (!kern.empty()) {
+        auto pitch_of = [&](int64_t b) { return round_up((int64_t)ns[b] * ns[b], 2); };  // every problem 16-byte aligned in the image
+        const std::vector<int64_t> cut = ragged_chunks(kern, [&](int64_t b) { return 8 * pitch_of(b); });
+        int64_t mcnt = 0, mrec = 0, mimg = 0;  // the largest chunk: problems, log / event records, doubles of the image
+        for (size_t c = 0; c + 1 < cut.size(); c++) {
+            int64_t rec = 0, img = 0;
+            for (int64_t k = cut[c]; k < cut[c + 1]; k++) { rec += ns[kern[(size_t)k]]; img += pitch_of(kern[(size_t)k]); }
+            mcnt = std::max(mcnt, cut[c + 1] - cut[c]); mrec = std::max(mrec, rec); mimg = std::max(mimg, img);
+        }
+        int32_t* d_meta = (int32_t*)be.alloc(sizeof(int32_t) * SMALL_META_INTS * (size_t)mcnt);
+        Agg3Rec* d_log = (Agg3Rec*)be.alloc(sizeof(Agg3Rec) * (size_t)mrec);
+        Event* d_ev = events_out ? (Event*)be.alloc(sizeof(Event) * (size_t)mrec) : nullptr;
+        RaggedDesc* d_desc = (RaggedDesc*)be.alloc(sizeof(RaggedDesc) * (size_t)mcnt);
+        double* dD = on_device ? nullptr : (double*)be.alloc(sizeof(double) * (size_t)mimg);
+        if (!d_meta || !d_log || (events_out && !d_ev) || !d_desc || (!on_device && !dD)) return fail(FNN_ENOMEM, W + "device allocation failed");
+        std::vector<double> pack(on_device ? 0 : (size_t)mimg);
+        std::vector<int32_t> meta((size_t)SMALL_META_INTS * (size_t)mcnt);
+        std::vector<Agg3Rec> log((size_t)mrec);
+        std::vector<fnn_event> cev(events_out ? (size_t)mrec : 0);
+        std::vector<RaggedDesc> slot, sorted;  // the chunk's descriptors in the caller's order / in launch order
+        std::vector<RaggedClass> classes;
+        for (size_t c = 0; c + 1 < cut.size() && bad < 0; c++) {
+            const int64_t cnt = cut[c + 1] - cut[c];
+            slot.clear();
+            int64_t rec = 0, img = 0;
+            const double tu = now_s();
+            for (int64_t k = 0; k < cnt; k++) {
+                const int64_t b = kern[(size_t)(cut[c] + k)];
+                const int32_t n = ns[b];
+                RaggedDesc d{};
+                d.id = b; d.n = n;
+                d.meta = k * SMALL_META_INTS; d.log = rec; d.ev = rec;
+                if (on_device) {  // in place; 16-byte loads only where the problem is dense and aligned
+                    d.src = offsets[b]; d.ld = ld_of(b);
+                    d.vec = (d.ld == n && reinterpret_cast<uintptr_t>(D + offsets[b]) % 16 == 0) ? 1 : 0;
+                } else {          // rows to the dense image (padding is never read)
+                    for (int32_t r = 0; r < n; r++)
+                        std::memcpy(&pack[(size_t)(img + (int64_t)r * n)], D + offsets[b] + (int64_t)r * ld_of(b), sizeof(double) * (size_t)n);
+                    d.src = img; d.ld = n; d.vec = 1;
+                    img += pitch_of(b);
+                }
+                rec += n;
+                slot.push_back(d);
+            }
+            sorted = slot;
+            ragged_classes(sorted, [](const RaggedDesc& d) { return small_layout(d.n).bytes; }, classes);
+            if ((int64_t)classes.size() > RAGGED_MAX_CLASSES) return fail(FNN_ESTATE, W + "more size classes than launches allowed");
+            if ((!on_device && be.h2d(dD, pack.data(), sizeof(double) * (size_t)img) != FNN_OK) ||
+                be.h2d(d_desc, sorted.data(), sizeof(RaggedDesc) * (size_t)cnt) != FNN_OK)
+                return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
+            st.t_upload_s += now_s() - tu;
+            const double* base = on_device ? D : dD;
+            if (opts.validate) {
+                if (be.validate_ragged(base, d_desc, cnt, &bad) != FNN_OK) return fail(FNN_EHIP, W + "validate failed (" + be.err() + ")");
+                if (bad >= 0) break;  // (chunks follow the caller's order: no later chunk holds a lower index)
+            }
+            double tk = 0.0;
+            if (be.run_ragged(base, d_desc, classes.data(), (int32_t)classes.size(), d_meta, d_log, d_ev, &tk) != FNN_OK)
+                return fail(FNN_EHIP, W + "kernel failed (" + be.err() + ")");
+            st.t_kernel_s += tk;
+            st.chunks += (int32_t)classes.size();
+            if (classes[0].lds_bytes > st.lds_bytes) { st.lds_bytes = classes[0].lds_bytes; st.block_threads = classes[0].threads; }
+            if (be.d2h(meta.data(), d_meta, sizeof(int32_t) * SMALL_META_INTS * (size_t)cnt) != FNN_OK ||
+                be.d2h(log.data(), d_log, sizeof(Agg3Rec) * (size_t)rec) != FNN_OK ||
+                (d_ev && be.d2h(cev.data(), d_ev, sizeof(Event) * (size_t)rec) != FNN_OK))
+                return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
+            for (const RaggedDesc& d : slot) {
+                const int32_t* mt = &meta[(size_t)d.meta];
+                rc = small_collect_one(W, d.n, d.id, mt, &log[(size_t)d.log], &orders[(size_t)oo[(size_t)d.id]]);
+                if (rc != FNN_OK) return rc;
+                nev[(size_t)d.id] = mt[2];
+                if (events_out) std::memcpy(&evs[(size_t)eo[(size_t)d.id]], &cev[(size_t)d.ev], sizeof(fnn_event) * (size_t)mt[2]);
+                st.n_events += mt[2];
+            }
+            st.n_lds += cnt;
+        }
+    }
+    std::vector<int64_t> offs, glds;
+    std::vector<int32_t> go, gn;
+    std::vector<fnn_event> ge;
+    for (const auto& g : large) {  // (after a failed check only the check runs: a lower index may still fail it)
+        const int32_t n = g.first;
+        const int64_t cnt = (int64_t)g.second.size();
+        offs.clear(); glds.clear();
+        for (int64_t b : g.second) { offs.push_back(offsets[b]); glds.push_back(ld_of(b)); }
+        go.assign((size_t)cnt * (size_t)(n + 1), 0);
+        gn.assign((size_t)cnt, 0);
+        ge.assign(events_out ? (size_t)cnt * (size_t)n : 0, fnn_event{});
+        fnn_batch_stats gs{};
+        int64_t gbad = -1;
+        rc = be.large(W, D, on_device, n, offs.data(), glds.data(), cnt, opts, bad < 0, go.data(), events_out ? ge.data() : nullptr, gn.data(), &gs, &gbad);
+        if (rc != FNN_OK) return rc;
+        if (gbad >= 0) { if (bad < 0 || g.second[(size_t)gbad] < bad) bad = g.second[(size_t)gbad]; continue; }
+        if (bad >= 0) continue;
+        for (int64_t k = 0; k < cnt; k++) {
+            const int64_t b = g.second[(size_t)k];
+            std::memcpy(&orders[(size_t)oo[(size_t)b]], &go[(size_t)k * (size_t)(n + 1)], sizeof(int32_t) * (size_t)(n + 1));
+            nev[(size_t)b] = gn[(size_t)k];
+            if (events_out) std::memcpy(&evs[(size_t)eo[(size_t)b]], &ge[(size_t)k * (size_t)n], sizeof(fnn_event) * (size_t)n);
+        }
+        st.n_global += gs.n_global; st.n_fallback += gs.n_fallback; st.n_lds += gs.n_lds; st.n_events += gs.n_events;
+        st.chunks += gs.chunks; st.t_upload_s += gs.t_upload_s; st.t_kernel_s += gs.t_kernel_s;
+    }
+    if (bad >= 0) return fail(FNN_EINVAL, W + "problem " + std::to_string(bad) + ": matrix is not symmetric, not finite or has a non-zero diagonal");
     std::memcpy(orders_out, orders.data(), sizeof(int32_t) * orders.size());
     if (events_out) std::memcpy(events_out, evs.data(), sizeof(fnn_event) * evs.size());
     if (nevents_out) std::memcpy(nevents_out, nev.data(), sizeof(int32_t) * nev.size());

@@ -610,6 +610,19 @@ inline int32_t small_splits_cap(int32_t n) {
     return cap;
 }
 
+// the per-problem record of a problem that the kernel solved (m: its meta record, w: its N weights)
+inline fnn_sw_stats small_splits_stats(const SplitsMeta& m, const double* w, int64_t N, int32_t cap) {
+    fnn_sw_stats s{};
+    const bool below = m.route == FNN_SW_ROUTE_FROM_BELOW;
+    for (int64_t k = 0; k < N; k++) s.nsplits += w[k] > 0.000001 ? 1 : 0;
+    s.route = m.route; s.certified = 1; s.kkt_violation = m.kkt;
+    s.outer_iterations = m.outer; s.entered = m.entered; s.departed = m.departed; s.n_set_aside = m.n_aside;
+    s.free_set_peak = m.peak; s.capacity = below ? cap : 0;
+    s.final_threshold_rel = below ? 1e-12 : 0.0;
+    s.reserved[0] = below ? 1 : 0;
+    return s;
+}
+
 // fnn_split_weights_batch[_device]_f64 over a backend B (HIP: fnn_splits_batch.hip; CPU driver:
 // tests/emu/fnn_splits_batch_emu.cpp): open / alloc / h2d / d2h / err as small_batch's, and
 //   run_splits(dD, n, ld, stride, d_ord, cnt, cap, threads, lds_bytes, d_work, pitch, d_out, d_meta, &t_kernel_s)
@@ -699,16 +712,8 @@ int32_t small_splits_batch(B& be, const char* who, const double* D, bool on_devi
                 if (m.giveup || !m.certified) { todo.push_back(b0 + b); continue; }
                 const double* w = &outs[(size_t)(b * N)];
                 std::memcpy(&wts[(size_t)((b0 + b) * N)], w, sizeof(double) * (size_t)N);
-                fnn_sw_stats s{};
-                const bool below = m.route == FNN_SW_ROUTE_FROM_BELOW;
-                for (int64_t k = 0; k < N; k++) s.nsplits += w[k] > 0.000001 ? 1 : 0;
-                s.route = m.route; s.certified = 1; s.kkt_violation = m.kkt;
-                s.outer_iterations = m.outer; s.entered = m.entered; s.departed = m.departed; s.n_set_aside = m.n_aside;
-                s.free_set_peak = m.peak; s.capacity = below ? cap : 0;
-                s.final_threshold_rel = below ? 1e-12 : 0.0;
-                s.reserved[0] = below ? 1 : 0;
-                sws[(size_t)(b0 + b)] = s;
-                if (below) st.n_kernel++; else st.n_closed_form++;
+                sws[(size_t)(b0 + b)] = small_splits_stats(m, w, N, cap);
+                if (m.route == FNN_SW_ROUTE_FROM_BELOW) st.n_kernel++; else st.n_closed_form++;
             }
         }
     }
@@ -728,6 +733,170 @@ int32_t small_splits_batch(B& be, const char* who, const double* D, bool on_devi
         if (rc != FNN_OK) { g_last_error = W + "problem " + std::to_string(b) + ": " + g_last_error; return rc; }
         st.n_fallback++;
     }
+    std::memcpy(weights_out, wts.data(), sizeof(double) * wts.size());
+    if (stats_out) std::memcpy(stats_out, sws.data(), sizeof(fnn_sw_stats) * sws.size());
+    st.t_total_s = now_s() - t0;
+    if (stats) *stats = st;
+    if (inexact) return fail(FNN_EINEXACT, W + "at least one problem of the one-problem solver returned weights that fail its Kuhn-Tucker check (stats_out[b].certified)");
+    return FNN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ ragged batches
+// fnn_split_weights_ragged[_device]_f64 over a backend B (HIP: fnn_splits_batch.hip; CPU driver:
+// tests/emu/fnn_ragged_emu.cpp): open / alloc / h2d / d2h / err / single as above, and
+//   run_splits_ragged(base, d_desc, classes, ncls, d_ord, d_work, d_out, d_meta, &t_kernel_s)     one launch per class
+// Layout as small_ragged's (fnn_small.h); `orderings` and weights_out are concatenated in the caller's order.  The kernel
+// takes the problems of 2 <= n <= SPLITS_MAX_N when there are at least small_splits_min_batch(largest such n) of them
+// (FNN_SW_BATCH_ROUTE overrides as for the same-size call); everything else, and what gives up in the kernel, goes
+// through the one-problem solver.
+template <class B>
+int32_t small_splits_ragged(B& be, const char* who, const double* D, bool on_device, const int64_t* offsets, const int32_t* ns, const int64_t* lds,
+                            int64_t batch, const int32_t* orderings, int32_t device, double* weights_out, fnn_sw_stats* stats_out,
+                            fnn_sw_batch_stats* stats) {
+    const double t0 = now_s();
+    const std::string W = std::string(who) + ": ";
+    fnn_sw_batch_stats st{};
+    st.max_n = SPLITS_MAX_N;
+    if (batch < 0) return fail(FNN_EINVAL, W + "negative batch");
+    if (batch == 0) { if (stats) *stats = st; return FNN_OK; }
+    if (!D || !offsets || !ns || !orderings || !weights_out) return fail(FNN_EINVAL, W + "NULL argument");
+    auto ld_of = [&](int64_t b) { return lds ? lds[b] : (int64_t)ns[b]; };
+    std::vector<int64_t> oo((size_t)batch + 1, 0), wo((size_t)batch + 1, 0);  // where problem b's ordering and weights start
+    std::vector<int64_t> kern, todo;  // kernel range in the caller's order; problems for the one-problem solver
+    int32_t kmax = 0;
+    {
+        std::vector<char> seen;
+        for (int64_t b = 0; b < batch; b++) {
+            const int32_t n = ns[b];
+            const std::string P = W + "problem " + std::to_string(b) + ": ";
+            if (n < 2) return fail(FNN_EINVAL, P + "needs n >= 2");
+            if (ld_of(b) < n) return fail(FNN_EINVAL, P + "needs ld >= n");
+            seen.assign((size_t)n + 1, 0);
+            const int32_t* o = orderings + oo[(size_t)b];
+            for (int32_t i = 1; i <= n; i++) {
+                if (o[i] < 1 || o[i] > n || seen[(size_t)o[i]]) return fail(FNN_EINVAL, P + "ordering is not a permutation of 1..n");
+                seen[(size_t)o[i]] = 1;
+            }
+            oo[(size_t)b + 1] = oo[(size_t)b] + n + 1;
+            wo[(size_t)b + 1] = wo[(size_t)b] + (int64_t)n * (n - 1) / 2;
+            if (n <= SPLITS_MAX_N) { kern.push_back(b); kmax = std::max(kmax, n); }
+            else todo.push_back(b);
+        }
+    }
+    st.n_problems = batch;
+    std::vector<double> wts((size_t)wo[(size_t)batch]);
+    std::vector<fnn_sw_stats> sws((size_t)batch);
+    int32_t rc = be.open(device);
+    if (rc != FNN_OK) return fail(rc, W + be.err());
+    int64_t bad = -1;  // the lowest caller's index whose distances the kernel found non-finite
+    if (kern.empty() || !small_splits_route(kmax, (int64_t)kern.size())) {
+        todo.insert(todo.end(), kern.begin(), kern.end());
+    } else {
+        auto cap_of = [&](int64_t b) { return small_splits_cap(ns[b]); };
+        auto pitch_of = [&](int64_t b) { return small_splits_work(ns[b], cap_of(b)).pitch; };
+        auto img_of = [&](int64_t b) { return round_up((int64_t)ns[b] * ns[b], 2); };  // every problem 16-byte aligned in the image
+        const std::vector<int64_t> cut = ragged_chunks(kern, [&](int64_t b) { return 8 * pitch_of(b); });
+        int64_t mcnt = 0, mwork = 0, mout = 0, mord = 0, mimg = 0;  // the largest chunk
+        for (size_t c = 0; c + 1 < cut.size(); c++) {
+            int64_t work = 0, out = 0, ord = 0, img = 0;
+            for (int64_t k = cut[c]; k < cut[c + 1]; k++) {
+                const int64_t b = kern[(size_t)k];
+                work += pitch_of(b); out += wo[(size_t)b + 1] - wo[(size_t)b]; ord += ns[b] + 1; img += img_of(b);
+            }
+            mcnt = std::max(mcnt, cut[c + 1] - cut[c]); mwork = std::max(mwork, work); mout = std::max(mout, out);
+            mord = std::max(mord, ord); mimg = std::max(mimg, img);
+        }
+        st.workspace_bytes = 8 * mwork;
+        double* d_work = (double*)be.alloc(sizeof(double) * (size_t)mwork);
+        double* d_out = (double*)be.alloc(sizeof(double) * (size_t)mout);
+        int32_t* d_ord = (int32_t*)be.alloc(sizeof(int32_t) * (size_t)mord);
+        SplitsMeta* d_meta = (SplitsMeta*)be.alloc(sizeof(SplitsMeta) * (size_t)mcnt);
+        RaggedDesc* d_desc = (RaggedDesc*)be.alloc(sizeof(RaggedDesc) * (size_t)mcnt);
+        double* d_D = on_device ? nullptr : (double*)be.alloc(sizeof(double) * (size_t)mimg);
+        if (!d_work || !d_out || !d_ord || !d_meta || !d_desc || (!on_device && !d_D)) return fail(FNN_ENOMEM, W + "device allocation failed");
+        std::unique_ptr<double[]> pack(on_device ? nullptr : new double[(size_t)mimg]);
+        std::vector<int32_t> ords((size_t)mord);
+        std::vector<SplitsMeta> meta((size_t)mcnt);
+        std::vector<double> outs((size_t)mout);
+        std::vector<RaggedDesc> slot, sorted;  // the chunk's descriptors in the caller's order / in launch order
+        std::vector<RaggedClass> classes;
+        for (size_t c = 0; c + 1 < cut.size() && bad < 0; c++) {
+            const int64_t cnt = cut[c + 1] - cut[c];
+            slot.clear();
+            int64_t work = 0, out = 0, ord = 0, img = 0;
+            const double tu = now_s();
+            for (int64_t k = 0; k < cnt; k++) {
+                const int64_t b = kern[(size_t)(cut[c] + k)];
+                const int32_t n = ns[b];
+                RaggedDesc d{};
+                d.id = b; d.n = n; d.cap = cap_of(b);
+                d.meta = k; d.ord = ord; d.out = out; d.work = work;
+                std::memcpy(&ords[(size_t)ord], orderings + oo[(size_t)b], sizeof(int32_t) * (size_t)(n + 1));
+                if (on_device) {
+                    d.src = offsets[b]; d.ld = ld_of(b);
+                } else {
+                    for (int32_t r = 0; r < n; r++)
+                        std::memcpy(&pack[(size_t)(img + (int64_t)r * n)], D + offsets[b] + (int64_t)r * ld_of(b), sizeof(double) * (size_t)n);
+                    d.src = img; d.ld = n;
+                    img += img_of(b);
+                }
+                work += pitch_of(b); out += wo[(size_t)b + 1] - wo[(size_t)b]; ord += n + 1;
+                slot.push_back(d);
+            }
+            sorted = slot;
+            ragged_classes(sorted, [](const RaggedDesc& d) { return small_splits_layout(d.n, d.cap).bytes; }, classes);
+            if ((int64_t)classes.size() > RAGGED_MAX_CLASSES) return fail(FNN_ESTATE, W + "more size classes than launches allowed");
+            if ((!on_device && be.h2d(d_D, pack.get(), sizeof(double) * (size_t)img) != FNN_OK) ||
+                be.h2d(d_ord, ords.data(), sizeof(int32_t) * (size_t)ord) != FNN_OK ||
+                be.h2d(d_desc, sorted.data(), sizeof(RaggedDesc) * (size_t)cnt) != FNN_OK)
+                return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
+            st.t_upload_s += now_s() - tu;
+            double tk = 0.0;
+            if (be.run_splits_ragged(on_device ? D : d_D, d_desc, classes.data(), (int32_t)classes.size(), d_ord, d_work, d_out, d_meta, &tk) != FNN_OK)
+                return fail(FNN_EHIP, W + "kernel failed (" + be.err() + ")");
+            st.t_kernel_s += tk;
+            st.chunks += (int32_t)classes.size();
+            if (classes[0].lds_bytes > st.lds_bytes) {
+                st.lds_bytes = classes[0].lds_bytes; st.block_threads = classes[0].threads; st.capacity = sorted[0].cap;
+            }
+            if (be.d2h(meta.data(), d_meta, sizeof(SplitsMeta) * (size_t)cnt) != FNN_OK ||
+                be.d2h(outs.data(), d_out, sizeof(double) * (size_t)out) != FNN_OK)
+                return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
+            for (const RaggedDesc& d : slot) {
+                const SplitsMeta& m = meta[(size_t)d.meta];
+                if (m.nonfinite) { bad = d.id; break; }
+                if (m.giveup || !m.certified) { todo.push_back(d.id); continue; }
+                const int64_t N = wo[(size_t)d.id + 1] - wo[(size_t)d.id];
+                const double* w = &outs[(size_t)d.out];
+                std::memcpy(&wts[(size_t)wo[(size_t)d.id]], w, sizeof(double) * (size_t)N);
+                sws[(size_t)d.id] = small_splits_stats(m, w, N, d.cap);
+                if (m.route == FNN_SW_ROUTE_FROM_BELOW) st.n_kernel++; else st.n_closed_form++;
+            }
+        }
+    }
+    // what the kernel did not take or gave up on: one by one through the one-problem solver, on a dense host copy, in the
+    // caller's order (after a non-finite problem only those in front of it: fnn_last_error() names the lowest failure)
+    std::sort(todo.begin(), todo.end());
+    bool inexact = false;
+    std::vector<double> one, span;
+    for (int64_t b : todo) {
+        if (bad >= 0 && b > bad) break;
+        const int32_t n = ns[b];
+        const int64_t ld = ld_of(b);
+        const double* src = D + offsets[b];
+        if (on_device) {
+            span.resize((size_t)((int64_t)(n - 1) * ld + n));
+            if (be.d2h(span.data(), src, sizeof(double) * span.size()) != FNN_OK) return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
+            src = span.data();
+        }
+        one.resize((size_t)n * (size_t)n);
+        for (int32_t r = 0; r < n; r++) std::memcpy(&one[(size_t)r * (size_t)n], src + (int64_t)r * ld, sizeof(double) * (size_t)n);
+        rc = be.single(one.data(), n, orderings + oo[(size_t)b], device, &wts[(size_t)wo[(size_t)b]], &sws[(size_t)b]);
+        if (rc == FNN_EINEXACT) { inexact = true; rc = FNN_OK; }
+        if (rc != FNN_OK) { g_last_error = W + "problem " + std::to_string(b) + ": " + g_last_error; return rc; }
+        st.n_fallback++;
+    }
+    if (bad >= 0) return fail(FNN_EINVAL, W + "problem " + std::to_string(bad) + ": the distances contain a NaN or an infinity");
     std::memcpy(weights_out, wts.data(), sizeof(double) * wts.size());
     if (stats_out) std::memcpy(stats_out, sws.data(), sizeof(fnn_sw_stats) * sws.size());
     st.t_total_s = now_s() - t0;

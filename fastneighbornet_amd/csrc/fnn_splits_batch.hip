@@ -1,6 +1,7 @@
 // fnn_splits_batch.hip -- circular split weights of many small problems in one call: k_small_splits solves one whole
 // non-negative least-squares problem per workgroup (the phase bodies, their sequence and the host side of the call are
-// fnn_small_splits.h).
+// fnn_small_splits.h); k_small_splits_ragged is the same for problems of different sizes, one
+// descriptor per workgroup.
 //
 // The kernel is a thin wrapper: it carves the dynamic LDS and the problem's workspace slice into the view and hands the
 // phases to small_splits_problem() with an executor whose barrier is __syncthreads().  No cross-workgroup communication,
@@ -10,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "fnn_ragged_hip.h"
 #include "fnn_small_splits.h"
 
 namespace fnn {
@@ -71,11 +73,25 @@ __global__ __launch_bounds__(1024) void k_small_splits(const double* __restrict_
     small_splits_problem(ex, V, D + b * stride, ld, ord + b * (n + 1), out + b * ((int64_t)n * (n - 1) / 2), meta + b);
 }
 
+// Ragged batches: one workgroup per DESCRIPTOR.  grid: the problems of one size class, desc already
+// advanced to the class's first descriptor; dynamic LDS: small_splits_layout of the class's largest member, of which the
+// problem uses its own small_splits_layout(n, cap).bytes.  The descriptor is the same for every thread of the workgroup.
+__global__ __launch_bounds__(1024) void k_small_splits_ragged(const double* __restrict__ D, const RaggedDesc* __restrict__ desc,
+                                                              const int32_t* __restrict__ ord, double* work, double* __restrict__ out,
+                                                              SplitsMeta* __restrict__ meta) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char splits_lds[];
+    const RaggedDesc d = desc[blockIdx.x];
+    const SplitsView V = small_splits_view(splits_lds, work + d.work, d.n, d.cap);
+    GpuSplitsExec ex;
+    small_splits_problem(ex, V, D + d.src, d.ld, ord + d.ord, out + d.out, meta + d.meta);
+}
+
 struct SplitsHipBackend {
     std::vector<void*> bufs;
     hipStream_t stream = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     std::string last;
+    RaggedLauncher ragged{RAGGED_SPLITS_STREAMS};
     int prev_device = -1;  // the caller's current device, restored when the call ends
 
     ~SplitsHipBackend() {
@@ -129,6 +145,20 @@ struct SplitsHipBackend {
         *t_kernel_s = (double)ms * 1e-3;
         return FNN_OK;
     }
+    int32_t run_splits_ragged(const double* base, const RaggedDesc* d_desc, const RaggedClass* cls, int32_t ncls, const int32_t* d_ord, double* d_work,
+                              double* d_out, SplitsMeta* d_meta, double* t_kernel_s) {
+        int32_t lds_max = 0;
+        for (int32_t c = 0; c < ncls; c++) lds_max = cls[c].lds_bytes > lds_max ? cls[c].lds_bytes : lds_max;
+        if (!ok(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_small_splits_ragged), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max),
+                "hipFuncSetAttribute"))
+            return FNN_EHIP;
+        const char* what = "";
+        const hipError_t e = ragged.run(stream, e0, e1, ncls, [&](int32_t c, hipStream_t s) {
+            hipLaunchKernelGGL(k_small_splits_ragged, dim3((unsigned)cls[c].count), dim3((unsigned)cls[c].threads), (size_t)cls[c].lds_bytes, s, base,
+                               d_desc + cls[c].first, d_ord, d_work, d_out, d_meta);
+        }, t_kernel_s, &what);
+        return ok(e, (std::string("k_small_splits_ragged: ") + what).c_str()) ? FNN_OK : FNN_EHIP;
+    }
     int32_t single(const double* D, int32_t n, const int32_t* ordering, int32_t device, double* weights, fnn_sw_stats* sw) {
         return fnn_split_weights_f64(D, n, n, ordering, device, weights, sw);
     }
@@ -163,6 +193,23 @@ int32_t fnn_split_weights_batch_device_f64(const double* d_D, int32_t n, int64_t
     FNN_SPLITS_BATCH_TRY(
         fnn::SplitsHipBackend be;
         return fnn::small_splits_batch(be, "fnn_split_weights_batch_device_f64", d_D, true, n, ld, stride, batch, orderings, device, weights_out, stats_out, stats);
+    )
+}
+
+int32_t fnn_split_weights_ragged_f64(const double* D, const int64_t* offsets, const int32_t* n, const int64_t* ld, int64_t batch, const int32_t* orderings,
+                                     int32_t device, double* weights_out, fnn_sw_stats* stats_out, fnn_sw_batch_stats* stats) {
+    FNN_SPLITS_BATCH_TRY(
+        fnn::SplitsHipBackend be;
+        return fnn::small_splits_ragged(be, "fnn_split_weights_ragged_f64", D, false, offsets, n, ld, batch, orderings, device, weights_out, stats_out, stats);
+    )
+}
+
+int32_t fnn_split_weights_ragged_device_f64(const double* d_D, const int64_t* offsets, const int32_t* n, const int64_t* ld, int64_t batch,
+                                            const int32_t* orderings, int32_t device, double* weights_out, fnn_sw_stats* stats_out,
+                                            fnn_sw_batch_stats* stats) {
+    FNN_SPLITS_BATCH_TRY(
+        fnn::SplitsHipBackend be;
+        return fnn::small_splits_ragged(be, "fnn_split_weights_ragged_device_f64", d_D, true, offsets, n, ld, batch, orderings, device, weights_out, stats_out, stats);
     )
 }
 

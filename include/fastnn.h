@@ -282,6 +282,35 @@ int32_t fnn_canonical_order_batch_device_f64(const double* d_D, int32_t n, int64
                                              const fnn_opts* opts, int32_t* orders_out, fnn_event* events_out,
                                              int32_t* nevents_out, fnn_batch_stats* stats);
 
+/* ---- ragged batches: problems of DIFFERENT sizes in one call -----------
+ * Per-gene matrices and sliding windows over alignments with missing taxa: problem b is the n[b] x n[b] matrix at
+ * D + offsets[b] (in doubles) with row stride ld[b] (ld == NULL: ld[b] = n[b]).  offsets, n and ld are host arrays in both
+ * variants; two problems may share or overlap storage; padding is never read and D is never written.  Every problem gets
+ * exactly what fnn_canonical_order_batch_f64 gives it in a batch of its own size, and the contract is that call's, problem
+ * by problem: n[b] <= 3 gives the identity without a device, batch == 0 is FNN_OK, opts->validate, opts->mode and
+ * opts->device act alike, a negative n[b], an ld[b] below n[b] or a NULL array is FNN_EINVAL, fnn_last_error() names the
+ * lowest failing problem in the CALLER's numbering (the call sorts the problems by size internally; nothing of that shows),
+ * and whatever fails, the output arrays are untouched.
+ * orders_out is concatenated: problem b's n[b] + 1 entries start at the sum of n[a] + 1 over a < b; events_out (NULL or
+ * concatenated): problem b's n[b] records start at the sum of n[a] over a < b, nevents_out[b] events, zero-filled behind
+ * them; nevents_out: NULL or batch.
+ * Problems of 4 <= n[b] <= fnn_batch_lds_max_n() run one workgroup each, out of LDS, in a few launches per chunk: the call
+ * sorts them into size classes (one block size and one LDS reservation per launch: at most 8, 6 with the default block
+ * sizes) and starts the largest problems first.  Larger problems are grouped by size and handed to the same-size entry,
+ * which picks the global-memory kernel or the one-problem engine by its own rule.  The host variant packs each chunk (at
+ * most 2 GiB, FNN_BATCH_CHUNK=<problems> for tests) into one dense device image; the device variant reads D in place, with
+ * 16-byte loads for a problem that is dense and 16-byte aligned, and is not ordered against the stream that produced D.
+ * stats: chunks counts kernel launches, block_threads and lds_bytes describe the largest class launched, the counters are
+ * summed over everything.  FNN_RAGGED_STREAMS=1..4: the streams the classes of a chunk are spread over (default: one for the orders, two for the
+ * split weights, as measured). */
+int32_t fnn_canonical_order_ragged_f64(const double* D, const int64_t* offsets, const int32_t* n, const int64_t* ld /* or NULL */,
+                                       int64_t batch, const fnn_opts* opts, int32_t* orders_out /* sum of n[b] + 1 */,
+                                       fnn_event* events_out /* NULL or sum of n[b] */, int32_t* nevents_out /* NULL or batch */,
+                                       fnn_batch_stats* stats /* may be NULL */);
+int32_t fnn_canonical_order_ragged_device_f64(const double* d_D, const int64_t* offsets, const int32_t* n, const int64_t* ld,
+                                              int64_t batch, const fnn_opts* opts, int32_t* orders_out, fnn_event* events_out,
+                                              int32_t* nevents_out, fnn_batch_stats* stats);
+
 /* ---- several GPUs of one node (one process per GPU): ONE problem on all ranks -----------------
  * Every rank holds the whole matrix (8 GiB at n = 32768, 3 % of an MI355X) and runs the whole event chain
  * itself (the ranks stay in step because every decision is a deterministic function of identical state), so no
@@ -424,6 +453,25 @@ int32_t fnn_split_weights_batch_f64(const double* D, int32_t n, int64_t ld, int6
 int32_t fnn_split_weights_batch_device_f64(const double* d_D, int32_t n, int64_t ld, int64_t stride, int64_t batch,
                                            const int32_t* orderings, int32_t device, double* weights_out,
                                            fnn_sw_stats* stats_out, fnn_sw_batch_stats* stats);
+
+/* The second half of a ragged run: problems laid out as for fnn_canonical_order_ragged_f64, `orderings` (host memory)
+ * concatenated as its orders_out.  weights_out is concatenated: n[b] (n[b] - 1) / 2 weights per problem, each as
+ * fnn_split_weights_f64's; stats_out: NULL or batch records.  The contract is fnn_split_weights_batch_f64's, problem by
+ * problem: batch == 0 is FNN_OK; n[b] < 2, an ld[b] below n[b], a NULL array or an ordering that is not a permutation is
+ * FNN_EINVAL, and so is a non-finite distance; FNN_ECAPACITY and FNN_EINEXACT as there; fnn_last_error() names the lowest
+ * failing problem in the caller's numbering; whatever fails but FNN_EINEXACT, the output arrays are untouched.
+ * The kernel takes the problems of n[b] <= fnn_split_weights_batch_max_n() when there are at least
+ * fnn_split_weights_batch_min_batch(the largest such n[b]) of them (FNN_SW_BATCH_ROUTE=kernel|loop overrides this as for the
+ * same-size call), one workgroup each in at most 8 launches per chunk (4 with the default block sizes), every problem with
+ * the block size and the factor capacity of the same-size call: its weights are bit for bit that call's.  Larger problems
+ * and problems that give up in the kernel go through fnn_split_weights_f64 (stats->n_fallback).  stats: as above. */
+int32_t fnn_split_weights_ragged_f64(const double* D, const int64_t* offsets, const int32_t* n, const int64_t* ld /* or NULL */,
+                                     int64_t batch, const int32_t* orderings /* sum of n[b] + 1 */, int32_t device,
+                                     double* weights_out /* sum of n[b] (n[b] - 1) / 2 */, fnn_sw_stats* stats_out /* NULL or batch */,
+                                     fnn_sw_batch_stats* stats /* may be NULL */);
+int32_t fnn_split_weights_ragged_device_f64(const double* d_D, const int64_t* offsets, const int32_t* n, const int64_t* ld,
+                                            int64_t batch, const int32_t* orderings, int32_t device, double* weights_out,
+                                            fnn_sw_stats* stats_out, fnn_sw_batch_stats* stats);
 
 /* Diagnostic: the exact block-parallel evaluation of the sequential fp64 sum
  * (((0 + b[0]) + b[1]) + ...) used for ComputeRx / u.Sx (NetMakerOriginal.java:551-560,
