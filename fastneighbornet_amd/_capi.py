@@ -57,7 +57,12 @@ class FnnSwStats(C.Structure):
                 ("route", C.c_int32), ("certified", C.c_int32), ("kkt_violation", C.c_double), ("final_threshold_rel", C.c_double),
                 ("n_set_aside", C.c_int64), ("capacity", C.c_int64), ("free_set_peak", C.c_int64), ("giveup_reason", C.c_int32),
                 ("pad_", C.c_int32), ("entered", C.c_int64), ("screened_out", C.c_int64), ("departed", C.c_int64),
-                ("t_alloc_s", C.c_double), ("reserved2", C.c_int64 * 4)]
+                ("t_alloc_s", C.c_double),
+                # reserved2[0..3] of include/fastnn.h: how often the batch kernel's safety net ran for this problem (splits set
+                # aside as dependent on a fresh append / on a rebuild / because they left in their entering step; rechecks of the
+                # splits set aside; releases after progress).  [3] holds two 32-bit counts.  0 from the one-problem solver.
+                ("aside_fresh", C.c_int64), ("aside_rebuild", C.c_int64), ("aside_entering", C.c_int64),
+                ("rechecks", C.c_int32), ("releases", C.c_int32)]
 
 
 class FnnBatchStats(C.Structure):

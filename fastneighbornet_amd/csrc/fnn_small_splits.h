@@ -51,12 +51,27 @@ enum { SPLITS_ACT_APPEND = 0, SPLITS_ACT_DONE = 1, SPLITS_ACT_RECHECK = 2, SPLIT
 
 struct SplitsCtl {
     double cmax, ll, lz, hkk, alpha, kkt;
+    double dep;         // SplitsSwitches.dep
+    int32_t max_steps;  // SplitsSwitches.steps, or 40 n + 1000
     int32_t nonfinite, neg, giveup, route, certified, action;
     int32_t f, ftot, leave, enter_pos;
-    int32_t steps, outer, entered, departed, n_aside, peak, rechecked, pad_;
+    int32_t steps, outer, entered, departed, n_aside, peak, rechecked;
+    int32_t aside_fresh, aside_rebuild, aside_enter, rechecks, releases;  // how often each safety-net path ran (never reset)
 };
 struct SplitsRec { double v; int32_t k, e; };  // value, tie key (lowest wins), payload; k < 0: none
-struct SplitsMeta { double kkt; int32_t nonfinite, giveup, route, certified, outer, entered, departed, n_aside, peak, pad_; };
+struct SplitsMeta {
+    double kkt;
+    int32_t nonfinite, giveup, route, certified, outer, entered, departed, n_aside, peak;
+    int32_t aside_fresh, aside_rebuild, aside_enter, rechecks, releases, steps, pad_;
+};
+static_assert(sizeof(SplitsMeta) == 72, "meta record layout");
+
+// Test switches of the safety net (small_splits_switches reads them on the host; FNN_HD code only ever sees the values, and
+// keeps them in the control block: the view stays as small as it was): the
+// relative size of delta^2 = H_kk - l.l below which an appended split counts as numerically dependent on the factor, and
+// the step limit (0: 40 n + 1000).
+struct SplitsSwitches { double dep; int32_t steps, pad_; };
+constexpr double SPLITS_DEP_REL = 1e-9;
 
 FNN_HD bool splits_better(const SplitsRec& a, const SplitsRec& b) {  // a before b: larger value, then lower key
     if (a.k < 0) return false;
@@ -161,10 +176,12 @@ FNN_HD void splits_reorder(int tid, int nt, const SplitsView& V, const double* D
         V.mask[e] = 0;
     }
 }
-FNN_HD void splits_init(int tid, int nt, const SplitsView& V) {
+FNN_HD void splits_init(int tid, int nt, const SplitsView& V, const SplitsSwitches& sw) {
     if (tid != 0) return;
     SplitsCtl z{};
     z.leave = -1; z.enter_pos = -1;
+    z.dep = sw.dep;
+    z.max_steps = sw.steps >= 1 ? sw.steps : 40 * V.n + 1000;
     *V.ctl = z;
 }
 
@@ -309,7 +326,7 @@ FNN_HD void splits_fold_pick(int tid, int nt, const SplitsView& V) {
         K.action = (K.n_aside > 0 && !K.rechecked) ? SPLITS_ACT_RECHECK : SPLITS_ACT_DONE;
         return;
     }
-    if (++K.steps > 40 * V.n + 1000) { splits_give_up(V, FNN_SW_GIVEUP_STEPS); return; }
+    if (++K.steps > K.max_steps) { splits_give_up(V, FNN_SW_GIVEUP_STEPS); return; }
     if (K.f >= V.cap) { splits_give_up(V, FNN_SW_GIVEUP_CAPACITY); return; }
     V.Fi[K.f] = b.e;
     V.xF[K.f] = 0.0;
@@ -323,7 +340,10 @@ FNN_HD void splits_release(int tid, int nt, const SplitsView& V, int32_t recheck
     const int32_t tot = V.n * V.n;
     for (int32_t e = tid; e < tot; e += nt)
         if (V.mask[e] == 2) V.mask[e] = 0;
-    if (tid == 0) { V.ctl->n_aside = 0; V.ctl->rechecked = rechecked; }
+    if (tid == 0) {
+        V.ctl->n_aside = 0; V.ctl->rechecked = rechecked;
+        if (rechecked) V.ctl->rechecks++; else V.ctl->releases++;
+    }
 }
 
 // ---- append row r of W for the split at position r of F (positions below r are in the factor)
@@ -360,7 +380,7 @@ FNN_HD void splits_append_r(int tid, int nt, const SplitsView& V, int32_t r) {
 // leaves F (the positions behind it move down)
 FNN_HD void splits_append_row(int tid, int nt, const SplitsView& V, int32_t r, int32_t ftot, int32_t fresh) {
     const double hkk = V.ctl->hkk, d2 = hkk - V.ctl->ll;
-    if (d2 > 1e-9 * hkk) {
+    if (d2 > V.ctl->dep * hkk) {
         const double dl = std::sqrt(d2);
         double* w = V.W + (int64_t)r * V.cap;
         for (int32_t j = tid; j < r; j += nt) w[j] = -V.rv[j] / dl;
@@ -379,7 +399,8 @@ FNN_HD void splits_append_row(int tid, int nt, const SplitsView& V, int32_t r, i
         V.mask[k] = 2;
         V.gx[k] = 0.0;
         K.n_aside++;
-        if (!fresh) K.departed++;
+        if (fresh) K.aside_fresh++;
+        else { K.departed++; K.aside_rebuild++; }
         if (K.enter_pos == r) K.enter_pos = -1;
         else if (K.enter_pos > r) K.enter_pos--;
         for (int32_t j = r + 1; j < ftot; j++) { V.Fi[j - 1] = V.Fi[j]; V.xF[j - 1] = V.xF[j]; V.cF[j - 1] = V.cF[j]; }
@@ -414,7 +435,7 @@ FNN_HD void splits_fold_ratio(int tid, int nt, const SplitsView& V) {
     K.leave = b.k;
     K.alpha = b.k >= 0 ? -b.v : 1.0;
     K.action = SPLITS_ACT_APPEND;
-    if (b.k >= 0 && ++K.steps > 40 * V.n + 1000) splits_give_up(V, FNN_SW_GIVEUP_STEPS);
+    if (b.k >= 0 && ++K.steps > K.max_steps) splits_give_up(V, FNN_SW_GIVEUP_STEPS);
 }
 // every s > 0: it is the new x
 FNN_HD void splits_accept(int tid, int nt, const SplitsView& V, int32_t f) {
@@ -447,7 +468,7 @@ FNN_HD void splits_compact(int tid, int nt, const SplitsView& V, int32_t f) {
         }
         const int32_t k = V.Fi[j];
         V.gx[k] = 0.0;
-        if (j == K.enter_pos) { V.mask[k] = 2; K.n_aside++; }
+        if (j == K.enter_pos) { V.mask[k] = 2; K.n_aside++; K.aside_enter++; }
         else V.mask[k] = 0;
         K.departed++;
         if (pmin < 0) pmin = j;
@@ -494,6 +515,8 @@ FNN_HD void splits_output(int tid, int nt, const SplitsView& V, double* out, Spl
         SplitsMeta m{};
         m.kkt = K.kkt; m.nonfinite = K.nonfinite; m.giveup = K.giveup; m.route = K.route; m.certified = K.certified;
         m.outer = K.outer; m.entered = K.entered; m.departed = K.departed; m.n_aside = K.n_aside; m.peak = K.peak;
+        m.aside_fresh = K.aside_fresh; m.aside_rebuild = K.aside_rebuild; m.aside_enter = K.aside_enter;
+        m.rechecks = K.rechecks; m.releases = K.releases; m.steps = K.steps;
         *meta = m;
     }
 }
@@ -527,9 +550,10 @@ FNN_HD void splits_append_pending(Exec& ex, const SplitsView& V, int32_t fresh) 
 }
 
 template <class Exec>
-FNN_HD void small_splits_problem(Exec& ex, const SplitsView& V, const double* D, int64_t ld, const int32_t* ord, double* out, SplitsMeta* meta) {
+FNN_HD void small_splits_problem(Exec& ex, const SplitsView& V, const SplitsSwitches& sw, const double* D, int64_t ld, const int32_t* ord, double* out,
+                                 SplitsMeta* meta) {
     const int32_t n = V.n;
-    ex.all([&](int tid, int nt) { splits_init(tid, nt, V); });
+    ex.all([&](int tid, int nt) { splits_init(tid, nt, V, sw); });
     ex.all([&](int tid, int nt) { splits_reorder(tid, nt, V, D, ld, ord); });
     if (!ex.get(&V.ctl->nonfinite)) {
         ex.all([&](int tid, int nt) { splits_closed_form(tid, nt, V); });
@@ -593,6 +617,11 @@ FNN_HD void small_splits_problem(Exec& ex, const SplitsView& V, const double* D,
     }
     ex.all([&](int tid, int nt) { splits_output(tid, nt, V, out, meta); });
 }
+// ... with the defaults (an executor that knows no switches)
+template <class Exec>
+FNN_HD void small_splits_problem(Exec& ex, const SplitsView& V, const double* D, int64_t ld, const int32_t* ord, double* out, SplitsMeta* meta) {
+    small_splits_problem(ex, V, SplitsSwitches{SPLITS_DEP_REL, 0, 0}, D, ld, ord, out, meta);
+}
 
 // ------------------------------------------------------------------------------------------------ host side
 // Which calls take the kernel.  FNN_SW_BATCH_ROUTE=kernel sends any batch >= 1 of n <= SPLITS_MAX_N to it (tests, and
@@ -609,6 +638,14 @@ inline int32_t small_splits_cap(int32_t n) {
     if (const char* e = std::getenv("FNN_SW_BATCH_CAP")) { const int v = std::atoi(e); if (v >= 1 && v < cap) cap = v; }
     return cap;
 }
+// FNN_SW_BATCH_DEP=<x in (0, 1)> and FNN_SW_BATCH_STEPS=<steps >= 1>, for tests: with a large threshold or a small limit
+// honest inputs reach the set-aside, recheck and give-up paths that they never reach otherwise.
+inline SplitsSwitches small_splits_switches() {
+    SplitsSwitches sw{SPLITS_DEP_REL, 0, 0};
+    if (const char* e = std::getenv("FNN_SW_BATCH_DEP")) { const double v = std::atof(e); if (v > 0.0 && v < 1.0) sw.dep = v; }
+    if (const char* e = std::getenv("FNN_SW_BATCH_STEPS")) { const long long v = std::atoll(e); if (v >= 1 && v <= 0x7fffffff) sw.steps = (int32_t)v; }
+    return sw;
+}
 
 // the per-problem record of a problem that the kernel solved (m: its meta record, w: its N weights)
 inline fnn_sw_stats small_splits_stats(const SplitsMeta& m, const double* w, int64_t N, int32_t cap) {
@@ -620,12 +657,16 @@ inline fnn_sw_stats small_splits_stats(const SplitsMeta& m, const double* w, int
     s.free_set_peak = m.peak; s.capacity = below ? cap : 0;
     s.final_threshold_rel = below ? 1e-12 : 0.0;
     s.reserved[0] = below ? 1 : 0;
+    s.reserved[2] = m.steps;  // what the step limit counts: entering splits and ratio steps
+    s.reserved2[0] = m.aside_fresh; s.reserved2[1] = m.aside_rebuild; s.reserved2[2] = m.aside_enter;
+    s.reserved2[3] = (int64_t)m.rechecks | ((int64_t)m.releases << 32);
     return s;
 }
 
 // fnn_split_weights_batch[_device]_f64 over a backend B (HIP: fnn_splits_batch.hip; CPU driver:
 // tests/emu/fnn_splits_batch_emu.cpp): open / alloc / h2d / d2h / err as small_batch's, and
 //   run_splits(dD, n, ld, stride, d_ord, cnt, cap, threads, lds_bytes, d_work, pitch, d_out, d_meta, &t_kernel_s)
+//                (a backend that honours the test switches reads small_splits_switches() here, once per launch)
 //   single(D_host, n, ordering, device, weights, &sw_stats)      the one-problem solver on a dense host matrix
 template <class B>
 int32_t small_splits_batch(B& be, const char* who, const double* D, bool on_device, int32_t n, int64_t ld, int64_t stride, int64_t batch,

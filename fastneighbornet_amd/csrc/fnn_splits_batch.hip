@@ -64,26 +64,26 @@ struct GpuSplitsExec {
 // grid: one workgroup per problem of the chunk; dynamic LDS: small_splits_layout(n, cap).bytes.  `work` (neither const nor
 // __restrict__: the workgroup stores to it and loads what it stored) holds the problems' slices, `pitch` doubles apart.
 __global__ __launch_bounds__(1024) void k_small_splits(const double* __restrict__ D, int32_t n, int64_t ld, int64_t stride,
-                                                       const int32_t* __restrict__ ord, int32_t cap, double* work, int64_t pitch,
+                                                       const int32_t* __restrict__ ord, int32_t cap, SplitsSwitches sw, double* work, int64_t pitch,
                                                        double* __restrict__ out, SplitsMeta* __restrict__ meta) {
     extern __shared__ __attribute__((aligned(16))) unsigned char splits_lds[];
     const int64_t b = blockIdx.x;
     const SplitsView V = small_splits_view(splits_lds, work + b * pitch, n, cap);
     GpuSplitsExec ex;
-    small_splits_problem(ex, V, D + b * stride, ld, ord + b * (n + 1), out + b * ((int64_t)n * (n - 1) / 2), meta + b);
+    small_splits_problem(ex, V, sw, D + b * stride, ld, ord + b * (n + 1), out + b * ((int64_t)n * (n - 1) / 2), meta + b);
 }
 
 // Ragged batches: one workgroup per DESCRIPTOR.  grid: the problems of one size class, desc already
 // advanced to the class's first descriptor; dynamic LDS: small_splits_layout of the class's largest member, of which the
 // problem uses its own small_splits_layout(n, cap).bytes.  The descriptor is the same for every thread of the workgroup.
 __global__ __launch_bounds__(1024) void k_small_splits_ragged(const double* __restrict__ D, const RaggedDesc* __restrict__ desc,
-                                                              const int32_t* __restrict__ ord, double* work, double* __restrict__ out,
-                                                              SplitsMeta* __restrict__ meta) {
+                                                              const int32_t* __restrict__ ord, SplitsSwitches sw, double* work,
+                                                              double* __restrict__ out, SplitsMeta* __restrict__ meta) {
     extern __shared__ __attribute__((aligned(16))) unsigned char splits_lds[];
     const RaggedDesc d = desc[blockIdx.x];
     const SplitsView V = small_splits_view(splits_lds, work + d.work, d.n, d.cap);
     GpuSplitsExec ex;
-    small_splits_problem(ex, V, D + d.src, d.ld, ord + d.ord, out + d.out, meta + d.meta);
+    small_splits_problem(ex, V, sw, D + d.src, d.ld, ord + d.ord, out + d.out, meta + d.meta);
 }
 
 struct SplitsHipBackend {
@@ -135,8 +135,9 @@ struct SplitsHipBackend {
         if (!ok(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_small_splits), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
                 "hipFuncSetAttribute"))
             return FNN_EHIP;
+        const SplitsSwitches sw = small_splits_switches();
         if (!ok(hipEventRecord(e0, stream), "hipEventRecord")) return FNN_EHIP;
-        hipLaunchKernelGGL(k_small_splits, dim3((unsigned)cnt), dim3((unsigned)threads), (size_t)lds_bytes, stream, dD, n, ld, stride, d_ord, cap, d_work,
+        hipLaunchKernelGGL(k_small_splits, dim3((unsigned)cnt), dim3((unsigned)threads), (size_t)lds_bytes, stream, dD, n, ld, stride, d_ord, cap, sw, d_work,
                            pitch, d_out, d_meta);
         if (!ok(hipGetLastError(), "k_small_splits launch")) return FNN_EHIP;
         if (!ok(hipEventRecord(e1, stream), "hipEventRecord") || !ok(hipEventSynchronize(e1), "k_small_splits")) return FNN_EHIP;
@@ -152,10 +153,11 @@ struct SplitsHipBackend {
         if (!ok(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_small_splits_ragged), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max),
                 "hipFuncSetAttribute"))
             return FNN_EHIP;
+        const SplitsSwitches sw = small_splits_switches();
         const char* what = "";
         const hipError_t e = ragged.run(stream, e0, e1, ncls, [&](int32_t c, hipStream_t s) {
             hipLaunchKernelGGL(k_small_splits_ragged, dim3((unsigned)cls[c].count), dim3((unsigned)cls[c].threads), (size_t)cls[c].lds_bytes, s, base,
-                               d_desc + cls[c].first, d_ord, d_work, d_out, d_meta);
+                               d_desc + cls[c].first, d_ord, sw, d_work, d_out, d_meta);
         }, t_kernel_s, &what);
         return ok(e, (std::string("k_small_splits_ragged: ") + what).c_str()) ? FNN_OK : FNN_EHIP;
     }

@@ -362,7 +362,8 @@ typedef struct fnn_sw_stats {
     int64_t cg_iterations;    /* ... and their iterations (each applies A and A^T once) */
     int64_t nsplits;          /* weights above 1e-6 */
     double  t_solve_s;        /* device time from the re-ordered distances to the weights */
-    int64_t reserved[3];      /* [0] 1 = solved from below (block active-set method), [1] rebuilds of the factor, [2] sub-problems solved */
+    int64_t reserved[3];      /* [0] 1 = solved from below (block active-set method), [1] rebuilds of the factor, [2] sub-problems solved
+                                 (batch kernel: [1] 0, [2] the steps that its step limit counts: entering splits plus ratio steps) */
     /* ---- ABI version 2 ---- */
     int32_t route;            /* FNN_SW_ROUTE_*: which of the three routes produced weights_out */
     int32_t certified;        /* 1 = the weights passed the solver's own Kuhn-Tucker check (kkt_violation <= 1e-9) */
@@ -378,7 +379,11 @@ typedef struct fnn_sw_stats {
     int32_t pad_;
     int64_t entered, screened_out, departed; /* from below: splits appended / dropped by the Schur-complement screening / left */
     double  t_alloc_s;        /* seconds in hipMalloc for the factor's buffers (0.1-2.7 s from box to box at 32768 taxa) */
-    int64_t reserved2[4];
+    int64_t reserved2[4];     /* batch kernel only (0 from the one-problem solver), how often its safety net ran: splits set aside as
+                                 numerically dependent on the factor [0] on a fresh append, [1] on a rebuild, [2] splits set aside
+                                 because they left in the step in which they entered, [3] low 32 bits: rechecks of the splits set
+                                 aside before the optimum was declared, high 32 bits: releases after progress.  n_set_aside is
+                                 only what was still aside at the end */
 } fnn_sw_stats;
 enum { FNN_SW_ROUTE_CLOSED_FORM = 0, FNN_SW_ROUTE_FROM_BELOW = 1, FNN_SW_ROUTE_REFERENCE = 2 };
 enum { FNN_SW_GIVEUP_NONE = 0, FNN_SW_GIVEUP_CAPACITY = 1,   /* the free set outgrew the dense factor */
@@ -419,7 +424,9 @@ int32_t fnn_split_weights_release_cache(void);
  * appended to and never updated (n_kernel), followed by the same Kuhn-Tucker certificate as the one-problem call, computed
  * from the weights with the prefix-sum operators alone.  A problem whose free set outgrows the per-problem factor
  * (`capacity` splits: min(n(n-1)/2, 6 n); FNN_SW_BATCH_CAP=<splits> lowers it, for tests), that exceeds 40 n + 1000 steps
- * or that ends uncertified gives up inside the kernel and goes, like every problem of a call with n above the limit, through
+ * (FNN_SW_BATCH_STEPS=<steps >= 1> replaces the limit, for tests; FNN_SW_BATCH_DEP=<x>, 0 < x < 1, replaces the relative
+ * threshold 1e-9 below which an appended split counts as numerically dependent on the factor and is set aside, for tests) or
+ * that ends uncertified gives up inside the kernel and goes, like every problem of a call with n above the limit, through
  * fnn_split_weights_f64 (n_fallback) - nearly circular metrics take that way.  The optimum is unique, so both ways meet.
  * stats_out (NULL or batch records): route, certified, kkt_violation, outer_iterations (steps: ONE split enters per step),
  * entered, departed, n_set_aside, free_set_peak, capacity, nsplits, final_threshold_rel from the kernel for its own problems,

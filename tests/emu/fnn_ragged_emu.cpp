@@ -123,6 +123,7 @@ struct EmuRaggedBackend {
     int32_t run_splits_ragged(const double* base, const RaggedDesc* desc, const RaggedClass* cls, int32_t ncls, const int32_t* ord, double* work,
                               double* out, SplitsMeta* meta, double* t_kernel_s) {
         const double t0 = now_s();
+        const SplitsSwitches sw = small_splits_switches();
         for (int32_t c = 0; c < ncls; c++)
             for (int64_t k = 0; k < cls[c].count; k++) {
                 const RaggedDesc d = desc[cls[c].first + k];
@@ -138,7 +139,7 @@ struct EmuRaggedBackend {
                 std::memset(w, 0xFF, sizeof(double) * (size_t)N);
                 const SplitsView V = small_splits_view(lds, slice, d.n, d.cap);
                 CpuSplitsExec ex{threads};
-                small_splits_problem(ex, V, base + d.src, d.ld, ord + d.ord, w, meta + d.meta);
+                small_splits_problem(ex, V, sw, base + d.src, d.ld, ord + d.ord, w, meta + d.meta);
                 std::memcpy(out + d.out, w, sizeof(double) * (size_t)N);
                 if ((size_t)d.id < g_giveups.size()) g_giveups[(size_t)d.id] = meta[d.meta].giveup;
                 std::free(w);

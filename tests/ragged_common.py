@@ -281,3 +281,62 @@ def check_weights(drv, max_n, same_weights):
             assert np.abs(w[b] - xs).max() <= 1e-6 * max(1.0, np.abs(xs).max()), (n, b, np.abs(w[b] - xs).max())
         assert w[b].tobytes() == same_weights(D[None], o[None]).tobytes(), (b, n)
     return w
+
+
+def emu_weight_giveups(a, mats, orders):
+    """FNN_SW_GIVEUP_* per problem from the CPU driver's ragged weight call, whether it fails (a problem gave up) or not."""
+    try:
+        Driver(a).weights(Layout(mats), orders, fill=sc.SENTINEL)
+    except _capi.FnnError as e:
+        assert e.code == -6 and (e.weights == sc.SENTINEL).all(), e
+        failed = str(e)
+    else:
+        failed = None
+    g = np.zeros(len(mats), dtype=np.int32)
+    assert a.split_weights_ragged_giveups(g.ctypes.data_as(C.POINTER(C.c_int32)), len(mats)) == len(mats)
+    assert (failed is None) == (not g.any()) and (failed is None or f"problem {int(np.flatnonzero(g)[0])}:" in failed), (failed, g)
+    return g
+
+
+def check_safety_net(drv, emu, same_solve, single, monkeypatch):
+    """The set-aside case of tests/splits_batch_common.py in one mixed call: FNN_SW_BATCH_DEP=0.02 reaches every workgroup of a
+    ragged launch as it reaches the same-size kernel.  Per problem: the same give-up as the same-size route, its bytes and
+    counters when it is solved, the certificate, scipy up to 33 taxa.  emu: the CPU driver's library (it says which problems
+    give up); same_solve: splits_batch_common's solve of the same-size route; single: the one-problem solver on the GPU, None
+    on the CPU, where the driver solves the problems that do not give up in a call of their own."""
+    mats, refs = mixed((5, 9, 33, 65, 8, 97, 64, 12), seed=None)
+    ord_of = [r[0] for r in refs]
+    # none of these eight is set aside AND certified (they certify untouched or give up); two of splits_batch_common's list that
+    # certify through set-aside, release and recheck join them, so that the counters of a ragged launch are seen to count
+    for n, pair in ((64, ("outgroup", 4)), (65, ("outgroup", 5))):
+        D, o = sc.class_batch(n, (pair,))
+        mats.append(D[0])
+        ord_of.append(o[0])
+    monkeypatch.setenv("FNN_SW_BATCH_DEP", "0.02")
+    g = emu_weight_giveups(emu, mats, ord_of)
+    print("ragged set-aside: give-ups", g.tolist())
+    assert set(g.tolist()) == {0, sc.GIVEUP_NUMERIC} and (g == 0).sum() >= 5, g     # both populations
+    keep = [b for b in range(len(mats)) if single is not None or g[b] == 0]
+    w, sw, st = drv.weights(Layout([mats[b] for b in keep]), [ord_of[b] for b in keep])
+    assert st.n_fallback == (0 if single is None else int((g != 0).sum())), (st.as_dict(), g)
+    total = dict.fromkeys(sc.COUNTERS, 0)
+    for k, b in enumerate(keep):
+        D, o, n = mats[b], ord_of[b], mats[b].shape[0]
+        w1, sw1, g1, _ = same_solve(D[None], o[None])
+        assert g1[0] == g[b], (b, n, g1, g)
+        if g[b]:
+            assert w[k].tobytes() == single(D, o).tobytes(), (b, n)
+        else:
+            assert w[k].tobytes() == w1[0].tobytes(), (b, n)
+            for c in sc.COUNTERS:
+                assert sw[c][k] == sw1[c][0], (b, n, c)
+                total[c] += int(sw[c][k])
+        xs = None
+        if n <= 33:
+            import scipy.optimize as so
+            xs = so.nnls(sc.W.live_design_matrix(n, o), sc.W.packed_distances(D), maxiter=10 ** 7)[0]
+        sc.assert_solved(D[None], o[None], w[k][None], sw[k: k + 1], 0, ("ragged set-aside", b, n), xs)
+    monkeypatch.delenv("FNN_SW_BATCH_DEP")
+    print("ragged set-aside: counters of the certified", total)
+    assert total["aside_fresh"] > 0 and total["rechecks"] > 0 and total["releases"] > 0, total
+    return total

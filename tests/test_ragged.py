@@ -64,6 +64,12 @@ def test_weights_of_the_mixed_batch(drv, hip_api):
     rc.check_weights(drv, hip_api.split_weights_batch_max_n(), same_calls(hip_api)[1])
 
 
+def test_safety_net_in_one_mixed_call(drv, fa, hip_api, monkeypatch):
+    pytest.importorskip("scipy")
+    emu = sc.emu_api()
+    rc.check_safety_net(drv, rc.emu_api(), sc.product_solver(hip_api, emu), lambda D, o: fa.split_weights(D, o)[0], monkeypatch)
+
+
 @pytest.mark.parametrize("streams", ["1", "2", "4"])
 def test_stream_count_does_not_show(drv, hip_api, monkeypatch, streams):
     """The classes of a chunk spread over one, two or four streams give the same results, orders and weights."""

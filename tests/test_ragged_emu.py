@@ -114,6 +114,11 @@ def test_give_up_in_the_kernel(drv, a, monkeypatch):
     assert f"problem {first}:" in str(ei.value)
 
 
+def test_safety_net_in_one_mixed_call(drv, a, same_size, monkeypatch):
+    pytest.importorskip("scipy")
+    rc.check_safety_net(drv, a, sc.emu_solver(same_size[1]), None, monkeypatch)
+
+
 def test_size_classes_keep_block_size_and_residency():
     """The classes as the launches see them, through the driver's stats: a call of 64- and 65-taxon problems and one of 96- and
     97-taxon problems take two launches each (a class never straddles a block-size edge), 16 with 140 likewise (a small

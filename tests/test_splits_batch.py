@@ -164,3 +164,64 @@ def test_whole_batched_pipeline(fa, oracle):
     assert (w >= 0).all()
     for b in (0, 15):
         assert common.kkt_violation(D[b], orders[b], w[b]) < 1e-9
+
+
+# ---- the safety net, through the test switches (splits_batch_common); which problems give up says the CPU driver -------
+
+@pytest.fixture(scope="module")
+def emu():
+    return sc.emu_api()
+
+
+@pytest.fixture(scope="module")
+def hip_call(hip_api):
+    return lambda D, orders, **kw: sc.run(hip_api, np.ascontiguousarray(D), orders, **kw)
+
+
+@pytest.fixture(scope="module")
+def solve(hip_api, emu):
+    return sc.product_solver(hip_api, emu)
+
+
+@pytest.fixture(scope="module")
+def single(fa):
+    return lambda D, order: fa.split_weights(D, order)[0]
+
+
+def test_set_aside_release_and_recheck(solve, single, monkeypatch):
+    """The kernel itself certified 35 of the 40 problems on the CPU driver (tests/test_splits_batch_emu.py); the GPU has to
+    agree, problem by problem, and the five others come back through the one-problem solver."""
+    pytest.importorskip("scipy")
+    n_solved, n_all, total = sc.check_set_aside(solve, single, monkeypatch)
+    assert (n_solved, n_all) == (35, 40), (n_solved, n_all)
+
+
+def test_give_up_by_steps(solve, single, monkeypatch):
+    sc.check_step_limit(solve, single, monkeypatch)
+
+
+def test_give_up_uncertified(solve, single, monkeypatch):
+    pytest.importorskip("scipy")
+    sc.check_uncertified_end(solve, single, monkeypatch)
+
+
+@pytest.mark.parametrize("n", [8, 33, 64, 65, 96, 97, "max_n"])
+def test_input_classes(hip_call, max_n, n):
+    pytest.importorskip("scipy")
+    sc.check_classes(hip_call, max_n if n == "max_n" else n)
+
+
+@pytest.mark.parametrize("n", [33, 65])
+def test_foreign_orderings(hip_call, n):
+    pytest.importorskip("scipy")
+    sc.check_foreign_orderings(hip_call, n)
+
+
+@pytest.mark.parametrize("n", [2, 3, 8, 65])
+def test_constant_and_zero_matrices(hip_call, n):
+    sc.check_flat(hip_call, n)
+
+
+@pytest.mark.parametrize("n", [33, 65])
+def test_power_of_two_scaling_is_exact(hip_call, n):
+    sc.check_power_of_two(hip_call, n)

@@ -169,3 +169,66 @@ def test_standalone_program_under_asan_ubsan(a):
     r = subprocess.run([exe, "4", "33", "64", str(a.split_weights_batch_max_n())], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert r.stdout.startswith("ok: ")
+
+
+# ---- the safety net, through the test switches (splits_batch_common) ----------------------------------------------------
+
+@pytest.fixture(scope="module")
+def solve(a):
+    return sc.emu_solver(a)
+
+
+def test_switches_ignore_values_outside_their_range(call, monkeypatch):
+    D, orders = sc.synth_batch(12, 6)
+    w0, sw0, _ = call(D, orders)
+    for dep, steps in (("0", "0"), ("1", "-3"), ("-0.5", "x"), ("nan", ""), ("1e-9", str(40 * 12 + 1000))):
+        monkeypatch.setenv("FNN_SW_BATCH_DEP", dep)
+        monkeypatch.setenv("FNN_SW_BATCH_STEPS", steps)
+        w, sw, _ = call(D, orders)
+        assert w.tobytes() == w0.tobytes() and (sw["outer_iterations"] == sw0["outer_iterations"]).all(), (dep, steps)
+
+
+def test_set_aside_release_and_recheck(solve, monkeypatch):
+    pytest.importorskip("scipy")
+    n_solved, n_all, total = sc.check_set_aside(solve, None, monkeypatch)
+    assert (n_solved, n_all) == (35, 40), (n_solved, n_all)   # the share the GPU case compares with
+
+
+def test_give_up_by_steps(a, solve, monkeypatch):
+    D, orders, steps = sc.check_step_limit(solve, None, monkeypatch)
+    # every limit below a problem's own step count, so that the limit falls on a pick and on a ratio step (both sites count)
+    b = 2
+    w0, sw0, _ = sc.run(a, D[b: b + 1], orders[b: b + 1])
+    assert sw0["departed"][0] > 0 and sw0["reserved"][0][2] == steps[b]
+    for L in range(1, int(steps[b]) + 1):
+        monkeypatch.setenv("FNN_SW_BATCH_STEPS", str(L))
+        w, sw, g = sc.emu_solve(a, D[b: b + 1], orders[b: b + 1])
+        assert g[0] == (sc.GIVEUP_STEPS if L < steps[b] else 0), (L, g)
+        assert L < steps[b] or w.tobytes() == w0.tobytes()
+
+
+def test_give_up_uncertified(solve, monkeypatch):
+    pytest.importorskip("scipy")
+    sc.check_uncertified_end(solve, None, monkeypatch)
+
+
+@pytest.mark.parametrize("n", [8, 33, 64, 65, 96, 97, "max_n"])
+def test_input_classes(a, call, n):
+    pytest.importorskip("scipy")
+    sc.check_classes(call, a.split_weights_batch_max_n() if n == "max_n" else n)
+
+
+@pytest.mark.parametrize("n", [33, 65])
+def test_foreign_orderings(call, n):
+    pytest.importorskip("scipy")
+    sc.check_foreign_orderings(call, n)
+
+
+@pytest.mark.parametrize("n", [2, 3, 8, 65])
+def test_constant_and_zero_matrices(call, n):
+    sc.check_flat(call, n)
+
+
+@pytest.mark.parametrize("n", [33, 65])
+def test_power_of_two_scaling_is_exact(call, n):
+    sc.check_power_of_two(call, n)
