@@ -9,13 +9,15 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
-def compare_trajectory(api, oracle, D, deep=True, deep_every=1, **hkw):
+def compare_trajectory(api, oracle, D, deep=True, deep_every=1, handle=None, **hkw):
     """Step engine and oracle together; every event record must agree exactly; with
     `deep`, node ids / partners / Sx bits / the whole live matrix are compared too.
-    (relaxed_seed / relaxed_min_active in hkw put both sides into the Relaxed mode.)"""
+    (relaxed_seed / relaxed_min_active in hkw put both sides into the Relaxed mode.)
+    With `handle`, the run goes through that existing handle (created with the options in hkw by
+    the caller, and left open) instead of a fresh one: a later run on a handle that has run before."""
     n = D.shape[0]
     st = oracle.Stepper(D, relaxed_seed=hkw.get("relaxed_seed"), relaxed_min_active=hkw.get("relaxed_min_active", 0))
-    h = Handle(api, n, **hkw)
+    h = handle if handle is not None else Handle(api, n, **hkw)
     try:
         h.set_matrix(D)
         h.begin()
@@ -43,7 +45,8 @@ def compare_trajectory(api, oracle, D, deep=True, deep_every=1, **hkw):
         assert (o1 == o2).all(), (o1, o2)
         return k, o2
     finally:
-        h.close()
+        if handle is None:
+            h.close()
         st.close()
 
 

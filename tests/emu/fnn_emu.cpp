@@ -61,7 +61,14 @@ struct EmuBackend {
     std::string err() const { return "emu"; }
     int32_t open(int32_t) { return FNN_OK; }
     void close() {}
-    void* alloc(size_t b) { return std::malloc(b ? b : 1); }
+    // FNN_EMU_POISON=<byte> (read at every allocation): the block starts filled with that byte instead of whatever malloc
+    // hands out, so that a word read before this run wrote it has a known, hostile value (tests/test_handle_reuse.py)
+    void* alloc(size_t b) {
+        void* p = std::malloc(b ? b : 1);
+        const char* e = std::getenv("FNN_EMU_POISON");
+        if (p && e && *e) std::memset(p, (int)(std::strtol(e, nullptr, 0) & 0xFF), b ? b : 1);
+        return p;
+    }
     void free(void* p) { std::free(p); }
     size_t max_records(int32_t) { return 1; }
     int32_t memset(void* p, int v, size_t b) { std::memset(p, v, b); return FNN_OK; }
@@ -695,6 +702,9 @@ double emu_chain_serial(const double* buf, int32_t m) {
 }
 
 void emu_set_order_mode(int32_t mode) { g_order_mode = mode % 3; g_update_mode = (mode / 3) % 3; }
+// the backend's allocator by itself, for the test that FNN_EMU_POISON reaches the blocks it hands out
+void* emu_debug_alloc(size_t bytes) { return EmuBackend{}.alloc(bytes); }
+void emu_debug_free(void* p) { EmuBackend{}.free(p); }
 void emu_set_screen_debug(int32_t force_rescan_all, int32_t cand_cap) {
     g_force_rescan_all = force_rescan_all;
     g_cand_cap = cand_cap > 0 ? cand_cap : fnn::SCR_CAP;

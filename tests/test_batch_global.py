@@ -39,6 +39,18 @@ def test_default_route_and_engine_override(a, monkeypatch):
     assert (o2 == orders).all() and (n2 == nev).all() and e2.tobytes() == ev.tobytes()
 
 
+def test_engine_route_on_mixed_classes(a, monkeypatch):
+    """FNN_BATCH_ROUTE=engine: the seven input classes run one after another on the fallback's single engine handle (`fallback`
+    in fnn_batch.hip), so each problem but the first starts in the buffers the previous class left behind - exact ties, zero
+    distances, negative entries (plain fp64 scans), an outgroup.  Against the oracle event by event.  (The CPU drivers of the
+    batch routes have no engine route: tests/test_batch_global_emu.py::test_engine_override.)"""
+    monkeypatch.setenv("FNN_BATCH_ROUTE", "engine")
+    D, refs = bc.class_batch(150)
+    orders, ev, nev, st = bc.run(a, D, events=True)
+    assert st.n_fallback == len(bc.CLASSES) == 7 and st.n_global == 0 and st.n_lds == 0, st.as_dict()
+    bc.assert_matches_oracle(orders, ev, nev, refs, ("engine route", 150))
+
+
 def test_cap(a, monkeypatch):
     bg.check_cap(a, monkeypatch)
 
