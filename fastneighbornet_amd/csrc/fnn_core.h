@@ -2071,6 +2071,53 @@ FNN_HD void close_event(const Dev& d) {
     if (st.ev_finish || st.m <= 3) st.done = 1;
 }
 
+// ---- The event feed's mailbox (fnn_engine.h: agglomerate_feed).  The kernel that closes a launch sequence posts what the
+// host needs to go on enqueueing - and nothing else - into host memory; the host follows these records instead of draining
+// the stream and downloading the control block once per batch.  A record stands for the device AFTER launch sequence
+// `seq` (counted by the host: the first sequence after begin() is 0); sequences that did nothing (stalled, or enqueued
+// after the last event) post too.  The words go out as separate stores and the host reads while the device writes: the
+// check word is a function of the seven others, and the host acts on a record only if it fits and the generation is the
+// running feed's (a torn record, one of an earlier feed, and one it has seen already are passed over).
+struct FeedRec {
+    int64_t seq;
+    int64_t n_events, n_rx_exact;
+    int32_t gen, m, done, stall, la_valid, la_k, la_Kcur, error;
+    uint64_t check;
+};
+static_assert(sizeof(FeedRec) == 64, "a feed record is eight 8-byte words");
+constexpr int FEED_WORDS = 8;
+constexpr int FEED_RING = 8;  // records: sequence s goes to slot s mod FEED_RING, so the host's read rarely meets the device's write
+struct FeedWords { uint64_t w[FEED_WORDS]; };
+FNN_HD uint64_t feed_check_word(const FeedWords& r) {
+    uint64_t h = 0x9E3779B97F4A7C15ULL;
+    for (int i = 0; i < FEED_WORDS - 1; i++) h = (h ^ r.w[i]) * 0xBF58476D1CE4E5B9ULL + (uint64_t)(i + 1);
+    return h ^ (h >> 29);
+}
+FNN_HD FeedWords feed_record(const State& st, int32_t gen, int64_t seq) {
+    FeedRec r;
+    r.seq = seq; r.n_events = st.n_events; r.n_rx_exact = st.n_rx_exact;
+    r.gen = gen; r.m = st.m; r.done = st.done; r.stall = st.stall;
+    r.la_valid = st.la_valid; r.la_k = st.la_k; r.la_Kcur = st.la_Kcur; r.error = st.error;
+    r.check = 0;
+    FeedWords w = __builtin_bit_cast(FeedWords, r);
+    w.w[FEED_WORDS - 1] = feed_check_word(w);
+    return w;
+}
+// host side: the newest record of generation `gen` in the ring that is whole and newer than sequence `seen`
+inline bool feed_pick(const FeedRec* ring, int nring, int32_t gen, int64_t seen, FeedRec* out) {
+    bool found = false;
+    for (int i = 0; i < nring; i++) {
+        FeedWords w;
+        const uint64_t* src = reinterpret_cast<const uint64_t*>(ring + i);
+        for (int k = 0; k < FEED_WORDS; k++) w.w[k] = __atomic_load_n(src + k, __ATOMIC_RELAXED);
+        if (w.w[FEED_WORDS - 1] != feed_check_word(w)) continue;
+        const FeedRec r = __builtin_bit_cast(FeedRec, w);
+        if (r.gen != gen || r.seq <= seen) continue;
+        if (!found || r.seq > out->seq) { *out = r; found = true; }
+    }
+    return found;
+}
+
 // NetMakerOriginal.initialize (:164-191) for the all-singleton start: node k receives
 // D[0][k], ..., D[k-1][k] (as q of the outer nodes p < k) and then D[k][k+1..n-1] (as p),
 // i.e. one sequential sum over j != k in ascending j.  Also sets up the identity layout.

@@ -15,6 +15,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/fastnn.h"
@@ -491,10 +493,13 @@ class Engine {
 
     // one event: scan (+ exchange of the per-rank candidates) + the rest of the sequence.
     // after a state download: when will the open window have served its K events?
-    void resync_schedule() {
+    // `next`: the launch sequence that follows the state in hst - ev_counter after a drained stream; under the feed the state
+    // is a record's, of sequence s, and ev_counter is ahead of it: s + 1.
+    void resync_schedule(int64_t next) {
         if (!dev.la) return;
-        sched_at = (hst.la_valid && !hst.stall) ? ev_counter + (hst.la_Kcur + 1 > hst.la_k ? hst.la_Kcur + 1 - hst.la_k : 0) : ev_counter;
+        sched_at = (hst.la_valid && !hst.stall) ? next + (hst.la_Kcur + 1 > hst.la_k ? hst.la_Kcur + 1 - hst.la_k : 0) : next;
     }
+    void resync_schedule() { resync_schedule(ev_counter); }
     // A rank contributes nper candidate records (1 after a local reduction, or the scan's
     // GATHER_RECS per-workgroup records as they are).
     // force_sched: -1 = follow the schedule, 0 / 1 = the caller knows whether this event scans
@@ -586,11 +591,115 @@ class Engine {
         return 1;
     }
 
+    // ---- The continuous feed (single rank, Canonical mode, a backend with a mailbox): the host never drains the stream
+    // between events.  The kernel that closes a launch sequence posts a FeedRec (fnn_core.h) into host memory; the host
+    // keeps at most feed_depth sequences in flight beyond the newest record it has seen and enqueues whenever there is
+    // room.  What it takes from a record is what it took from the state after a batch: the bound of the live nodes, the
+    // open window's progress (when to schedule the next base scan), a stall, the count of exact ComputeRx sums - all of them
+    // tolerated stale before, by up to a batch, and now by up to feed_depth sequences.  The pending row sum is flushed,
+    // the stream drained and the state downloaded ONCE, after a record shows the end of the run or an error.
+    // (FNN_FEED_DEPTH.  8: the best of 8, 16, 32 and 64 at 32768 taxa, profiles/r11.  A stall episode costs about feed_depth
+    //  sequences that do nothing - and those return so fast that the device runs the queue dry before the host's scan arrives -
+    //  so a deep feed pays for slack it does not need: the host enqueues a sequence in a quarter of the time the device runs it.)
+    int32_t feed_depth = 8;
+    int64_t feed_seen = -1;      // sequence number of the newest record taken
+    int64_t feed_sched_idx = -1; // sequence number of the newest launch sequence with a scheduled scan
+    int64_t feed_note_at = 0;    // the backend hears of the exact sums once per `batch` sequences, as it did once per batch
+    int64_t feed_tail = 0;       // launch sequences enqueued behind the last event (diagnostic; at most feed_depth)
+    // A record of sequence s: the device as it was after s, while ev_counter is ahead of it.
+    void feed_take(const FeedRec& r) {
+        feed_seen = r.seq;
+        hst.m = r.m; hst.done = r.done; hst.stall = r.stall; hst.error = r.error;
+        hst.la_valid = r.la_valid; hst.la_k = r.la_k; hst.la_Kcur = r.la_Kcur;
+        hst.n_events = r.n_events; hst.n_rx_exact = r.n_rx_exact;
+        m_bound = r.m;
+        // (a record from before the newest scheduled scan knows nothing of the window that scan opens - or of the stall it
+        //  ends: the host's own estimate from enqueue_event stands until a record from behind that scan arrives)
+        if (r.seq >= feed_sched_idx) resync_schedule(r.seq + 1);
+        if (r.seq >= feed_note_at) {
+            be.note_rx_exact(r.n_rx_exact);
+            feed_note_at = r.seq + batch;
+        }
+    }
+    template <class BB>
+    int32_t agglomerate_feed(BB& fb) {
+        feed_depth = 8;
+        env_int("FNN_FEED_DEPTH", 1, 4096, &feed_depth);
+        double wait_s = 30.0;  // no record for this long while sequences are in flight: the run fails, it does not hang
+        { int32_t ms = 0; if (env_int("FNN_FEED_WAIT_MS", 1, INT_MAX, &ms)) wait_s = ms * 1e-3; }
+        be.defer_chain = dev.la != 0 && !std::getenv("FNN_NO_DEFER");
+        feed_seen = ev_counter - 1;
+        feed_sched_idx = -1;
+        feed_note_at = ev_counter + batch - 1;
+        feed_tail = 0;
+        int32_t rc = FNN_OK;
+        FeedRec r{};
+        while (rc == FNN_OK && !hst.done && !hst.error) {
+            rc = enqueue_status_exchange();  // (single rank: only the FNN_FAULT_ERROR hook)
+            if (rc != FNN_OK) break;
+            if (fb.feed_newest(feed_seen, &r)) { feed_take(r); continue; }
+            // room: feed_depth sequences beyond the newest record, and no more than the events that are left: the sequences
+            // behind the last event do nothing.  (A run has n - 1 events, n - 2 where the special finish comes one event
+            // early; should a run ever have more, its last events go one sequence at a time - slower, never wrong.)
+            const int64_t left = (int64_t)n - 1 - hst.n_events;
+            const int64_t room = left < feed_depth ? (left > 1 ? left : 1) : feed_depth;
+            if (ev_counter - (feed_seen + 1) < room) {
+                const int64_t cnt = ev_counter, at = sched_at;
+                rc = enqueue_event();
+                if (sched_at != at) feed_sched_idx = cnt;  // (enqueue_event moves sched_at exactly when it schedules a scan)
+                continue;
+            }
+            const int32_t w = fb.feed_wait(feed_seen, &r, wait_s);
+            if (w == FNN_OK) feed_take(r);
+            else if (w == 1) {
+                // the stream ran dry and no record came: read the state the ordinary way and go on from it
+                rc = pull_state();
+                if (rc != FNN_OK) break;
+                feed_seen = ev_counter - 1;
+                m_bound = hst.m;
+                resync_schedule(ev_counter);
+            } else rc = fail(FNN_EHIP, "fnn_run: no word from the device within " + std::to_string(wait_s) + " s, or the stream failed (" + be.err() + ")");
+        }
+        fb.feed_end();
+        if (rc == FNN_OK) {
+            feed_tail = ev_counter - (feed_seen + 1);
+            if (be.defer_chain) rc = launched(be.launch_chain_flush(dev));
+        }
+        be.defer_chain = false;
+        if (rc != FNN_OK) return rc;
+        if (be.sync() != FNN_OK) return fail(FNN_EHIP, "fnn_run: sync failed (" + be.err() + ")");
+        rc = pull_state();
+        if (rc != FNN_OK) return rc;
+        m_bound = hst.m;
+        resync_schedule(ev_counter);
+        be.note_rx_exact(hst.n_rx_exact);
+        if (hst.done) ended = true;
+        return FNN_OK;
+    }
+    // (the capability check: a backend without a mailbox - the CPU emulation, the counting backend of the buffer table's test -
+    //  compiles against this header as it is and always takes the batch loop)
+    template <class T, class = void> struct has_feed : std::false_type {};
+    template <class T>
+    struct has_feed<T, std::void_t<decltype(std::declval<T&>().feed_begin(int64_t{})), decltype(std::declval<T&>().feed_newest(int64_t{}, (FeedRec*)nullptr)),
+                                   decltype(std::declval<T&>().feed_wait(int64_t{}, (FeedRec*)nullptr, 0.0)), decltype(std::declval<T&>().feed_end())>> : std::true_type {};
+
     // the whole agglomNodes loop without per-event round trips
     int32_t agglomerate() {
         if (!begun) return fail(FNN_ESTATE, "agglomerate: call fnn_begin first");
         double t0 = now_s();
         env_int("FNN_BATCH", 1, 4096, &batch);
+        // The feed, where it applies.  The batch loop below stays for several ranks (their status exchange is per batch), for the
+        // timing of every kernel (an event pair per launch, drained at every sync), for the Relaxed mode, for FNN_FEED=0 and
+        // for every backend without a mailbox.
+        if constexpr (has_feed<B>::value) {
+            bool feed = true;
+            env_flag("FNN_FEED", &feed);
+            if (feed && !ended && comm_mode == 0 && !relaxed() && be.feed_timing_ok() && be.feed_begin(ev_counter)) {  // (false: no mailbox)
+                const int32_t rc = agglomerate_feed(be);
+                if (rc == FNN_OK) stats.t_agglom_s = now_s() - t0;
+                return rc;
+            }
+        }
         while (!ended) {
             // with lookahead windows on, k_update closes the events and the exact row sum of the new
             // cluster is computed inside the next event's k_track (flushed before the host looks)

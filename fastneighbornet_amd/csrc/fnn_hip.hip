@@ -2905,7 +2905,26 @@ __global__ __launch_bounds__(TRK_THREADS) void k_track(Dev d, int force_base, in
 // so a phase is a few dozen instructions.  Same operations, same order, same roundings as the generic bodies (which
 // the CPU emulation runs against the oracle); the GPU parity tests compare Sx, T's consumers and the live matrix
 // after every event.  Returns this lane's addends {row-sum addend, T terms of u, v} of the add phase.
-__global__ __launch_bounds__(256) void k_update(Dev d, int defer, int ticks) {
+// The event feed (fnn_core.h: FeedRec): ONE lane posts the record of launch sequence `seq` into the host's mailbox (pinned,
+// coherent host memory; box == nullptr: the host drains the stream per batch and no record goes out).  Eight relaxed
+// system-scope stores of values that come from registers and LDS: no fence and no release - nothing else has to be visible
+// with the record, and a release would be a write-back of the L2 on the closing leg of the event.  The host checks the
+// record's check word (feed_pick).
+struct FeedArg {
+    FeedRec* box;
+    int64_t seq;
+    int32_t gen;
+};
+__device__ __forceinline__ void feed_post(const FeedArg& f, const State& st) {
+    if (!f.box) return;
+    const FeedWords w = feed_record(st, f.gen, f.seq);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(f.box + (int)(f.seq & (FEED_RING - 1)));
+#pragma unroll
+    for (int k = 0; k < FEED_WORDS; k++) __hip_atomic_store(dst + k, w.w[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+static_assert((FEED_RING & (FEED_RING - 1)) == 0, "the ring's slot is the low bits of the sequence number");
+
+__global__ __launch_bounds__(256) void k_update(Dev d, int defer, int ticks, FeedArg feed) {
     __shared__ double shp[4][4];
     __shared__ State lst;  // the workgroup of the involved slots fetches the control block ONCE, with one coalesced load
     State* st = d.st;
@@ -2955,10 +2974,20 @@ __global__ __launch_bounds__(256) void k_update(Dev d, int defer, int ticks) {
         const double pusx = up->usx;
         state_in(lst, st);
         __syncthreads();
-        if (!lst.ev_active || lst.stall) return;
+        // The feed's record goes out at ONE place, behind this block (the kernel arguments it needs are then loaded there, not
+        // carried through the phases).  A sequence that does nothing - stalled, or behind the last event - and one that ends
+        // in error 15 post like any other: the host counts what is in flight by the sequence number.  Without `defer`
+        // k_finalize closes the event and posts.  act: bit 0 = post, bit 1 = the event was applied (go on to the partial sums).
+        int act = 0;
+        do {
+        if (!lst.ev_active || lst.stall) { act = defer ? 1 : 0; break; }
         if (pevent != lst.n_events || pu_id != lst.cur.u_id) {  // (not expected: an event decided without leaving its record)
-            if (t == 0) { st->error = 15; up->cnt[2] += 1; }
-            return;
+            if (t == 0) {
+                st->error = 15; up->cnt[2] += 1;
+                lst.error = 15;
+            }
+            act = 1;
+            break;
         }
         UPD_TICK(0);
         Dev dl = d;
@@ -3000,6 +3029,11 @@ __global__ __launch_bounds__(256) void k_update(Dev d, int defer, int ticks) {
             }
         }
         __syncthreads();
+        act = defer ? 3 : 2;
+        } while (0);
+        // (beside state_out: the record is the closed control block's few words the host follows, from LDS)
+        if ((act & 1) && t == 0) feed_post(feed, lst);
+        if (!(act & 2)) return;
         state_out(st, lst);
     }
     // per-workgroup partial sums (tree order): of the new cluster's row-sum addends and their magnitudes (for
@@ -3057,14 +3091,20 @@ __device__ __forceinline__ double serial_chain_sum(const double* buf, int m, dou
     return s;
 }
 
-__global__ __launch_bounds__(CH_T) void k_finalize(Dev d) {
+__global__ __launch_bounds__(CH_T) void k_finalize(Dev d, FeedArg feed) {
     __shared__ ChainLds<CH_EPT> L;
     __shared__ double ser[SER_CHUNK];
     State* st = d.st;
-    if (!st->ev_active || st->stall) return;
+    if (!st->ev_active || st->stall) {
+        if (threadIdx.x == 0) feed_post(feed, *st);
+        return;
+    }
     double usx = 0.0;
     if (!st->ev_finish) usx = st->nonneg ? block_chain_sum2<CH_EPT>(d.chain, st->m, CH_GUARD_BITS, L, nullptr) : serial_chain_sum(d.chain, st->m, ser);
-    if (threadIdx.x == 0) finalize(d, usx);
+    if (threadIdx.x == 0) {
+        finalize(d, usx);
+        feed_post(feed, *st);  // (this kernel closes the event when k_update does not: the feed's record goes out here)
+    }
 }
 
 // diagnostic entry: the block chain sum on an arbitrary buffer (tests)
@@ -3290,6 +3330,16 @@ struct HipBackend {
         while ((track_grid + track_group - 1) / track_group > 64) track_group *= 2;
         env_int("FNN_RELAXED_GRID", 1, RL_GMAX, &relaxed_grid);
         screen_min_m_fixed = env_int("FNN_SCREEN_MIN_M", 8, INT_MAX, &screen_min_m);
+        // the feed's mailbox (a handle that cannot have one runs without a feed)
+        if (hipHostMalloc((void**)&box, sizeof(FeedRec) * FEED_RING, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+            (void)hipGetLastError();
+            box = nullptr;
+        }
+        if (box && hipHostGetDevicePointer((void**)&box_dev, box, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipHostFree(box);
+            box = nullptr;
+        }
         opened = true;
         return FNN_OK;
     }
@@ -3305,6 +3355,10 @@ struct HipBackend {
         if (d_stage) (void)hipFree(d_stage);
         d_stage = nullptr;
         stage_cap = 0;
+        if (stream) (void)hipStreamSynchronize(stream);  // (nothing may still be on its way into the mailbox when it goes)
+        if (box) (void)hipHostFree(box);
+        box = box_dev = nullptr;
+        feed_on = false;
         if (stream) (void)hipStreamDestroy(stream);
         stream = nullptr;
         opened = false;
@@ -3528,8 +3582,54 @@ struct HipBackend {
             track_tag = (track_tag % 0x7FFFFFEu) + 1u;
             launch(TC_DECIDE, tall, help ? k_decide<true> : k_decide<false>, dim3(1 + (help ? TRK_NHELP : 0)), dim3(CH_T), d, src, nrecs, track_tag);
         }
-        launch(TC_UPDATE, tall, k_update, dim3(grid1(m_bound).x + 1), dim3(256), d, defer_chain ? 1 : 0, ticks ? 1 : 0);
-        if (!defer_chain) launch(TC_OTHER, tall, k_finalize, dim3(1), dim3(CH_T), d);
+        // (the feed's sequence number is counted here like track_tag: one per launch sequence while a feed runs)
+        const FeedArg feed{feed_on ? box_dev : nullptr, feed_on ? feed_seq++ : 0, feed_gen};
+        launch(TC_UPDATE, tall, k_update, dim3(grid1(m_bound).x + 1), dim3(256), d, defer_chain ? 1 : 0, ticks ? 1 : 0, feed);
+        if (!defer_chain) launch(TC_OTHER, tall, k_finalize, dim3(1), dim3(CH_T), d, feed);
+    }
+    // ---- The event feed's mailbox (fnn_core.h: FeedRec; fnn_engine.h: agglomerate_feed): FEED_RING records in pinned, coherent
+    // host memory that lives as long as the handle.  Without it (the allocation failed) feed_begin says no and the engine
+    // drains the stream per batch as before.
+    FeedRec* box = nullptr;      // as the host reads it
+    FeedRec* box_dev = nullptr;  // ... and as the kernels write it
+    bool feed_on = false;
+    int32_t feed_gen = 0;
+    int64_t feed_seq = 0;
+    // a new feed whose first launch sequence is `first_seq`: a new generation, an empty ring.  (The stream is drained here:
+    // nothing of an earlier feed is still on its way into the ring while the host clears it.)
+    bool feed_begin(int64_t first_seq) {
+        if (!box || !HIPOK(hipStreamSynchronize(stream))) return false;
+        feed_gen = feed_gen == INT32_MAX ? 1 : feed_gen + 1;
+        std::memset(box, 0, sizeof(FeedRec) * FEED_RING);
+        feed_seq = first_seq;
+        feed_on = true;
+        return true;
+    }
+    void feed_end() { feed_on = false; }
+    // (with every kernel timed, each sync drains an event pair per launch: such a run keeps its batches)
+    bool feed_timing_ok() const { return timing != 2; }
+    // the newest whole record of this feed beyond sequence `seen`, without synchronising
+    bool feed_newest(int64_t seen, FeedRec* out) const { return feed_pick(box, FEED_RING, feed_gen, seen, out); }
+    // ... and the same, waiting for one: FNN_OK with a record; 1 when the stream has run dry without one (the caller then
+    // reads the state the ordinary way); FNN_EHIP on a HIP error, or when `limit_s` seconds pass.  Never spins for ever.
+    int32_t feed_wait(int64_t seen, FeedRec* out, double limit_s) {
+        // (The stream is asked only after a millisecond without a record, and then once per millisecond: records come every few
+        //  dozen microseconds while the device works, so a healthy run never asks.  hipStreamQuery is not free for the DEVICE:
+        //  the runtime puts a marker with a completion signal behind the last kernel to answer it, and asked every few
+        //  microseconds - the first form of this loop - that cost every kernel boundary of the run: +100 ms at 32768 taxa.)
+        const double t0 = now_s();
+        double asked = t0;
+        for (int64_t spins = 1;; spins++) {
+            if (feed_newest(seen, out)) return FNN_OK;
+            if (spins % 64) continue;
+            const double t = now_s();
+            if (t - asked < 1e-3) continue;
+            asked = t;
+            const hipError_t q = hipStreamQuery(stream);
+            if (q == hipSuccess) return feed_newest(seen, out) ? FNN_OK : 1;
+            if (q != hipErrorNotReady) { last = q; return FNN_EHIP; }
+            if (t - t0 > limit_s) { last = hipErrorNotReady; return FNN_EHIP; }
+        }
     }
     // single GPU: the whole event.  (m_bound >= 1 in all of these: Engine::enqueue_event sees to it)
     int32_t launch_event(const Dev& d, int32_t m_bound, bool sched) {
