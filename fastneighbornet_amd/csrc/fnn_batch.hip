@@ -115,52 +115,11 @@ __global__ __launch_bounds__(256) void k_small_validate(const double* __restrict
     if (small_validate_thread((int)threadIdx.x, (int)blockDim.x, D + b * stride, n, ld)) atomicMin(first_bad, (int32_t)blockIdx.x);
 }
 
-struct SmallHipBackend {
-    std::vector<void*> bufs;
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    std::string last;
+struct SmallHipBackend : HipBatchBase {
     int32_t* d_bad = nullptr;
     unsigned long long* d_bad64 = nullptr;
     RaggedLauncher ragged{RAGGED_ORDER_STREAMS};
-    int prev_device = -1;  // the caller's current device, restored when the call ends
 
-    ~SmallHipBackend() {
-        for (void* p : bufs) (void)hipFree(p);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (prev_device >= 0) (void)hipSetDevice(prev_device);
-    }
-    const std::string& err() const { return last; }
-    bool ok(hipError_t e, const char* what) {
-        if (e == hipSuccess) return true;
-        last = std::string(what) + ": " + hipGetErrorString(e);
-        return false;
-    }
-    int32_t open(int32_t device) {
-        int cnt = 0;
-        if (!ok(hipGetDeviceCount(&cnt), "hipGetDeviceCount")) return FNN_EHIP;
-        if (device < 0 || device >= cnt) { last = "no HIP device " + std::to_string(device) + " (there is no CPU fallback)"; return FNN_EHIP; }
-        int cur = -1;
-        if (hipGetDevice(&cur) == hipSuccess && cur != device) prev_device = cur;
-        if (!ok(hipSetDevice(device), "hipSetDevice") || !ok(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "hipStreamCreate") ||
-            !ok(hipEventCreate(&e0), "hipEventCreate") || !ok(hipEventCreate(&e1), "hipEventCreate"))
-            return FNN_EHIP;
-        return FNN_OK;
-    }
-    void* alloc(size_t bytes) {
-        void* p = nullptr;
-        if (!ok(hipMalloc(&p, bytes ? bytes : 1), "hipMalloc")) return nullptr;
-        bufs.push_back(p);
-        return p;
-    }
-    int32_t h2d(void* dst, const void* src, size_t bytes) {
-        return ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream), "hipMemcpy") && ok(hipStreamSynchronize(stream), "upload") ? FNN_OK : FNN_EHIP;
-    }
-    int32_t d2h(void* dst, const void* src, size_t bytes) {
-        return ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream), "hipMemcpy") && ok(hipStreamSynchronize(stream), "download") ? FNN_OK : FNN_EHIP;
-    }
     int32_t validate(const double* dD, int32_t n, int64_t ld, int64_t stride, int64_t cnt, int64_t* bad) {
         if (!d_bad && !(d_bad = (int32_t*)alloc(sizeof(int32_t)))) return FNN_EHIP;
         int32_t h = INT_MAX;
@@ -173,33 +132,16 @@ struct SmallHipBackend {
     }
     int32_t run(const double* dD, int32_t n, int64_t ld, int64_t stride, int64_t cnt, int32_t threads, int32_t lds_bytes,
                 int32_t* d_meta, Agg3Rec* d_log, Event* d_ev, double* t_kernel_s) {
-        // more than 64 KiB of dynamic LDS has to be asked for
-        if (!ok(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_small), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
-                "hipFuncSetAttribute"))
-            return FNN_EHIP;
         const int32_t vec = (ld == n && stride % 2 == 0 && reinterpret_cast<uintptr_t>(dD) % 16 == 0) ? 1 : 0;
-        if (!ok(hipEventRecord(e0, stream), "hipEventRecord")) return FNN_EHIP;
-        hipLaunchKernelGGL(k_small, dim3((unsigned)cnt), dim3((unsigned)threads), (size_t)lds_bytes, stream, dD, n, ld, stride, vec, d_meta, d_log, d_ev);
-        if (!ok(hipGetLastError(), "k_small launch")) return FNN_EHIP;
-        if (!ok(hipEventRecord(e1, stream), "hipEventRecord") || !ok(hipEventSynchronize(e1), "k_small")) return FNN_EHIP;
-        float ms = 0.f;
-        if (!ok(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime")) return FNN_EHIP;
-        *t_kernel_s = (double)ms * 1e-3;
-        return FNN_OK;
+        return timed_launch(reinterpret_cast<const void*>(&k_small), "k_small", lds_bytes, [&] {
+            hipLaunchKernelGGL(k_small, dim3((unsigned)cnt), dim3((unsigned)threads), (size_t)lds_bytes, stream, dD, n, ld, stride, vec, d_meta, d_log, d_ev);
+        }, t_kernel_s);
     }
     int32_t run_global(const double* src, int64_t ld, int64_t stride, double* work, int64_t cnt, int32_t n, int32_t threads, int32_t lds_bytes,
                        int32_t* d_meta, Agg3Rec* d_log, Event* d_ev, double* t_kernel_s) {
-        if (!ok(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_small_global), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
-                "hipFuncSetAttribute"))
-            return FNN_EHIP;
-        if (!ok(hipEventRecord(e0, stream), "hipEventRecord")) return FNN_EHIP;
-        hipLaunchKernelGGL(k_small_global, dim3((unsigned)cnt), dim3((unsigned)threads), (size_t)lds_bytes, stream, src, n, ld, stride, work, d_meta, d_log, d_ev);
-        if (!ok(hipGetLastError(), "k_small_global launch")) return FNN_EHIP;
-        if (!ok(hipEventRecord(e1, stream), "hipEventRecord") || !ok(hipEventSynchronize(e1), "k_small_global")) return FNN_EHIP;
-        float ms = 0.f;
-        if (!ok(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime")) return FNN_EHIP;
-        *t_kernel_s = (double)ms * 1e-3;
-        return FNN_OK;
+        return timed_launch(reinterpret_cast<const void*>(&k_small_global), "k_small_global", lds_bytes, [&] {
+            hipLaunchKernelGGL(k_small_global, dim3((unsigned)cnt), dim3((unsigned)threads), (size_t)lds_bytes, stream, src, n, ld, stride, work, d_meta, d_log, d_ev);
+        }, t_kernel_s);
     }
     // ---- ragged batches (small_ragged<B>, fnn_small.h)
     int32_t validate_ragged(const double* base, const RaggedDesc* d_desc, int64_t cnt, int64_t* bad) {
@@ -302,15 +244,6 @@ struct SmallHipBackend {
 };
 
 }  // namespace fnn
-
-#define FNN_BATCH_TRY(body)                                                   \
-    try {                                                                     \
-        body                                                                  \
-    } catch (const std::bad_alloc&) {                                         \
-        return fnn::fail(FNN_ENOMEM, "out of host memory");                   \
-    } catch (const std::exception& e) {                                       \
-        return fnn::fail(FNN_ESTATE, std::string("exception: ") + e.what()); \
-    }
 
 extern "C" {
 

@@ -490,6 +490,52 @@ FNN_HD void small_problem(Exec& ex, const SmallView& V, Event* gev, int32_t* gme
 // Results go to the caller's arrays only when the whole call has succeeded.
 constexpr int64_t SMALL_CHUNK_BYTES = (int64_t)2 << 30;  // device buffer for matrices per chunk
 
+// ---- steps that every batch call takes (the routes of this header, fnn_small_global.h and fnn_small_splits.h), one
+// definition each.  A call reads a switch once, before its first chunk.
+// FNN_BATCH_THREADS=256|512|1024: the block size of every launch of the call; 0: not set
+inline int32_t batch_threads_switch() {
+    if (const char* e = std::getenv("FNN_BATCH_THREADS")) { int v = std::atoi(e); if (v == 256 || v == 512 || v == 1024) return v; }
+    return 0;
+}
+// FNN_BATCH_CHUNK=<problems >= 1>: the problems of one chunk; 0: not set
+inline int64_t batch_chunk_switch() {
+    if (const char* e = std::getenv("FNN_BATCH_CHUNK")) { long long v = std::atoll(e); if (v >= 1) return v; }
+    return 0;
+}
+// Problems per chunk of a same-size call: what SMALL_CHUNK_BYTES holds (or the switch), at most the batch, at least one.
+// even: as many chunks, of equal size (no short last launch).
+inline int64_t batch_chunk(int64_t batch, int64_t bytes_per_problem, bool even) {
+    int64_t chunk = SMALL_CHUNK_BYTES / bytes_per_problem;
+    if (const int64_t v = batch_chunk_switch()) chunk = v;
+    if (chunk > batch) chunk = batch;
+    if (chunk < 1) chunk = 1;
+    if (even) { const int64_t chunks = (batch + chunk - 1) / chunk; chunk = (batch + chunks - 1) / chunks; }
+    return chunk;
+}
+// the rows of one n x n matrix (row stride ld) to an image with row stride dld; what lies between the rows is not written
+inline void pack_rows(double* dst, int64_t dld, const double* src, int64_t ld, int32_t n) {
+    for (int32_t r = 0; r < n; r++) std::memcpy(dst + (int64_t)r * dld, src + (int64_t)r * ld, sizeof(double) * (size_t)n);
+}
+// the two failures that name the caller's index of the problem at fault
+inline int32_t fail_bad_matrix(const std::string& W, int64_t b) {
+    return fail(FNN_EINVAL, W + "problem " + std::to_string(b) + ": matrix is not symmetric, not finite or has a non-zero diagonal");
+}
+inline int32_t fail_nonfinite(const std::string& W, int64_t b) {
+    return fail(FNN_EINVAL, W + "problem " + std::to_string(b) + ": the distances contain a NaN or an infinity");
+}
+// The outputs of an order call.  The call fills these and commits as its last step: a failing call returns before that
+// and leaves the caller's arrays untouched.
+struct OrderStage {
+    std::vector<int32_t> orders, nev;
+    std::vector<fnn_event> evs;  // (zero: the fill behind each problem's last event; empty when no events are wanted)
+    OrderStage(int64_t batch, size_t order_ints, size_t event_recs) : orders(order_ints), nev((size_t)batch, 0), evs(event_recs) {}
+    void commit(int32_t* orders_out, fnn_event* events_out, int32_t* nevents_out) const {
+        std::memcpy(orders_out, orders.data(), sizeof(int32_t) * orders.size());
+        if (events_out) std::memcpy(events_out, evs.data(), sizeof(fnn_event) * evs.size());
+        if (nevents_out) std::memcpy(nevents_out, nev.data(), sizeof(int32_t) * nev.size());
+    }
+};
+
 // One chunk's result records (problems b0 ... b0 + cnt - 1) to orders, event counts and the zero fill behind each problem's
 // last event; shared by the LDS route below and the global-memory route (fnn_small_global.h).
 // one problem's result record (mt: its SMALL_META_INTS words, log: its merge log) to its order; the caller's index is `b`
@@ -541,25 +587,20 @@ int32_t small_batch(B& be, const char* who, const double* D, bool on_device, int
         if (stats) *stats = st;
         return FNN_OK;
     }
-    std::vector<int32_t> orders((size_t)batch * (size_t)(n + 1));
-    std::vector<fnn_event> evs(events_out ? (size_t)batch * (size_t)n : 0);
-    std::vector<int32_t> nev((size_t)batch, 0);
+    OrderStage out(batch, (size_t)batch * (size_t)(n + 1), events_out ? (size_t)batch * (size_t)n : 0);
     int32_t rc;
     if (n > SMALL_LDS_MAX_N) {  // too large for LDS: the one-problem engine, one handle for all
-        rc = be.fallback(W, D, on_device, n, ld, stride, batch, opts, orders.data(), events_out ? evs.data() : nullptr, nev.data(), st);
+        rc = be.fallback(W, D, on_device, n, ld, stride, batch, opts, out.orders.data(), events_out ? out.evs.data() : nullptr, out.nev.data(), st);
         if (rc != FNN_OK) return rc;
     } else {
         rc = be.open(opts.device);
         if (rc != FNN_OK) return fail(rc, W + be.err());
         const SmallLayout L = small_layout(n);
         st.block_threads = small_block_threads(n);
-        if (const char* e = std::getenv("FNN_BATCH_THREADS")) { int v = std::atoi(e); if (v == 256 || v == 512 || v == 1024) st.block_threads = v; }
+        if (const int32_t v = batch_threads_switch()) st.block_threads = v;
         st.lds_bytes = L.bytes;
         const int64_t pitch = round_up((int64_t)n * n, 2);  // doubles per problem in the device buffer: every problem 16-byte aligned
-        int64_t chunk = SMALL_CHUNK_BYTES / (8 * pitch);
-        if (const char* e = std::getenv("FNN_BATCH_CHUNK")) { long long v = std::atoll(e); if (v >= 1) chunk = v; }
-        if (chunk > batch) chunk = batch;
-        if (chunk < 1) chunk = 1;
+        const int64_t chunk = batch_chunk(batch, 8 * pitch, false);  // (the last chunk may be short)
         // the caller's array is the device image already only if it is dense and every problem 16-byte aligned in it; anything
         // else is packed (an upload of whole pitches from the caller's array would read past its last problem)
         const bool dense = ld == n && stride == (int64_t)n * n && stride == pitch;
@@ -581,9 +622,7 @@ int32_t small_batch(B& be, const char* who, const double* D, bool on_device, int
                 const double tu = now_s();
                 const double* up = src;
                 if (!dense) {  // rows to a dense image (padding is never read)
-                    for (int64_t b = 0; b < cnt; b++)
-                        for (int32_t r = 0; r < n; r++)
-                            std::memcpy(&pack[(size_t)(b * pitch + (int64_t)r * n)], src + b * stride + (int64_t)r * ld, sizeof(double) * (size_t)n);
+                    for (int64_t b = 0; b < cnt; b++) pack_rows(&pack[(size_t)(b * pitch)], n, src + b * stride, ld, n);
                     up = pack.data();
                 }
                 if (be.h2d(dD, up, sizeof(double) * (size_t)(cnt * pitch)) != FNN_OK) return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
@@ -593,8 +632,7 @@ int32_t small_batch(B& be, const char* who, const double* D, bool on_device, int
             if (opts.validate) {
                 int64_t bad = -1;
                 if (be.validate(src, n, kld, kstride, cnt, &bad) != FNN_OK) return fail(FNN_EHIP, W + "validate failed (" + be.err() + ")");
-                if (bad >= 0)
-                    return fail(FNN_EINVAL, W + "problem " + std::to_string(b0 + bad) + ": matrix is not symmetric, not finite or has a non-zero diagonal");
+                if (bad >= 0) return fail_bad_matrix(W, b0 + bad);
             }
             double tk = 0.0;
             if (be.run(src, n, kld, kstride, cnt, st.block_threads, L.bytes, d_meta, d_log, d_ev, &tk) != FNN_OK)
@@ -602,16 +640,14 @@ int32_t small_batch(B& be, const char* who, const double* D, bool on_device, int
             st.t_kernel_s += tk;
             if (be.d2h(meta.data(), d_meta, sizeof(int32_t) * SMALL_META_INTS * (size_t)cnt) != FNN_OK ||
                 be.d2h(log.data(), d_log, sizeof(Agg3Rec) * (size_t)n * (size_t)cnt) != FNN_OK ||
-                (d_ev && be.d2h(&evs[(size_t)b0 * (size_t)n], d_ev, sizeof(Event) * (size_t)n * (size_t)cnt) != FNN_OK))
+                (d_ev && be.d2h(&out.evs[(size_t)b0 * (size_t)n], d_ev, sizeof(Event) * (size_t)n * (size_t)cnt) != FNN_OK))
                 return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
-            rc = small_collect(W, n, b0, cnt, meta.data(), log.data(), orders.data(), nev.data(), events_out ? evs.data() : nullptr, st);
+            rc = small_collect(W, n, b0, cnt, meta.data(), log.data(), out.orders.data(), out.nev.data(), events_out ? out.evs.data() : nullptr, st);
             if (rc != FNN_OK) return rc;
             st.n_lds += cnt;
         }
     }
-    std::memcpy(orders_out, orders.data(), sizeof(int32_t) * orders.size());
-    if (events_out) std::memcpy(events_out, evs.data(), sizeof(fnn_event) * evs.size());
-    if (nevents_out) std::memcpy(nevents_out, nev.data(), sizeof(int32_t) * nev.size());
+    out.commit(orders_out, events_out, nevents_out);
     st.t_total_s = now_s() - t0;
     if (stats) *stats = st;
     return FNN_OK;
@@ -637,10 +673,6 @@ struct RaggedClass { int64_t first, count; int32_t threads, lds_bytes; };
 constexpr int32_t RAGGED_CU_THREADS = 2048;  // 32 waves per CU
 constexpr int32_t RAGGED_MAX_CLASSES = 8;
 
-inline int32_t ragged_threads(int32_t n) {
-    if (const char* e = std::getenv("FNN_BATCH_THREADS")) { int v = std::atoi(e); if (v == 256 || v == 512 || v == 1024) return v; }
-    return small_block_threads(n);
-}
 // Workgroups of this shape that one CU holds at a time, rounded down to a power of two: the class key next to the block size.
 inline int32_t ragged_resident(int32_t threads, int32_t lds_bytes) {
     int32_t r = SMALL_LDS_CAP / lds_bytes;
@@ -653,14 +685,15 @@ inline int32_t ragged_resident(int32_t threads, int32_t lds_bytes) {
 // Sorts a chunk's descriptors by descending n (ties: the caller's index) and cuts them into classes wherever the block
 // size or the residency step changes.  Both are monotone in n, so a class is a range of n: it never straddles 64|65 or
 // 96|97, and a problem is never launched under a reservation that halves the workgroups per CU its own size allows.  A
-// class reserves the LDS of its largest member.  lds_of(desc) = the problem's own dynamic LDS in bytes.
+// class reserves the LDS of its largest member.  lds_of(desc) = the problem's own dynamic LDS in bytes; threads_switch =
+// what batch_threads_switch() gave the call.
 template <class LdsOf>
-inline void ragged_classes(std::vector<RaggedDesc>& d, LdsOf lds_of, std::vector<RaggedClass>& out) {
+inline void ragged_classes(std::vector<RaggedDesc>& d, int32_t threads_switch, LdsOf lds_of, std::vector<RaggedClass>& out) {
     std::sort(d.begin(), d.end(), [](const RaggedDesc& a, const RaggedDesc& b) { return a.n != b.n ? a.n > b.n : a.id < b.id; });
     out.clear();
     int32_t key_t = 0, key_r = 0;
     for (size_t k = 0; k < d.size(); k++) {
-        const int32_t t = ragged_threads(d[k].n), bytes = lds_of(d[k]), r = ragged_resident(t, bytes);
+        const int32_t t = threads_switch ? threads_switch : small_block_threads(d[k].n), bytes = lds_of(d[k]), r = ragged_resident(t, bytes);
         if (out.empty() || t != key_t || r != key_r) {
             out.push_back(RaggedClass{(int64_t)k, 0, t, bytes});
             key_t = t; key_r = r;
@@ -675,7 +708,7 @@ inline void ragged_classes(std::vector<RaggedDesc>& d, LdsOf lds_of, std::vector
 template <class BytesOf>
 inline std::vector<int64_t> ragged_chunks(const std::vector<int64_t>& items, BytesOf bytes_of) {
     int64_t max_count = INT64_MAX;
-    if (const char* e = std::getenv("FNN_BATCH_CHUNK")) { long long v = std::atoll(e); if (v >= 1) max_count = v; }
+    if (const int64_t v = batch_chunk_switch()) max_count = v;
     std::vector<int64_t> cut{0};
     int64_t bytes = 0, count = 0;
     for (size_t k = 0; k < items.size(); k++) {
@@ -725,12 +758,10 @@ int32_t small_ragged(B& be, const char* who, const double* D, bool on_device, co
         else if (n > 3) kern.push_back(b);
     }
     st.n_problems = batch;
-    std::vector<int32_t> orders((size_t)oo[(size_t)batch]);
-    std::vector<fnn_event> evs(events_out ? (size_t)eo[(size_t)batch] : 0);  // (zero: the fill behind each problem's last event)
-    std::vector<int32_t> nev((size_t)batch, 0);
+    OrderStage out(batch, (size_t)oo[(size_t)batch], events_out ? (size_t)eo[(size_t)batch] : 0);
     for (int64_t b = 0; b < batch; b++)
         if (ns[b] <= 3)  // NetMakerOriginal.java:133-140: the identity, no device needed
-            for (int32_t i = 0; i <= ns[b]; i++) orders[(size_t)(oo[(size_t)b] + i)] = i;
+            for (int32_t i = 0; i <= ns[b]; i++) out.orders[(size_t)(oo[(size_t)b] + i)] = i;
     int64_t bad = -1;  // the lowest caller's index that fails the check
     int32_t rc;
     if (!kern.empty() || !large.empty()) {
@@ -758,6 +789,7 @@ int32_t small_ragged(B& be, const char* who, const double* D, bool on_device, co
         std::vector<fnn_event> cev(events_out ? (size_t)mrec : 0);
         std::vector<RaggedDesc> slot, sorted;  // the chunk's descriptors in the caller's order / in launch order
         std::vector<RaggedClass> classes;
+        const int32_t threads_switch = batch_threads_switch();
         for (size_t c = 0; c + 1 < cut.size() && bad < 0; c++) {
             const int64_t cnt = cut[c + 1] - cut[c];
             slot.clear();
@@ -773,8 +805,7 @@ int32_t small_ragged(B& be, const char* who, const double* D, bool on_device, co
                     d.src = offsets[b]; d.ld = ld_of(b);
                     d.vec = (d.ld == n && reinterpret_cast<uintptr_t>(D + offsets[b]) % 16 == 0) ? 1 : 0;
                 } else {          // rows to the dense image (padding is never read)
-                    for (int32_t r = 0; r < n; r++)
-                        std::memcpy(&pack[(size_t)(img + (int64_t)r * n)], D + offsets[b] + (int64_t)r * ld_of(b), sizeof(double) * (size_t)n);
+                    pack_rows(&pack[(size_t)img], n, D + offsets[b], ld_of(b), n);
                     d.src = img; d.ld = n; d.vec = 1;
                     img += pitch_of(b);
                 }
@@ -782,7 +813,7 @@ int32_t small_ragged(B& be, const char* who, const double* D, bool on_device, co
                 slot.push_back(d);
             }
             sorted = slot;
-            ragged_classes(sorted, [](const RaggedDesc& d) { return small_layout(d.n).bytes; }, classes);
+            ragged_classes(sorted, threads_switch, [](const RaggedDesc& d) { return small_layout(d.n).bytes; }, classes);
             if ((int64_t)classes.size() > RAGGED_MAX_CLASSES) return fail(FNN_ESTATE, W + "more size classes than launches allowed");
             if ((!on_device && be.h2d(dD, pack.data(), sizeof(double) * (size_t)img) != FNN_OK) ||
                 be.h2d(d_desc, sorted.data(), sizeof(RaggedDesc) * (size_t)cnt) != FNN_OK)
@@ -805,10 +836,10 @@ int32_t small_ragged(B& be, const char* who, const double* D, bool on_device, co
                 return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
             for (const RaggedDesc& d : slot) {
                 const int32_t* mt = &meta[(size_t)d.meta];
-                rc = small_collect_one(W, d.n, d.id, mt, &log[(size_t)d.log], &orders[(size_t)oo[(size_t)d.id]]);
+                rc = small_collect_one(W, d.n, d.id, mt, &log[(size_t)d.log], &out.orders[(size_t)oo[(size_t)d.id]]);
                 if (rc != FNN_OK) return rc;
-                nev[(size_t)d.id] = mt[2];
-                if (events_out) std::memcpy(&evs[(size_t)eo[(size_t)d.id]], &cev[(size_t)d.ev], sizeof(fnn_event) * (size_t)mt[2]);
+                out.nev[(size_t)d.id] = mt[2];
+                if (events_out) std::memcpy(&out.evs[(size_t)eo[(size_t)d.id]], &cev[(size_t)d.ev], sizeof(fnn_event) * (size_t)mt[2]);
                 st.n_events += mt[2];
             }
             st.n_lds += cnt;
@@ -833,17 +864,15 @@ int32_t small_ragged(B& be, const char* who, const double* D, bool on_device, co
         if (bad >= 0) continue;
         for (int64_t k = 0; k < cnt; k++) {
             const int64_t b = g.second[(size_t)k];
-            std::memcpy(&orders[(size_t)oo[(size_t)b]], &go[(size_t)k * (size_t)(n + 1)], sizeof(int32_t) * (size_t)(n + 1));
-            nev[(size_t)b] = gn[(size_t)k];
-            if (events_out) std::memcpy(&evs[(size_t)eo[(size_t)b]], &ge[(size_t)k * (size_t)n], sizeof(fnn_event) * (size_t)n);
+            std::memcpy(&out.orders[(size_t)oo[(size_t)b]], &go[(size_t)k * (size_t)(n + 1)], sizeof(int32_t) * (size_t)(n + 1));
+            out.nev[(size_t)b] = gn[(size_t)k];
+            if (events_out) std::memcpy(&out.evs[(size_t)eo[(size_t)b]], &ge[(size_t)k * (size_t)n], sizeof(fnn_event) * (size_t)n);
         }
         st.n_global += gs.n_global; st.n_fallback += gs.n_fallback; st.n_lds += gs.n_lds; st.n_events += gs.n_events;
         st.chunks += gs.chunks; st.t_upload_s += gs.t_upload_s; st.t_kernel_s += gs.t_kernel_s;
     }
-    if (bad >= 0) return fail(FNN_EINVAL, W + "problem " + std::to_string(bad) + ": matrix is not symmetric, not finite or has a non-zero diagonal");
-    std::memcpy(orders_out, orders.data(), sizeof(int32_t) * orders.size());
-    if (events_out) std::memcpy(events_out, evs.data(), sizeof(fnn_event) * evs.size());
-    if (nevents_out) std::memcpy(nevents_out, nev.data(), sizeof(int32_t) * nev.size());
+    if (bad >= 0) return fail_bad_matrix(W, bad);
+    out.commit(orders_out, events_out, nevents_out);
     st.t_total_s = now_s() - t0;
     if (stats) *stats = st;
     return FNN_OK;

@@ -358,21 +358,15 @@ int32_t small_global_batch(B& be, const char* who, const double* D, bool on_devi
     if (!orders_out || !D) return fail(FNN_EINVAL, W + "NULL argument");
     if (ld < n || stride < (int64_t)n * ld) return fail(FNN_EINVAL, W + "needs ld >= n and stride >= n * ld");
     st.n_problems = batch;
-    std::vector<int32_t> orders((size_t)batch * (size_t)(n + 1));
-    std::vector<fnn_event> evs(events_out ? (size_t)batch * (size_t)n : 0);
-    std::vector<int32_t> nev((size_t)batch, 0);
+    OrderStage out(batch, (size_t)batch * (size_t)(n + 1), events_out ? (size_t)batch * (size_t)n : 0);
     int32_t rc = be.open(opts.device);
     if (rc != FNN_OK) return fail(rc, W + be.err());
     const GlobalLayout L = small_global_layout(n);
     st.block_threads = small_global_block_threads(n);
-    if (const char* e = std::getenv("FNN_BATCH_THREADS")) { int v = std::atoi(e); if (v == 256 || v == 512 || v == 1024) st.block_threads = v; }
+    if (const int32_t v = batch_threads_switch()) st.block_threads = v;
     st.lds_bytes = L.bytes;
     const int64_t pitch = small_global_pitch(n);
-    int64_t chunk = SMALL_CHUNK_BYTES / (8 * pitch);
-    if (const char* e = std::getenv("FNN_BATCH_CHUNK")) { long long v = std::atoll(e); if (v >= 1) chunk = v; }
-    if (chunk > batch) chunk = batch;
-    if (chunk < 1) chunk = 1;
-    chunk = (batch + (batch + chunk - 1) / chunk - 1) / ((batch + chunk - 1) / chunk);  // as many chunks, of equal size: no short last launch
+    const int64_t chunk = batch_chunk(batch, 8 * pitch, true);
     int32_t* d_meta = (int32_t*)be.alloc(sizeof(int32_t) * SMALL_META_INTS * (size_t)chunk);
     Agg3Rec* d_log = (Agg3Rec*)be.alloc(sizeof(Agg3Rec) * (size_t)n * (size_t)chunk);
     Event* d_ev = events_out ? (Event*)be.alloc(sizeof(Event) * (size_t)n * (size_t)chunk) : nullptr;
@@ -389,9 +383,7 @@ int32_t small_global_batch(B& be, const char* who, const double* D, bool on_devi
         int64_t kld = ld, kstride = stride;
         if (!on_device) {
             const double tu = now_s();
-            for (int64_t b = 0; b < cnt; b++)
-                for (int32_t r = 0; r < n; r++)
-                    std::memcpy(&pack[(size_t)(b * pitch + (int64_t)r * L.ldw)], src + b * stride + (int64_t)r * ld, sizeof(double) * (size_t)n);
+            for (int64_t b = 0; b < cnt; b++) pack_rows(&pack[(size_t)(b * pitch)], L.ldw, src + b * stride, ld, n);
             if (be.h2d(d_work, pack.get(), sizeof(double) * (size_t)(cnt * pitch)) != FNN_OK) return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
             st.t_upload_s += now_s() - tu;
             src = d_work; kld = L.ldw; kstride = pitch;
@@ -399,8 +391,7 @@ int32_t small_global_batch(B& be, const char* who, const double* D, bool on_devi
         if (opts.validate) {
             int64_t bad = -1;
             if (be.validate(src, n, kld, kstride, cnt, &bad) != FNN_OK) return fail(FNN_EHIP, W + "validate failed (" + be.err() + ")");
-            if (bad >= 0)
-                return fail(FNN_EINVAL, W + "problem " + std::to_string(b0 + bad) + ": matrix is not symmetric, not finite or has a non-zero diagonal");
+            if (bad >= 0) return fail_bad_matrix(W, b0 + bad);
         }
         double tk = 0.0;
         if (be.run_global(src, kld, kstride, d_work, cnt, n, st.block_threads, L.bytes, d_meta, d_log, d_ev, &tk) != FNN_OK)
@@ -408,15 +399,13 @@ int32_t small_global_batch(B& be, const char* who, const double* D, bool on_devi
         st.t_kernel_s += tk;
         if (be.d2h(meta.data(), d_meta, sizeof(int32_t) * SMALL_META_INTS * (size_t)cnt) != FNN_OK ||
             be.d2h(log.data(), d_log, sizeof(Agg3Rec) * (size_t)n * (size_t)cnt) != FNN_OK ||
-            (d_ev && be.d2h(&evs[(size_t)b0 * (size_t)n], d_ev, sizeof(Event) * (size_t)n * (size_t)cnt) != FNN_OK))
+            (d_ev && be.d2h(&out.evs[(size_t)b0 * (size_t)n], d_ev, sizeof(Event) * (size_t)n * (size_t)cnt) != FNN_OK))
             return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
-        rc = small_collect(W, n, b0, cnt, meta.data(), log.data(), orders.data(), nev.data(), events_out ? evs.data() : nullptr, st);
+        rc = small_collect(W, n, b0, cnt, meta.data(), log.data(), out.orders.data(), out.nev.data(), events_out ? out.evs.data() : nullptr, st);
         if (rc != FNN_OK) return rc;
         st.n_global += cnt;
     }
-    std::memcpy(orders_out, orders.data(), sizeof(int32_t) * orders.size());
-    if (events_out) std::memcpy(events_out, evs.data(), sizeof(fnn_event) * evs.size());
-    if (nevents_out) std::memcpy(nevents_out, nev.data(), sizeof(int32_t) * nev.size());
+    out.commit(orders_out, events_out, nevents_out);
     st.t_total_s = now_s() - t0;
     if (stats) *stats = st;
     return FNN_OK;

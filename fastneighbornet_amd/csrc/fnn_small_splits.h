@@ -663,6 +663,68 @@ inline fnn_sw_stats small_splits_stats(const SplitsMeta& m, const double* w, int
     return s;
 }
 
+// ---- steps that the same-size and the ragged call share, one definition each (those of every batch call: fnn_small.h)
+// o[1] ... o[n] is a permutation of 1..n (`seen`: scratch)
+inline bool splits_ordering_ok(const int32_t* o, int32_t n, std::vector<char>& seen) {
+    seen.assign((size_t)n + 1, 0);
+    for (int32_t i = 1; i <= n; i++) {
+        if (o[i] < 1 || o[i] > n || seen[(size_t)o[i]]) return false;
+        seen[(size_t)o[i]] = 1;
+    }
+    return true;
+}
+
+// The outputs of a weight call.  The call fills these and commits as its last step: a failing call returns before that
+// and leaves the caller's arrays untouched.
+struct WeightStage {
+    std::vector<double> wts;
+    std::vector<fnn_sw_stats> sws;
+    WeightStage(int64_t batch, size_t weights) : wts(weights), sws((size_t)batch) {}
+    void commit(double* weights_out, fnn_sw_stats* stats_out) const {
+        std::memcpy(weights_out, wts.data(), sizeof(double) * wts.size());
+        if (stats_out) std::memcpy(stats_out, sws.data(), sizeof(fnn_sw_stats) * sws.size());
+    }
+};
+
+// One problem's result from the kernel (m: its record, w: its N weights, cap: the capacity it ran with).  Taken: the
+// weights are in wts, the per-problem record in sw, and the problem is counted under its route.
+enum SplitsTaken { SPLITS_NONFINITE, SPLITS_TO_SINGLE, SPLITS_TAKEN };
+inline SplitsTaken small_splits_take(const SplitsMeta& m, const double* w, int64_t N, int32_t cap, double* wts, fnn_sw_stats& sw, fnn_sw_batch_stats& st) {
+    if (m.nonfinite) return SPLITS_NONFINITE;
+    if (m.giveup || !m.certified) return SPLITS_TO_SINGLE;
+    std::memcpy(wts, w, sizeof(double) * (size_t)N);
+    sw = small_splits_stats(m, w, N, cap);
+    if (m.route == FNN_SW_ROUTE_FROM_BELOW) st.n_kernel++; else st.n_closed_form++;
+    return SPLITS_TAKEN;
+}
+
+// What the kernel did not take or gave up on goes one by one through the one-problem solver, on a dense host copy.
+struct SplitsSingle {
+    std::vector<double> one, span;
+    bool inexact = false;  // FNN_EINEXACT from a problem does not end the call: result() reports it after the commit
+    // problem b: the n x n matrix at src with row stride ld (on_device: in device memory), to w and sw
+    template <class B>
+    int32_t run(B& be, const std::string& W, int64_t b, const double* src, bool on_device, int32_t n, int64_t ld, const int32_t* ordering,
+                int32_t device, double* w, fnn_sw_stats* sw, fnn_sw_batch_stats& st) {
+        if (on_device) {
+            span.resize((size_t)((int64_t)(n - 1) * ld + n));
+            if (be.d2h(span.data(), src, sizeof(double) * span.size()) != FNN_OK) return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
+            src = span.data();
+        }
+        one.resize((size_t)n * (size_t)n);
+        pack_rows(one.data(), n, src, ld, n);
+        int32_t rc = be.single(one.data(), n, ordering, device, w, sw);
+        if (rc == FNN_EINEXACT) { inexact = true; rc = FNN_OK; }
+        if (rc != FNN_OK) { g_last_error = W + "problem " + std::to_string(b) + ": " + g_last_error; return rc; }
+        st.n_fallback++;
+        return FNN_OK;
+    }
+    int32_t result(const std::string& W) const {
+        if (inexact) return fail(FNN_EINEXACT, W + "at least one problem of the one-problem solver returned weights that fail its Kuhn-Tucker check (stats_out[b].certified)");
+        return FNN_OK;
+    }
+};
+
 // fnn_split_weights_batch[_device]_f64 over a backend B (HIP: fnn_splits_batch.hip; CPU driver:
 // tests/emu/fnn_splits_batch_emu.cpp): open / alloc / h2d / d2h / err as small_batch's, and
 //   run_splits(dD, n, ld, stride, d_ord, cnt, cap, threads, lds_bytes, d_work, pitch, d_out, d_meta, &t_kernel_s)
@@ -681,20 +743,14 @@ int32_t small_splits_batch(B& be, const char* who, const double* D, bool on_devi
     if (!D || !orderings || !weights_out) return fail(FNN_EINVAL, W + "NULL argument");
     if (ld < n || stride < (int64_t)n * ld) return fail(FNN_EINVAL, W + "needs ld >= n and stride >= n * ld");
     {
-        std::vector<char> seen((size_t)n + 1);
-        for (int64_t b = 0; b < batch; b++) {
-            std::fill(seen.begin(), seen.end(), 0);
-            const int32_t* o = orderings + b * (n + 1);
-            for (int32_t i = 1; i <= n; i++) {
-                if (o[i] < 1 || o[i] > n || seen[(size_t)o[i]]) return fail(FNN_EINVAL, W + "problem " + std::to_string(b) + ": ordering is not a permutation of 1..n");
-                seen[(size_t)o[i]] = 1;
-            }
-        }
+        std::vector<char> seen;
+        for (int64_t b = 0; b < batch; b++)
+            if (!splits_ordering_ok(orderings + b * (n + 1), n, seen))
+                return fail(FNN_EINVAL, W + "problem " + std::to_string(b) + ": ordering is not a permutation of 1..n");
     }
     st.n_problems = batch;
     const int64_t N = (int64_t)n * (n - 1) / 2;
-    std::vector<double> wts((size_t)batch * (size_t)N);
-    std::vector<fnn_sw_stats> sws((size_t)batch);
+    WeightStage res(batch, (size_t)batch * (size_t)N);
     std::vector<int64_t> todo;  // problems for the one-problem solver
     int32_t rc = be.open(device);
     if (rc != FNN_OK) return fail(rc, W + be.err());
@@ -708,12 +764,8 @@ int32_t small_splits_batch(B& be, const char* who, const double* D, bool on_devi
         st.capacity = cap;
         st.lds_bytes = L.bytes;
         st.block_threads = small_block_threads(n);
-        if (const char* e = std::getenv("FNN_BATCH_THREADS")) { int v = std::atoi(e); if (v == 256 || v == 512 || v == 1024) st.block_threads = v; }
-        int64_t chunk = SMALL_CHUNK_BYTES / (8 * pitch);
-        if (const char* e = std::getenv("FNN_BATCH_CHUNK")) { long long v = std::atoll(e); if (v >= 1) chunk = v; }
-        if (chunk > batch) chunk = batch;
-        if (chunk < 1) chunk = 1;
-        chunk = (batch + (batch + chunk - 1) / chunk - 1) / ((batch + chunk - 1) / chunk);  // as many chunks, of equal size
+        if (const int32_t v = batch_threads_switch()) st.block_threads = v;
+        const int64_t chunk = batch_chunk(batch, 8 * pitch, true);
         st.workspace_bytes = 8 * pitch * chunk;
         double* d_work = (double*)be.alloc(sizeof(double) * (size_t)pitch * (size_t)chunk);
         double* d_out = (double*)be.alloc(sizeof(double) * (size_t)N * (size_t)chunk);
@@ -731,9 +783,7 @@ int32_t small_splits_batch(B& be, const char* who, const double* D, bool on_devi
             const double* src = D + b0 * stride;
             int64_t kld = ld, kstride = stride;
             if (!on_device) {
-                for (int64_t b = 0; b < cnt; b++)
-                    for (int32_t r = 0; r < n; r++)
-                        std::memcpy(&pack[(size_t)((b * n + r) * n)], src + b * stride + (int64_t)r * ld, sizeof(double) * (size_t)n);
+                for (int64_t b = 0; b < cnt; b++) pack_rows(&pack[(size_t)(b * n * n)], n, src + b * stride, ld, n);
                 if (be.h2d(d_D, pack.get(), sizeof(double) * (size_t)(cnt * n * n)) != FNN_OK) return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
                 src = d_D; kld = n; kstride = (int64_t)n * n;
             }
@@ -748,38 +798,22 @@ int32_t small_splits_batch(B& be, const char* who, const double* D, bool on_devi
                 be.d2h(outs.data(), d_out, sizeof(double) * (size_t)(cnt * N)) != FNN_OK)
                 return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
             for (int64_t b = 0; b < cnt; b++) {
-                const SplitsMeta& m = meta[(size_t)b];
-                if (m.nonfinite) return fail(FNN_EINVAL, W + "problem " + std::to_string(b0 + b) + ": the distances contain a NaN or an infinity");
-                if (m.giveup || !m.certified) { todo.push_back(b0 + b); continue; }
-                const double* w = &outs[(size_t)(b * N)];
-                std::memcpy(&wts[(size_t)((b0 + b) * N)], w, sizeof(double) * (size_t)N);
-                sws[(size_t)(b0 + b)] = small_splits_stats(m, w, N, cap);
-                if (m.route == FNN_SW_ROUTE_FROM_BELOW) st.n_kernel++; else st.n_closed_form++;
+                const SplitsTaken t = small_splits_take(meta[(size_t)b], &outs[(size_t)(b * N)], N, cap, &res.wts[(size_t)((b0 + b) * N)],
+                                                        res.sws[(size_t)(b0 + b)], st);
+                if (t == SPLITS_NONFINITE) return fail_nonfinite(W, b0 + b);
+                if (t == SPLITS_TO_SINGLE) todo.push_back(b0 + b);
             }
         }
     }
-    // what the kernel did not take or gave up on: one by one through the one-problem solver, on a dense host copy
-    bool inexact = false;
-    std::vector<double> one(todo.empty() ? 0 : (size_t)n * (size_t)n), span;
+    SplitsSingle single;
     for (int64_t b : todo) {
-        const double* src = D + b * stride;
-        if (on_device) {
-            span.resize((size_t)((int64_t)(n - 1) * ld + n));
-            if (be.d2h(span.data(), src, sizeof(double) * span.size()) != FNN_OK) return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
-            src = span.data();
-        }
-        for (int32_t r = 0; r < n; r++) std::memcpy(&one[(size_t)r * (size_t)n], src + (int64_t)r * ld, sizeof(double) * (size_t)n);
-        rc = be.single(one.data(), n, orderings + b * (n + 1), device, &wts[(size_t)(b * N)], &sws[(size_t)b]);
-        if (rc == FNN_EINEXACT) { inexact = true; rc = FNN_OK; }
-        if (rc != FNN_OK) { g_last_error = W + "problem " + std::to_string(b) + ": " + g_last_error; return rc; }
-        st.n_fallback++;
+        rc = single.run(be, W, b, D + b * stride, on_device, n, ld, orderings + b * (n + 1), device, &res.wts[(size_t)(b * N)], &res.sws[(size_t)b], st);
+        if (rc != FNN_OK) return rc;
     }
-    std::memcpy(weights_out, wts.data(), sizeof(double) * wts.size());
-    if (stats_out) std::memcpy(stats_out, sws.data(), sizeof(fnn_sw_stats) * sws.size());
+    res.commit(weights_out, stats_out);
     st.t_total_s = now_s() - t0;
     if (stats) *stats = st;
-    if (inexact) return fail(FNN_EINEXACT, W + "at least one problem of the one-problem solver returned weights that fail its Kuhn-Tucker check (stats_out[b].certified)");
-    return FNN_OK;
+    return single.result(W);
 }
 
 // ------------------------------------------------------------------------------------------------ ragged batches
@@ -812,12 +846,7 @@ int32_t small_splits_ragged(B& be, const char* who, const double* D, bool on_dev
             const std::string P = W + "problem " + std::to_string(b) + ": ";
             if (n < 2) return fail(FNN_EINVAL, P + "needs n >= 2");
             if (ld_of(b) < n) return fail(FNN_EINVAL, P + "needs ld >= n");
-            seen.assign((size_t)n + 1, 0);
-            const int32_t* o = orderings + oo[(size_t)b];
-            for (int32_t i = 1; i <= n; i++) {
-                if (o[i] < 1 || o[i] > n || seen[(size_t)o[i]]) return fail(FNN_EINVAL, P + "ordering is not a permutation of 1..n");
-                seen[(size_t)o[i]] = 1;
-            }
+            if (!splits_ordering_ok(orderings + oo[(size_t)b], n, seen)) return fail(FNN_EINVAL, P + "ordering is not a permutation of 1..n");
             oo[(size_t)b + 1] = oo[(size_t)b] + n + 1;
             wo[(size_t)b + 1] = wo[(size_t)b] + (int64_t)n * (n - 1) / 2;
             if (n <= SPLITS_MAX_N) { kern.push_back(b); kmax = std::max(kmax, n); }
@@ -825,8 +854,7 @@ int32_t small_splits_ragged(B& be, const char* who, const double* D, bool on_dev
         }
     }
     st.n_problems = batch;
-    std::vector<double> wts((size_t)wo[(size_t)batch]);
-    std::vector<fnn_sw_stats> sws((size_t)batch);
+    WeightStage res(batch, (size_t)wo[(size_t)batch]);
     int32_t rc = be.open(device);
     if (rc != FNN_OK) return fail(rc, W + be.err());
     int64_t bad = -1;  // the lowest caller's index whose distances the kernel found non-finite
@@ -861,6 +889,7 @@ int32_t small_splits_ragged(B& be, const char* who, const double* D, bool on_dev
         std::vector<double> outs((size_t)mout);
         std::vector<RaggedDesc> slot, sorted;  // the chunk's descriptors in the caller's order / in launch order
         std::vector<RaggedClass> classes;
+        const int32_t threads_switch = batch_threads_switch();
         for (size_t c = 0; c + 1 < cut.size() && bad < 0; c++) {
             const int64_t cnt = cut[c + 1] - cut[c];
             slot.clear();
@@ -876,8 +905,7 @@ int32_t small_splits_ragged(B& be, const char* who, const double* D, bool on_dev
                 if (on_device) {
                     d.src = offsets[b]; d.ld = ld_of(b);
                 } else {
-                    for (int32_t r = 0; r < n; r++)
-                        std::memcpy(&pack[(size_t)(img + (int64_t)r * n)], D + offsets[b] + (int64_t)r * ld_of(b), sizeof(double) * (size_t)n);
+                    pack_rows(&pack[(size_t)img], n, D + offsets[b], ld_of(b), n);
                     d.src = img; d.ld = n;
                     img += img_of(b);
                 }
@@ -885,7 +913,7 @@ int32_t small_splits_ragged(B& be, const char* who, const double* D, bool on_dev
                 slot.push_back(d);
             }
             sorted = slot;
-            ragged_classes(sorted, [](const RaggedDesc& d) { return small_splits_layout(d.n, d.cap).bytes; }, classes);
+            ragged_classes(sorted, threads_switch, [](const RaggedDesc& d) { return small_splits_layout(d.n, d.cap).bytes; }, classes);
             if ((int64_t)classes.size() > RAGGED_MAX_CLASSES) return fail(FNN_ESTATE, W + "more size classes than launches allowed");
             if ((!on_device && be.h2d(d_D, pack.get(), sizeof(double) * (size_t)img) != FNN_OK) ||
                 be.h2d(d_ord, ords.data(), sizeof(int32_t) * (size_t)ord) != FNN_OK ||
@@ -904,46 +932,28 @@ int32_t small_splits_ragged(B& be, const char* who, const double* D, bool on_dev
                 be.d2h(outs.data(), d_out, sizeof(double) * (size_t)out) != FNN_OK)
                 return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
             for (const RaggedDesc& d : slot) {
-                const SplitsMeta& m = meta[(size_t)d.meta];
-                if (m.nonfinite) { bad = d.id; break; }
-                if (m.giveup || !m.certified) { todo.push_back(d.id); continue; }
-                const int64_t N = wo[(size_t)d.id + 1] - wo[(size_t)d.id];
-                const double* w = &outs[(size_t)d.out];
-                std::memcpy(&wts[(size_t)wo[(size_t)d.id]], w, sizeof(double) * (size_t)N);
-                sws[(size_t)d.id] = small_splits_stats(m, w, N, d.cap);
-                if (m.route == FNN_SW_ROUTE_FROM_BELOW) st.n_kernel++; else st.n_closed_form++;
+                const SplitsTaken t = small_splits_take(meta[(size_t)d.meta], &outs[(size_t)d.out], wo[(size_t)d.id + 1] - wo[(size_t)d.id], d.cap,
+                                                        &res.wts[(size_t)wo[(size_t)d.id]], res.sws[(size_t)d.id], st);
+                if (t == SPLITS_NONFINITE) { bad = d.id; break; }
+                if (t == SPLITS_TO_SINGLE) todo.push_back(d.id);
             }
         }
     }
     // what the kernel did not take or gave up on: one by one through the one-problem solver, on a dense host copy, in the
     // caller's order (after a non-finite problem only those in front of it: fnn_last_error() names the lowest failure)
     std::sort(todo.begin(), todo.end());
-    bool inexact = false;
-    std::vector<double> one, span;
+    SplitsSingle single;
     for (int64_t b : todo) {
         if (bad >= 0 && b > bad) break;
-        const int32_t n = ns[b];
-        const int64_t ld = ld_of(b);
-        const double* src = D + offsets[b];
-        if (on_device) {
-            span.resize((size_t)((int64_t)(n - 1) * ld + n));
-            if (be.d2h(span.data(), src, sizeof(double) * span.size()) != FNN_OK) return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
-            src = span.data();
-        }
-        one.resize((size_t)n * (size_t)n);
-        for (int32_t r = 0; r < n; r++) std::memcpy(&one[(size_t)r * (size_t)n], src + (int64_t)r * ld, sizeof(double) * (size_t)n);
-        rc = be.single(one.data(), n, orderings + oo[(size_t)b], device, &wts[(size_t)wo[(size_t)b]], &sws[(size_t)b]);
-        if (rc == FNN_EINEXACT) { inexact = true; rc = FNN_OK; }
-        if (rc != FNN_OK) { g_last_error = W + "problem " + std::to_string(b) + ": " + g_last_error; return rc; }
-        st.n_fallback++;
+        rc = single.run(be, W, b, D + offsets[b], on_device, ns[b], ld_of(b), orderings + oo[(size_t)b], device, &res.wts[(size_t)wo[(size_t)b]],
+                        &res.sws[(size_t)b], st);
+        if (rc != FNN_OK) return rc;
     }
-    if (bad >= 0) return fail(FNN_EINVAL, W + "problem " + std::to_string(bad) + ": the distances contain a NaN or an infinity");
-    std::memcpy(weights_out, wts.data(), sizeof(double) * wts.size());
-    if (stats_out) std::memcpy(stats_out, sws.data(), sizeof(fnn_sw_stats) * sws.size());
+    if (bad >= 0) return fail_nonfinite(W, bad);
+    res.commit(weights_out, stats_out);
     st.t_total_s = now_s() - t0;
     if (stats) *stats = st;
-    if (inexact) return fail(FNN_EINEXACT, W + "at least one problem of the one-problem solver returned weights that fail its Kuhn-Tucker check (stats_out[b].certified)");
-    return FNN_OK;
+    return single.result(W);
 }
 
 }  // namespace fnn

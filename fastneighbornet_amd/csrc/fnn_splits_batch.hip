@@ -86,65 +86,16 @@ __global__ __launch_bounds__(1024) void k_small_splits_ragged(const double* __re
     small_splits_problem(ex, V, sw, D + d.src, d.ld, ord + d.ord, out + d.out, meta + d.meta);
 }
 
-struct SplitsHipBackend {
-    std::vector<void*> bufs;
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    std::string last;
+struct SplitsHipBackend : HipBatchBase {
     RaggedLauncher ragged{RAGGED_SPLITS_STREAMS};
-    int prev_device = -1;  // the caller's current device, restored when the call ends
 
-    ~SplitsHipBackend() {
-        for (void* p : bufs) (void)hipFree(p);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (prev_device >= 0) (void)hipSetDevice(prev_device);
-    }
-    const std::string& err() const { return last; }
-    bool ok(hipError_t e, const char* what) {
-        if (e == hipSuccess) return true;
-        last = std::string(what) + ": " + hipGetErrorString(e);
-        return false;
-    }
-    int32_t open(int32_t device) {
-        int cnt = 0;
-        if (!ok(hipGetDeviceCount(&cnt), "hipGetDeviceCount")) return FNN_EHIP;
-        if (device < 0 || device >= cnt) { last = "no HIP device " + std::to_string(device) + " (there is no CPU fallback)"; return FNN_EHIP; }
-        int cur = -1;
-        if (hipGetDevice(&cur) == hipSuccess) prev_device = cur;  // (the one-problem solver sets the device too)
-        if (!ok(hipSetDevice(device), "hipSetDevice") || !ok(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "hipStreamCreate") ||
-            !ok(hipEventCreate(&e0), "hipEventCreate") || !ok(hipEventCreate(&e1), "hipEventCreate"))
-            return FNN_EHIP;
-        return FNN_OK;
-    }
-    void* alloc(size_t bytes) {
-        void* p = nullptr;
-        if (!ok(hipMalloc(&p, bytes ? bytes : 1), "hipMalloc")) return nullptr;
-        bufs.push_back(p);
-        return p;
-    }
-    int32_t h2d(void* dst, const void* src, size_t bytes) {
-        return ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream), "hipMemcpy") && ok(hipStreamSynchronize(stream), "upload") ? FNN_OK : FNN_EHIP;
-    }
-    int32_t d2h(void* dst, const void* src, size_t bytes) {
-        return ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream), "hipMemcpy") && ok(hipStreamSynchronize(stream), "download") ? FNN_OK : FNN_EHIP;
-    }
     int32_t run_splits(const double* dD, int32_t n, int64_t ld, int64_t stride, const int32_t* d_ord, int64_t cnt, int32_t cap, int32_t threads,
                        int32_t lds_bytes, double* d_work, int64_t pitch, double* d_out, SplitsMeta* d_meta, double* t_kernel_s) {
-        if (!ok(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_small_splits), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes),
-                "hipFuncSetAttribute"))
-            return FNN_EHIP;
         const SplitsSwitches sw = small_splits_switches();
-        if (!ok(hipEventRecord(e0, stream), "hipEventRecord")) return FNN_EHIP;
-        hipLaunchKernelGGL(k_small_splits, dim3((unsigned)cnt), dim3((unsigned)threads), (size_t)lds_bytes, stream, dD, n, ld, stride, d_ord, cap, sw, d_work,
-                           pitch, d_out, d_meta);
-        if (!ok(hipGetLastError(), "k_small_splits launch")) return FNN_EHIP;
-        if (!ok(hipEventRecord(e1, stream), "hipEventRecord") || !ok(hipEventSynchronize(e1), "k_small_splits")) return FNN_EHIP;
-        float ms = 0.f;
-        if (!ok(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime")) return FNN_EHIP;
-        *t_kernel_s = (double)ms * 1e-3;
-        return FNN_OK;
+        return timed_launch(reinterpret_cast<const void*>(&k_small_splits), "k_small_splits", lds_bytes, [&] {
+            hipLaunchKernelGGL(k_small_splits, dim3((unsigned)cnt), dim3((unsigned)threads), (size_t)lds_bytes, stream, dD, n, ld, stride, d_ord, cap, sw,
+                               d_work, pitch, d_out, d_meta);
+        }, t_kernel_s);
     }
     int32_t run_splits_ragged(const double* base, const RaggedDesc* d_desc, const RaggedClass* cls, int32_t ncls, const int32_t* d_ord, double* d_work,
                               double* d_out, SplitsMeta* d_meta, double* t_kernel_s) {
@@ -168,15 +119,6 @@ struct SplitsHipBackend {
 
 }  // namespace fnn
 
-#define FNN_SPLITS_BATCH_TRY(body)                                            \
-    try {                                                                     \
-        body                                                                  \
-    } catch (const std::bad_alloc&) {                                         \
-        return fnn::fail(FNN_ENOMEM, "out of host memory");                   \
-    } catch (const std::exception& e) {                                       \
-        return fnn::fail(FNN_ESTATE, std::string("exception: ") + e.what()); \
-    }
-
 extern "C" {
 
 int32_t fnn_split_weights_batch_max_n(void) { return fnn::SPLITS_MAX_N; }
@@ -184,7 +126,7 @@ int64_t fnn_split_weights_batch_min_batch(int32_t n) { return fnn::small_splits_
 
 int32_t fnn_split_weights_batch_f64(const double* D, int32_t n, int64_t ld, int64_t stride, int64_t batch, const int32_t* orderings, int32_t device,
                                     double* weights_out, fnn_sw_stats* stats_out, fnn_sw_batch_stats* stats) {
-    FNN_SPLITS_BATCH_TRY(
+    FNN_BATCH_TRY(
         fnn::SplitsHipBackend be;
         return fnn::small_splits_batch(be, "fnn_split_weights_batch_f64", D, false, n, ld, stride, batch, orderings, device, weights_out, stats_out, stats);
     )
@@ -192,7 +134,7 @@ int32_t fnn_split_weights_batch_f64(const double* D, int32_t n, int64_t ld, int6
 
 int32_t fnn_split_weights_batch_device_f64(const double* d_D, int32_t n, int64_t ld, int64_t stride, int64_t batch, const int32_t* orderings,
                                            int32_t device, double* weights_out, fnn_sw_stats* stats_out, fnn_sw_batch_stats* stats) {
-    FNN_SPLITS_BATCH_TRY(
+    FNN_BATCH_TRY(
         fnn::SplitsHipBackend be;
         return fnn::small_splits_batch(be, "fnn_split_weights_batch_device_f64", d_D, true, n, ld, stride, batch, orderings, device, weights_out, stats_out, stats);
     )
@@ -200,7 +142,7 @@ int32_t fnn_split_weights_batch_device_f64(const double* d_D, int32_t n, int64_t
 
 int32_t fnn_split_weights_ragged_f64(const double* D, const int64_t* offsets, const int32_t* n, const int64_t* ld, int64_t batch, const int32_t* orderings,
                                      int32_t device, double* weights_out, fnn_sw_stats* stats_out, fnn_sw_batch_stats* stats) {
-    FNN_SPLITS_BATCH_TRY(
+    FNN_BATCH_TRY(
         fnn::SplitsHipBackend be;
         return fnn::small_splits_ragged(be, "fnn_split_weights_ragged_f64", D, false, offsets, n, ld, batch, orderings, device, weights_out, stats_out, stats);
     )
@@ -209,7 +151,7 @@ int32_t fnn_split_weights_ragged_f64(const double* D, const int64_t* offsets, co
 int32_t fnn_split_weights_ragged_device_f64(const double* d_D, const int64_t* offsets, const int32_t* n, const int64_t* ld, int64_t batch,
                                             const int32_t* orderings, int32_t device, double* weights_out, fnn_sw_stats* stats_out,
                                             fnn_sw_batch_stats* stats) {
-    FNN_SPLITS_BATCH_TRY(
+    FNN_BATCH_TRY(
         fnn::SplitsHipBackend be;
         return fnn::small_splits_ragged(be, "fnn_split_weights_ragged_device_f64", d_D, true, offsets, n, ld, batch, orderings, device, weights_out, stats_out, stats);
     )

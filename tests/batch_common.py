@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 CSRC = os.path.join(ROOT, "fastneighbornet_amd", "csrc")
 EMU_SRCS = [os.path.join(EMU_DIR, "fnn_batch_emu.cpp")] + [os.path.join(CSRC, f) for f in ("fnn_small.h", "fnn_engine.h", "fnn_core.h")] + \
-    [os.path.join(ROOT, "include", "fastnn.h")]
+    [os.path.join(ROOT, "include", "fastnn.h"), os.path.join(EMU_DIR, "fnn_small_emu.h"), os.path.join(CSRC, "fnn_small_splits.h")]
 
 CLASSES = ("uniform53", "dec4", "tree", "treenoise", "dup", "neg", "outgroup")
 SMALL_SIZES = (4, 5, 6, 7, 8, 9, 16, 33, 63, 64, 65, 100, 127, 128)   # ... and lds_max_n
@@ -139,13 +139,17 @@ def check_chunking(a, n, monkeypatch):
     assert_matches_oracle(o2, e2, n2, refs, ("chunked", n))
 
 
-def check_validation(a):
+def check_validation(a, monkeypatch):
     n, B = 16, 5
     good, _ = dec4_batch(n, B, seed0=700)
-    for what in ("asymmetric", "nan", "diagonal"):
+    for what in ("asymmetric", "asymmetric, chunks of 2", "nan", "diagonal"):
+        monkeypatch.delenv("FNN_BATCH_CHUNK", raising=False)
         D = good.copy()
         if what == "asymmetric":
             D[3, 2, 5] += 0.5
+        elif what == "asymmetric, chunks of 2":  # problem 3 is chunk 1, local index 1: the failure names the caller's index
+            D[3, 2, 5] += 0.5
+            monkeypatch.setenv("FNN_BATCH_CHUNK", "2")
         elif what == "nan":
             D[3, 2, 5] = D[3, 5, 2] = np.nan
         else:

@@ -15,7 +15,7 @@ from fastneighbornet_amd import _capi
 
 EMU_SRCS = [os.path.join(bc.EMU_DIR, "fnn_batch_global_emu.cpp")] + \
     [os.path.join(bc.CSRC, f) for f in ("fnn_small_global.h", "fnn_small.h", "fnn_engine.h", "fnn_core.h")] + \
-    [os.path.join(bc.ROOT, "include", "fastnn.h")]
+    [os.path.join(bc.ROOT, "include", "fastnn.h"), os.path.join(bc.EMU_DIR, "fnn_small_emu.h"), os.path.join(bc.CSRC, "fnn_small_splits.h")]
 
 # 4: the special finish with no scan before it; 63, 64, 65 straddle a wave in the staging arrays; 141: the first size of the
 # default route; 257: more positions than a 256-thread block
@@ -140,10 +140,14 @@ def check_validation(a, monkeypatch):
     n, B = 141, 5
     monkeypatch.setenv("FNN_BATCH_ROUTE", "global")
     good, _ = dec4_batch(n, B, seed0=1300)
-    for what in ("asymmetric", "nan", "diagonal"):
+    for what in ("asymmetric", "asymmetric, chunks of 2", "nan", "diagonal"):
+        monkeypatch.delenv("FNN_BATCH_CHUNK", raising=False)
         D = good.copy()
         if what == "asymmetric":
             D[3, 2, 5] += 0.5
+        elif what == "asymmetric, chunks of 2":  # problem 3 is chunk 1, local index 1: the failure names the caller's index
+            D[3, 2, 5] += 0.5
+            monkeypatch.setenv("FNN_BATCH_CHUNK", "2")
         elif what == "nan":
             D[3, 2, 5] = D[3, 5, 2] = np.nan
         else:

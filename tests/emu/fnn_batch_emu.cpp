@@ -3,53 +3,19 @@
 // Runs the per-thread phase bodies of fastneighbornet_amd/csrc/fnn_small.h for tid = 0 ... nthreads-1, phase by phase
 // (a barrier of the kernel is the end of such a loop), under the same host logic as the product (small_batch<B>):
 // argument checks, chunking, validation, expansion.  "Device memory" is the heap, and each problem's LDS image is a heap
-// block of exactly the size the kernel declares, filled with 0xFF bytes first: under AddressSanitizer an index past the
-// layout is an error, and a word read before it is written is a NaN or -1 that the comparison with the oracle notices.
+// block of exactly the size the kernel declares, filled with 0xFF bytes first (fnn_small_emu.h): under AddressSanitizer an
+// index past the layout is an error, and a word read before it is written is a NaN or -1 that the comparison with the
+// oracle notices.
 //
 // Build: g++ -O2 -std=c++17 -fPIC -shared -ffp-contract=off (tests/test_batch_emu.py).  Same signatures as include/fastnn.h
 // with the prefix emu_.
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../fastneighbornet_amd/csrc/fnn_small.h"
+#include "fnn_small_emu.h"
 
 namespace {
 
 using namespace fnn;
 
-struct CpuExec {
-    int nt;
-    template <class F>
-    void all(F f) {
-        for (int t = 0; t < nt; t++) f(t, nt);
-    }
-    void scan(const SmallView& V, int32_t m, int32_t c) {
-        for (int w = 0; w < (nt + 63) / 64; w++) {
-            SmallCand b{0.0, -1, -1};
-            for (int t = w * 64; t < nt && t < (w + 1) * 64; t++) {
-                const SmallCand o = small_scan_thread(t, nt, V, m, c);
-                if (small_before(o, b)) b = o;
-            }
-            V.wred[w] = b;
-        }
-    }
-};
-
-struct EmuBatchBackend {
-    std::vector<void*> bufs;
-    std::string last;
-    ~EmuBatchBackend() { for (void* p : bufs) std::free(p); }
-    const std::string& err() const { return last; }
-    int32_t open(int32_t) { return FNN_OK; }
-    void* alloc(size_t bytes) {
-        void* p = std::malloc(bytes ? bytes : 1);
-        if (p) { std::memset(p, 0xFF, bytes); bufs.push_back(p); }
-        return p;
-    }
-    int32_t h2d(void* dst, const void* src, size_t bytes) { std::memcpy(dst, src, bytes); return FNN_OK; }
-    int32_t d2h(void* dst, const void* src, size_t bytes) { std::memcpy(dst, src, bytes); return FNN_OK; }
+struct EmuBatchBackend : EmuHeapBackend {
     int32_t validate(const double* D, int32_t n, int64_t ld, int64_t stride, int64_t cnt, int64_t* bad) {
         *bad = -1;
         for (int64_t b = cnt; b-- > 0;)  // (any order: the kernel takes the minimum index)
@@ -62,14 +28,12 @@ struct EmuBatchBackend {
         const int32_t vec = (ld == n && stride % 2 == 0 && reinterpret_cast<uintptr_t>(D) % 16 == 0) ? 1 : 0;
         const double t0 = now_s();
         for (int64_t b = 0; b < cnt; b++) {
-            unsigned char* lds = (unsigned char*)std::malloc((size_t)lds_bytes);
-            if (!lds) { last = "out of memory"; return FNN_ENOMEM; }
-            std::memset(lds, 0xFF, (size_t)lds_bytes);
-            const SmallView V = small_view(lds, n);
+            EmuBlock lds((size_t)lds_bytes);
+            if (!lds.p) { last = "out of memory"; return FNN_ENOMEM; }
+            const SmallView V = small_view(lds.bytes(), n);
             for (int t = 0; t < threads; t++) small_load(t, threads, V, D + b * stride, ld, vec);
             CpuExec ex{threads};
             small_problem(ex, V, ev ? ev + b * n : nullptr, meta + b * SMALL_META_INTS, log + b * n);
-            std::free(lds);
         }
         *t_kernel_s = now_s() - t0;
         return FNN_OK;

@@ -12,12 +12,8 @@
 // Build: g++ -O2 -std=c++17 -fPIC -shared -ffp-contract=off (tests/batch_global_common.py).  Same signatures as
 // include/fastnn.h with the prefix emu_.  Calls that the product would not send down this route fail with FNN_EINVAL: the
 // driver has neither the LDS kernel nor the one-problem engine.
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include "../../fastneighbornet_amd/csrc/fnn_small_global.h"
+#include "fnn_small_emu.h"
 
 namespace {
 
@@ -41,19 +37,7 @@ struct CpuGlobalExec {
     }
 };
 
-struct EmuGlobalBackend {
-    std::vector<void*> bufs;
-    std::string last;
-    ~EmuGlobalBackend() { for (void* p : bufs) std::free(p); }
-    const std::string& err() const { return last; }
-    int32_t open(int32_t) { return FNN_OK; }
-    void* alloc(size_t bytes) {
-        void* p = std::malloc(bytes ? bytes : 1);
-        if (p) { std::memset(p, 0xFF, bytes); bufs.push_back(p); }
-        return p;
-    }
-    int32_t h2d(void* dst, const void* src, size_t bytes) { std::memcpy(dst, src, bytes); return FNN_OK; }
-    int32_t d2h(void* dst, const void* src, size_t bytes) { std::memcpy(dst, src, bytes); return FNN_OK; }
+struct EmuGlobalBackend : EmuHeapBackend {
     int32_t validate(const double* D, int32_t n, int64_t ld, int64_t stride, int64_t cnt, int64_t* bad) {
         *bad = -1;
         for (int64_t b = cnt; b-- > 0;)  // (any order: the kernel takes the minimum index)
@@ -66,12 +50,10 @@ struct EmuGlobalBackend {
         const size_t pitch = (size_t)small_global_pitch(n);
         const double t0 = now_s();
         for (int64_t b = 0; b < cnt; b++) {
-            unsigned char* lds = (unsigned char*)std::malloc((size_t)lds_bytes);
-            double* mat = (double*)std::malloc(sizeof(double) * pitch);  // this problem's working copy, on its own
-            if (!lds || !mat) { std::free(lds); std::free(mat); last = "out of memory"; return FNN_ENOMEM; }
-            std::memset(lds, 0xFF, (size_t)lds_bytes);
-            std::memset(mat, 0xFF, sizeof(double) * pitch);
-            const GlobalView V = small_global_view(lds, mat, n);
+            EmuBlock lds((size_t)lds_bytes), copy(sizeof(double) * pitch);  // copy: this problem's working copy, on its own
+            if (!lds.p || !copy.p) { last = "out of memory"; return FNN_ENOMEM; }
+            double* mat = copy.doubles();
+            const GlobalView V = small_global_view(lds.bytes(), mat, n);
             if (src != work) {
                 for (int t = 0; t < threads; t++) global_copy(t, threads, V, src + b * stride, ld);
             } else {  // in place in the upload buffer: the rows (never the padding) are what the kernel finds there
@@ -79,8 +61,6 @@ struct EmuGlobalBackend {
             }
             CpuGlobalExec ex{threads};
             global_problem(ex, V, ev ? ev + b * n : nullptr, meta + b * SMALL_META_INTS, log + b * n);
-            std::free(mat);
-            std::free(lds);
         }
         *t_kernel_s = now_s() - t0;
         return FNN_OK;

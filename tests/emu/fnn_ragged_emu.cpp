@@ -14,12 +14,7 @@
 // with the prefix emu_.  There is no same-size entry, one-problem engine or one-problem solver behind the driver: an order
 // problem above the LDS limit fails the call with FNN_EINVAL, a split problem that the kernel's method gives up on (and any
 // n above its limit) with FNN_ECAPACITY; emu_split_weights_ragged_giveups says which problems of the last call gave up.
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../fastneighbornet_amd/csrc/fnn_small_splits.h"
+#include "fnn_small_emu.h"
 
 namespace {
 
@@ -27,68 +22,7 @@ using namespace fnn;
 
 thread_local std::vector<int32_t> g_giveups;  // FNN_SW_GIVEUP_* per problem (caller's index) of the last call that reached the kernel
 
-struct CpuExec {
-    int nt;
-    template <class F>
-    void all(F f) {
-        for (int t = 0; t < nt; t++) f(t, nt);
-    }
-    void scan(const SmallView& V, int32_t m, int32_t c) {
-        for (int w = 0; w < (nt + 63) / 64; w++) {
-            SmallCand b{0.0, -1, -1};
-            for (int t = w * 64; t < nt && t < (w + 1) * 64; t++) {
-                const SmallCand o = small_scan_thread(t, nt, V, m, c);
-                if (small_before(o, b)) b = o;
-            }
-            V.wred[w] = b;
-        }
-    }
-};
-
-struct CpuSplitsExec {
-    int nt;
-    template <class F>
-    void all(F f) {
-        for (int t = 0; t < nt; t++) f(t, nt);
-    }
-    template <class F>
-    void best(const SplitsView& V, F f) {
-        for (int w = 0; w < (nt + 63) / 64; w++) {
-            SplitsRec b{0.0, -1, -1};
-            for (int t = w * 64; t < nt && t < (w + 1) * 64; t++) {
-                const SplitsRec o = f(t, nt);
-                if (splits_better(o, b)) b = o;
-            }
-            V.wred[w] = b;
-        }
-    }
-    template <class P, class S>
-    void rows(int32_t nrows, P share, S store) {
-        for (int32_t row = 0; row < nrows; row++) {
-            double p[64];
-            for (int l = 0; l < 64; l++) p[l] = share(row, l);
-            for (int off = 32; off > 0; off >>= 1)  // the tree of the kernel's shuffles, as lane 0 sees it
-                for (int l = 0; l < off; l++) p[l] += p[l + off];
-            store(row, p[0]);
-        }
-    }
-    template <class T>
-    T get(const T* p) { return *p; }
-};
-
-struct EmuRaggedBackend {
-    std::vector<void*> bufs;
-    std::string last;
-    ~EmuRaggedBackend() { for (void* p : bufs) std::free(p); }
-    const std::string& err() const { return last; }
-    int32_t open(int32_t) { return FNN_OK; }
-    void* alloc(size_t bytes) {
-        void* p = std::malloc(bytes ? bytes : 1);
-        if (p) { std::memset(p, 0xFF, bytes); bufs.push_back(p); }
-        return p;
-    }
-    int32_t h2d(void* dst, const void* src, size_t bytes) { std::memcpy(dst, src, bytes); return FNN_OK; }
-    int32_t d2h(void* dst, const void* src, size_t bytes) { std::memcpy(dst, src, bytes); return FNN_OK; }
+struct EmuRaggedBackend : EmuHeapBackend {
     int32_t validate_ragged(const double* base, const RaggedDesc* desc, int64_t cnt, int64_t* bad) {
         *bad = -1;
         for (int64_t k = 0; k < cnt; k++)  // (any order: the kernel takes the minimum index)
@@ -104,14 +38,12 @@ struct EmuRaggedBackend {
                 const RaggedDesc d = desc[cls[c].first + k];
                 const int32_t bytes = small_layout(d.n).bytes, threads = cls[c].threads;
                 if (bytes > cls[c].lds_bytes) { last = "a class reserves less LDS than one of its problems needs"; return FNN_ESTATE; }
-                unsigned char* lds = (unsigned char*)std::malloc((size_t)bytes);
-                if (!lds) { last = "out of memory"; return FNN_ENOMEM; }
-                std::memset(lds, 0xFF, (size_t)bytes);
-                const SmallView V = small_view(lds, d.n);
+                EmuBlock lds((size_t)bytes);
+                if (!lds.p) { last = "out of memory"; return FNN_ENOMEM; }
+                const SmallView V = small_view(lds.bytes(), d.n);
                 for (int t = 0; t < threads; t++) small_load(t, threads, V, base + d.src, d.ld, d.vec);
                 CpuExec ex{threads};
                 small_problem(ex, V, ev ? ev + d.ev : nullptr, meta + d.meta, log + d.log);
-                std::free(lds);
             }
         *t_kernel_s = now_s() - t0;
         return FNN_OK;
@@ -129,22 +61,12 @@ struct EmuRaggedBackend {
                 const RaggedDesc d = desc[cls[c].first + k];
                 const int32_t bytes = small_splits_layout(d.n, d.cap).bytes, threads = cls[c].threads;
                 if (bytes > cls[c].lds_bytes) { last = "a class reserves less LDS than one of its problems needs"; return FNN_ESTATE; }
-                const int64_t N = (int64_t)d.n * (d.n - 1) / 2, pitch = small_splits_work(d.n, d.cap).pitch;
-                unsigned char* lds = (unsigned char*)std::malloc((size_t)bytes);
-                double* slice = (double*)std::malloc(sizeof(double) * (size_t)pitch);  // this problem's slice, on its own
-                double* w = (double*)std::malloc(sizeof(double) * (size_t)N);
-                if (!lds || !slice || !w) { std::free(lds); std::free(slice); std::free(w); last = "out of memory"; return FNN_ENOMEM; }
-                std::memset(lds, 0xFF, (size_t)bytes);
-                std::memset(slice, 0xFF, sizeof(double) * (size_t)pitch);
-                std::memset(w, 0xFF, sizeof(double) * (size_t)N);
-                const SplitsView V = small_splits_view(lds, slice, d.n, d.cap);
-                CpuSplitsExec ex{threads};
-                small_splits_problem(ex, V, sw, base + d.src, d.ld, ord + d.ord, w, meta + d.meta);
-                std::memcpy(out + d.out, w, sizeof(double) * (size_t)N);
+                if (!emu_splits_problem(threads, bytes, small_splits_work(d.n, d.cap).pitch, d.n, d.cap, sw, base + d.src, d.ld, ord + d.ord, out + d.out,
+                                        meta + d.meta)) {
+                    last = "out of memory";
+                    return FNN_ENOMEM;
+                }
                 if ((size_t)d.id < g_giveups.size()) g_giveups[(size_t)d.id] = meta[d.meta].giveup;
-                std::free(w);
-                std::free(slice);
-                std::free(lds);
             }
         (void)work;
         *t_kernel_s = now_s() - t0;

@@ -12,12 +12,7 @@
 // include/fastnn.h with the prefix emu_.  There is no one-problem solver behind the driver: a problem that the kernel's
 // method gives up on (and any n above the limit) fails the call with FNN_ECAPACITY; emu_split_weights_batch_giveups says
 // which problems of the last call gave up, and why.
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../fastneighbornet_amd/csrc/fnn_small_splits.h"
+#include "fnn_small_emu.h"
 
 namespace {
 
@@ -26,74 +21,21 @@ using namespace fnn;
 thread_local std::vector<int32_t> g_giveups;  // FNN_SW_GIVEUP_* per problem of the last call that reached the kernel
 thread_local std::vector<int32_t> g_counts;   // ... and its six safety-net counts (the host keeps them for solved problems only)
 
-struct CpuSplitsExec {
-    int nt;
-    template <class F>
-    void all(F f) {
-        for (int t = 0; t < nt; t++) f(t, nt);
-    }
-    template <class F>
-    void best(const SplitsView& V, F f) {
-        for (int w = 0; w < (nt + 63) / 64; w++) {
-            SplitsRec b{0.0, -1, -1};
-            for (int t = w * 64; t < nt && t < (w + 1) * 64; t++) {
-                const SplitsRec o = f(t, nt);
-                if (splits_better(o, b)) b = o;
-            }
-            V.wred[w] = b;
-        }
-    }
-    template <class P, class S>
-    void rows(int32_t nrows, P share, S store) {
-        for (int32_t row = 0; row < nrows; row++) {
-            double p[64];
-            for (int l = 0; l < 64; l++) p[l] = share(row, l);
-            for (int off = 32; off > 0; off >>= 1)  // the tree of the kernel's shuffles, as lane 0 sees it
-                for (int l = 0; l < off; l++) p[l] += p[l + off];
-            store(row, p[0]);
-        }
-    }
-    template <class T>
-    T get(const T* p) { return *p; }
-};
-
-struct EmuSplitsBackend {
-    std::vector<void*> bufs;
-    std::string last;
+struct EmuSplitsBackend : EmuHeapBackend {
     int64_t done = 0;  // problems of earlier chunks
-    ~EmuSplitsBackend() { for (void* p : bufs) std::free(p); }
-    const std::string& err() const { return last; }
-    int32_t open(int32_t) { return FNN_OK; }
-    void* alloc(size_t bytes) {
-        void* p = std::malloc(bytes ? bytes : 1);
-        if (p) { std::memset(p, 0xFF, bytes); bufs.push_back(p); }
-        return p;
-    }
-    int32_t h2d(void* dst, const void* src, size_t bytes) { std::memcpy(dst, src, bytes); return FNN_OK; }
-    int32_t d2h(void* dst, const void* src, size_t bytes) { std::memcpy(dst, src, bytes); return FNN_OK; }
     int32_t run_splits(const double* D, int32_t n, int64_t ld, int64_t stride, const int32_t* ord, int64_t cnt, int32_t cap, int32_t threads,
                        int32_t lds_bytes, double* work, int64_t pitch, double* out, SplitsMeta* meta, double* t_kernel_s) {
         const double t0 = now_s();
         const SplitsSwitches sw = small_splits_switches();
         const int64_t N = (int64_t)n * (n - 1) / 2;
         for (int64_t b = 0; b < cnt; b++) {
-            unsigned char* lds = (unsigned char*)std::malloc((size_t)lds_bytes);
-            double* slice = (double*)std::malloc(sizeof(double) * (size_t)pitch);  // this problem's slice, on its own
-            double* w = (double*)std::malloc(sizeof(double) * (size_t)N);
-            if (!lds || !slice || !w) { std::free(lds); std::free(slice); std::free(w); last = "out of memory"; return FNN_ENOMEM; }
-            std::memset(lds, 0xFF, (size_t)lds_bytes);
-            std::memset(slice, 0xFF, sizeof(double) * (size_t)pitch);
-            std::memset(w, 0xFF, sizeof(double) * (size_t)N);
-            const SplitsView V = small_splits_view(lds, slice, n, cap);
-            CpuSplitsExec ex{threads};
-            small_splits_problem(ex, V, sw, D + b * stride, ld, ord + b * (n + 1), w, meta + b);
-            std::memcpy(out + b * N, w, sizeof(double) * (size_t)N);
+            if (!emu_splits_problem(threads, lds_bytes, pitch, n, cap, sw, D + b * stride, ld, ord + b * (n + 1), out + b * N, meta + b)) {
+                last = "out of memory";
+                return FNN_ENOMEM;
+            }
             g_giveups[(size_t)(done + b)] = meta[b].giveup;
             const int32_t cnt6[6] = {meta[b].aside_fresh, meta[b].aside_rebuild, meta[b].aside_enter, meta[b].rechecks, meta[b].releases, meta[b].departed};
             std::memcpy(&g_counts[(size_t)(done + b) * 6], cnt6, sizeof(cnt6));
-            std::free(w);
-            std::free(slice);
-            std::free(lds);
         }
         (void)work;
         done += cnt;
@@ -154,21 +96,15 @@ int64_t emu_split_weights_batch_counts(int32_t* out, int64_t cnt) {
 // exactly the kernel's sizes, filled with 0xFF bytes, as in run_splits.
 namespace {
 struct PhaseView {
-    unsigned char* lds;
-    double* slice;
+    EmuBlock lds, slice;
     SplitsView V;
-    PhaseView(int32_t n, double dep, int32_t max_steps) {
-        const int32_t cap = small_splits_capacity(n);
-        const size_t lb = (size_t)small_splits_layout(n, cap).bytes, wb = sizeof(double) * (size_t)small_splits_work(n, cap).pitch;
-        lds = (unsigned char*)std::malloc(lb);
-        slice = (double*)std::malloc(wb);
-        if (!lds || !slice) std::abort();
-        std::memset(lds, 0xFF, lb);
-        std::memset(slice, 0xFF, wb);
-        V = small_splits_view(lds, slice, n, cap);
+    PhaseView(int32_t n, double dep, int32_t max_steps)
+        : lds((size_t)small_splits_layout(n, small_splits_capacity(n)).bytes),
+          slice(sizeof(double) * (size_t)small_splits_work(n, small_splits_capacity(n)).pitch) {
+        if (!lds.p || !slice.p) std::abort();
+        V = small_splits_view(lds.bytes(), slice.doubles(), n, small_splits_capacity(n));
         splits_init(0, 1, V, SplitsSwitches{dep, max_steps, 0});
     }
-    ~PhaseView() { std::free(lds); std::free(slice); }
 };
 }  // namespace
 

@@ -18,7 +18,8 @@ import splits_batch_common as sc
 from fastneighbornet_amd import _capi
 
 EMU_SRCS = [os.path.join(bc.EMU_DIR, "fnn_ragged_emu.cpp")] + \
-    [os.path.join(bc.CSRC, f) for f in ("fnn_small_splits.h", "fnn_small.h", "fnn_engine.h", "fnn_core.h")] + [os.path.join(bc.ROOT, "include", "fastnn.h")]
+    [os.path.join(bc.CSRC, f) for f in ("fnn_small_splits.h", "fnn_small.h", "fnn_engine.h", "fnn_core.h")] + \
+    [os.path.join(bc.ROOT, "include", "fastnn.h"), os.path.join(bc.EMU_DIR, "fnn_small_emu.h")]
 
 SIZES = (1, 2, 3, 4, 5, 7, 8, 9, 16, 33, 63, 64, 65, 96, 97, 128)   # ... and lds_max_n
 SENTINEL = -77

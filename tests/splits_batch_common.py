@@ -17,7 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 CSRC = os.path.join(ROOT, "fastneighbornet_amd", "csrc")
 EMU_SRCS = [os.path.join(EMU_DIR, "fnn_splits_batch_emu.cpp")] + \
-    [os.path.join(CSRC, f) for f in ("fnn_small_splits.h", "fnn_small.h", "fnn_engine.h", "fnn_core.h")] + [os.path.join(ROOT, "include", "fastnn.h")]
+    [os.path.join(CSRC, f) for f in ("fnn_small_splits.h", "fnn_small.h", "fnn_engine.h", "fnn_core.h")] + \
+    [os.path.join(ROOT, "include", "fastnn.h"), os.path.join(EMU_DIR, "fnn_small_emu.h")]
 
 ROUTE_CLOSED_FORM, ROUTE_FROM_BELOW = 0, 1
 GIVEUP_CAPACITY = 1
@@ -203,6 +204,16 @@ def check_chunking(call, n, monkeypatch):
     assert (sw1["outer_iterations"] == sw2["outer_iterations"]).all()
     assert_kernel_only(s2, 8)
     assert_optimal(D, orders, w2, sw2, ("chunked", n))
+    # the chunks are evened out: 9 problems under a limit of 4 run as 3 + 3 + 3, not 4 + 4 + 1 (ceil(9 / ceil(9 / 4)) = 3),
+    # so the workspace is that of a 3-problem call
+    D9, orders9 = synth_batch(n, 9, seed0=500)
+    _, _, s3 = call(D9[:3], orders9[:3])
+    monkeypatch.setenv("FNN_BATCH_CHUNK", "4")
+    w9, _, s9 = call(D9, orders9)
+    monkeypatch.delenv("FNN_BATCH_CHUNK")
+    assert s3.chunks == 1 and s9.chunks == 3
+    assert s9.workspace_bytes == s3.workspace_bytes
+    assert w9[:8].tobytes() == w1.tobytes()
 
 
 def check_determinism(call, n):

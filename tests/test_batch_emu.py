@@ -43,8 +43,8 @@ def test_chunking(a, n, monkeypatch):
     bc.check_chunking(a, n, monkeypatch)
 
 
-def test_validation(a):
-    bc.check_validation(a)
+def test_validation(a, monkeypatch):
+    bc.check_validation(a, monkeypatch)
 
 
 def test_above_the_lds_limit_needs_the_engine(a):
