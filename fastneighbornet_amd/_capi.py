@@ -220,6 +220,45 @@ def run_splits_batch(a: Api, D, n: int, ld: int, stride: int, batch: int, orders
     return w, np.ctypeslib.as_array(sw)[:batch].copy(), st
 
 
+class FnnDistStats(C.Structure):
+    _fields_ = [("n_problems", C.c_int64), ("n_pairs", C.c_int64), ("n_sites", C.c_int64),
+                ("digit_passes", C.c_int32), ("has_missing", C.c_int32), ("block_threads", C.c_int32), ("chunks", C.c_int32),
+                ("t_upload_s", C.c_double), ("t_kernel_s", C.c_double), ("t_total_s", C.c_double), ("reserved", C.c_int64 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+SITE_MISSING = 255
+DIST_P = 0
+_DIST_ARGS = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+              C.c_int64, C.c_int64, C.POINTER(FnnDistStats)]
+
+
+def bind_dist(a: Api) -> Api:
+    """The alignment-distance entry points of include/fastnn.h (distance matrices of bootstrap replicates) on `a`."""
+    a._fn("alignment_distances_batch_f64", C.c_int32, _DIST_ARGS)
+    a._fn("alignment_distances_batch_device_f64", C.c_int32, _DIST_ARGS)
+    a._fn("bootstrap_counts", C.c_int32, [C.c_int64, C.c_int64, C.c_uint64, C.c_void_p])
+    return a
+
+
+def run_dist(a: Api, seq, n: int, L: int, lds: int, counts, batch: int, ldc: int, out, ld: int, stride: int,
+             model: int = DIST_P, device: int = 0, on_device: bool = False):
+    """One alignment-distance call on raw addresses (seq, counts: host memory; out: host memory, or device memory with
+    on_device); any of them may be None (NULL).  Returns the stats."""
+    st = FnnDistStats()
+    fn = a.alignment_distances_batch_device_f64 if on_device else a.alignment_distances_batch_f64
+    a.check(fn(seq, n, L, lds, counts, batch, ldc, model, device, out, ld, stride, C.byref(st)))
+    return st
+
+
+def run_bootstrap_counts(a: Api, L: int, batch: int, seed: int) -> np.ndarray:
+    counts = np.zeros((max(batch, 0), max(L, 0)), dtype=np.uint16)
+    a.check(a.bootstrap_counts(L, batch, seed & 0xFFFFFFFFFFFFFFFF, counts.ctypes.data))
+    return counts
+
+
 _lp = C.POINTER(C.c_int64)
 _RAGGED_ARGS = [C.c_void_p, _lp, _ip, _lp, C.c_int64, C.POINTER(FnnOpts), _ip, C.c_void_p, _ip, C.POINTER(FnnBatchStats)]
 _SPLITS_RAGGED_ARGS = [C.c_void_p, _lp, _ip, _lp, C.c_int64, _ip, C.c_int32, _dp, C.POINTER(FnnSwStats), C.POINTER(FnnSwBatchStats)]

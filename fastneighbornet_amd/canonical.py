@@ -332,3 +332,74 @@ def split_weights_sparse(D: np.ndarray, ordering: np.ndarray, threshold: float =
     out = {k: getattr(st, k) for k, _ in st._fields_ if not k.startswith(("reserved", "pad_"))}
     out["method"] = ("closed form", "from below", "reference")[st.route]
     return idx[:cnt.value], w[:cnt.value], out
+
+
+# ---- distance matrices of bootstrap replicates from an alignment
+
+def encode_alignment(seqs, missing: str = "-?NX") -> np.ndarray:
+    """A list of equal-length strings as the uint8 (n, L) array `alignment_distances_batch` takes: case is folded (to upper
+    case), every character of `missing` becomes 255 (`FNN_SITE_MISSING`), every other character its byte."""
+    rows = [s.upper().encode("latin-1") for s in seqs]
+    if not rows or any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError("the sequences must be a non-empty list of strings of one length")
+    out = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), len(rows[0])).copy()
+    for ch in set(missing.upper().encode("latin-1")):
+        out[out == ch] = _capi.SITE_MISSING
+    return out
+
+
+def bootstrap_counts(L: int, B: int, seed: int) -> np.ndarray:
+    """Site multiplicities uint16 (B, L) of B bootstrap replicates of an L-site alignment (`fnn_bootstrap_counts`: host only,
+    reproducible from `seed`; every row sums to L)."""
+    from . import api
+    return _capi.run_bootstrap_counts(api(), int(L), int(B), int(seed))
+
+
+def _dist_inputs(seq, counts):
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    counts = np.ascontiguousarray(counts, dtype=np.uint16)
+    if seq.ndim != 2 or counts.ndim != 2 or counts.shape[1] != seq.shape[1]:
+        raise ValueError("seq must have shape (n, L) and counts (B, L)")
+    return seq, counts
+
+
+def alignment_distances_batch(seq, counts, device: int = 0, out: str = "numpy"):
+    """p-distance matrices of the replicates `counts` (uint16 (B, L) site multiplicities) of the alignment `seq` (uint8 (n, L),
+    255 = missing: `encode_alignment`) over `fnn_alignment_distances_batch_f64`: exact integer counts on the int8 matrix
+    cores and one IEEE division per entry.  out="numpy" returns a float64 array (B, n, n); out="torch" allocates a
+    torch.float64 tensor (B, n, n) on the GPU and hands its address to the device entry, so that `canonical_order_batch` and
+    `split_weights_batch` can read it in place.  Returns (matrices, stats dict).  Raises FnnError with code -1 naming the
+    lowest (b, i, j) when two taxa share no site in a replicate."""
+    from . import api
+    a = api()
+    seq, counts = _dist_inputs(seq, counts)
+    (n, L), B = seq.shape, counts.shape[0]
+    if out == "torch":
+        import torch
+        dev = torch.device("cuda", device)
+        D = torch.empty((B, n, n), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        st = _capi.run_dist(a, seq.ctypes.data, n, L, L, counts.ctypes.data, B, L, D.data_ptr() if B and n else None, max(n, 1), max(n * n, 1),
+                            device=device, on_device=True)
+    elif out == "numpy":
+        D = np.empty((B, n, n), dtype=np.float64)
+        st = _capi.run_dist(a, seq.ctypes.data, n, L, L, counts.ctypes.data, B, L, D.ctypes.data, max(n, 1), max(n * n, 1), device=device)
+    else:
+        raise ValueError('out must be "numpy" or "torch"')
+    return D, st.as_dict()
+
+
+def bootstrap(seq, B: int, seed: int, weights: bool = True, device: int = 0):
+    """B bootstrap replicates of the alignment `seq` (uint8 (n, L)) end to end: `bootstrap_counts`, the distance matrices as a
+    tensor on the GPU, `canonical_order_batch` of that tensor and (weights=True) `split_weights_batch` of it.  No matrix
+    crosses to the host.  Returns (orders[B, n + 1], W[B, n(n-1)/2] or None, stats) with stats = {"distances": ..., "splits":
+    ... (weights=True)}."""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    counts = bootstrap_counts(seq.shape[1], B, seed)
+    D, dst = alignment_distances_batch(seq, counts, device=device, out="torch")
+    orders = canonical_order_batch(D, device=device)
+    stats = {"distances": dst}
+    W = None
+    if weights:
+        W, stats["splits"] = split_weights_batch(D, orders, device=device)
+    return orders, W, stats

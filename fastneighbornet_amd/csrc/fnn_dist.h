@@ -1,0 +1,323 @@
+// fnn_dist.h -- p-distance matrices of bootstrap replicates from one alignment: the per-lane
+// steps of k_dist (fnn_dist.hip) and the host side of fnn_alignment_distances_batch[_device]_f64, both shared with the
+// CPU driver (tests/emu/fnn_dist_emu.cpp) the way fnn_small.h is.
+//
+// For one alignment and all replicates the counts are a matrix product, C[pair][b] = sum_s M[pair][s] * W[s][b], with M
+// the 0/1 indicator of a mismatch (or of "both present") and W the site multiplicities.  One wave takes one TILE of 16
+// pairs - one taxon i against 16 consecutive taxa j0 ... j0 + 15 - and DIST_RT tiles of 16 replicates, and walks the
+// sites 64 at a time on v_mfma_i32_16x16x64_i8:
+//   A (pairs x sites)       lane l holds A[row l & 15][k = 16 (l >> 4) + t], t = 0 ... 15: sixteen 0/1 bytes made in registers
+//                           from 16 bytes of row i and 16 bytes of row j0 + (l & 15) (packed-byte arithmetic, no LDS);
+//   B (sites x replicates)  lane l holds B[k = 16 (l >> 4) + t][col l & 15]: 16 consecutive bytes of one replicate's row of a
+//                           DIGIT PLANE of the counts (int8 operands are signed: a count is split into base-128 digits,
+//                           one plane and one int32 accumulator per digit);
+//   C / D                   lane l holds C[row 4 (l >> 4) + r][col l & 15] in register r = 0 ... 3.
+// The device images are padded by the host: the alignment to n + 16 rows of lpad = round_up(L, 64) bytes, padding 255;
+// the planes to round_up(replicates of the chunk, 64) rows of lpad bytes, padding 0.  Padded pairs and replicates compute
+// values that are never stored, so the kernel has no tail branch in its loop and a 16-byte load never leaves its buffer.
+// Every (b, i, j) is stored by exactly one lane; no atomics, no LDS, no hand-over between workgroups.
+#ifndef FNN_DIST_H
+#define FNN_DIST_H
+
+#include <stdint.h>
+
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "fnn_small.h"  // batch_chunk (FNN_BATCH_CHUNK), round_up; fnn_engine.h: fail, now_s, the FNN_* codes
+
+namespace fnn {
+
+constexpr int32_t DIST_TILE = 16;          // pairs per tile = replicates per tile (M = N of the instruction)
+constexpr int32_t DIST_K = 64;             // sites per instruction
+constexpr int32_t DIST_RT = 4;             // replicate tiles per wave: one A fragment serves 4 x digits (x 2) products
+constexpr int32_t DIST_WAVES = 4;          // waves per workgroup: 4 pair tiles against the same replicates
+constexpr int32_t DIST_THREADS = 64 * DIST_WAVES;
+constexpr int32_t DIST_REPS = DIST_TILE * DIST_RT;  // replicates per workgroup
+constexpr int32_t DIST_PAD_ROWS = 16;      // rows of 255 behind the alignment: j0 + 15 <= n + 15
+constexpr int32_t DIST_MAX_DIGITS = 3;     // 65535 < 128^3
+
+struct alignas(16) DistFrag { uint32_t w[4]; };  // 16 operand bytes of one lane
+struct DistAcc { int32_t r[4]; };                // the 4 accumulator registers of one lane
+struct DistTile { int32_t i, j0; };              // taxon i against j0 ... j0 + 15; i == n: a filler tile, nothing stored
+
+struct DistArgs {
+    const uint8_t* seq;      // n + DIST_PAD_ROWS rows of lpad bytes
+    int64_t lpad;
+    const DistTile* tiles;   // a multiple of DIST_WAVES
+    const int8_t* planes;    // digit d of the chunk's replicate b: planes + d * plane_stride + b * lpad
+    int64_t plane_stride;
+    const int64_t* total;    // sum of the counts of replicate b: `valid` of every pair when no byte is missing
+    int32_t n;
+    int64_t cnt;             // replicates of the chunk
+    double* out;             // replicate b at out + b * stride, row stride ld
+    int64_t ld, stride;
+    int32_t* bad;            // bad[b] = 1: some pair of replicate b has valid == 0 (its entries are NaN)
+};
+
+// ---- fragment construction from bytes
+FNN_HD DistFrag dist_load16(const void* p) {
+    DistFrag f;
+    __builtin_memcpy(&f, __builtin_assume_aligned(p, 16), 16);
+    return f;
+}
+// per byte of x: 1 where the byte is not zero, else 0
+FNN_HD uint32_t dist_nonzero_bytes(uint32_t x) { return ((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u) >> 7; }
+// the A operands of one lane from its 16 bytes of row i and of row j: mism = both present and different, valid = both
+// present (MISSING only; without a missing byte in the alignment mism is "different" and valid is not needed)
+template <bool MISSING>
+FNN_HD void dist_a_frags(const DistFrag& ri, const DistFrag& rj, DistFrag& mism, DistFrag& valid) {
+    for (int q = 0; q < 4; q++) {
+        uint32_t d = dist_nonzero_bytes(ri.w[q] ^ rj.w[q]);
+        if (MISSING) {
+            const uint32_t p = dist_nonzero_bytes(~ri.w[q]) & dist_nonzero_bytes(~rj.w[q]);  // (~x == 0: the byte is 255)
+            valid.w[q] = p;
+            d &= p;
+        }
+        mism.w[q] = d;
+    }
+}
+// lane maps of the 16 x 16 x 64 int8 form (verified with exact integers: tests/dist_common.py, case "lane maps")
+FNN_HD int dist_lane_rc(int lane) { return lane & 15; }        // A: row (pair of the tile); B, C: column (replicate)
+FNN_HD int dist_lane_k(int lane) { return 16 * (lane >> 4); }  // A, B: first of the lane's 16 consecutive k (sites)
+FNN_HD int dist_lane_row(int lane, int r) { return 4 * (lane >> 4) + r; }  // C: row (pair) of accumulator register r
+
+template <bool MISSING>
+FNN_HD void dist_lane_a(const DistArgs& a, const DistTile& t, int lane, int64_t s, DistFrag& mism, DistFrag& valid) {
+    const int64_t off = s + dist_lane_k(lane);
+    const DistFrag ri = dist_load16(a.seq + (int64_t)t.i * a.lpad + off);
+    const DistFrag rj = dist_load16(a.seq + (int64_t)(t.j0 + dist_lane_rc(lane)) * a.lpad + off);
+    dist_a_frags<MISSING>(ri, rj, mism, valid);
+}
+// b0: the first replicate of the workgroup (a multiple of DIST_REPS), rt: the replicate tile, d: the digit
+FNN_HD DistFrag dist_lane_b(const DistArgs& a, int64_t b0, int rt, int d, int lane, int64_t s) {
+    return dist_load16(a.planes + (int64_t)d * a.plane_stride + (b0 + DIST_TILE * rt + dist_lane_rc(lane)) * a.lpad + s + dist_lane_k(lane));
+}
+
+// ---- digit split and combine
+FNN_HD int8_t dist_digit(uint16_t c, int d) { return (int8_t)((c >> (7 * d)) & 127); }
+template <int P>
+FNN_HD int64_t dist_combine(const DistAcc* acc, int r) {  // (each digit's sum is below 2^31: 127 L < 2^31 is an argument check)
+    int64_t v = 0;
+    for (int d = P; d-- > 0;) v = v * 128 + (int64_t)acc[d].r[r];
+    return v;
+}
+FNN_HD double dist_divide(int64_t mism, int64_t valid) { return (double)mism / (double)valid; }  // one IEEE division
+FNN_HD int64_t dist_store_index(int64_t i, int64_t j, int64_t ld) { return i * ld + j; }
+
+// ---- the tile product over the 64 lanes' fragments.  Device: the instruction; host: loops from the lane maps above.
+#if defined(__HIPCC__)
+typedef int dist_v4i __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ DistAcc dist_mma(const DistFrag& a, const DistFrag& b, const DistAcc& c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const dist_v4i va = {(int)a.w[0], (int)a.w[1], (int)a.w[2], (int)a.w[3]}, vb = {(int)b.w[0], (int)b.w[1], (int)b.w[2], (int)b.w[3]};
+    const dist_v4i vc = {c.r[0], c.r[1], c.r[2], c.r[3]};
+    const dist_v4i o = __builtin_amdgcn_mfma_i32_16x16x64_i8(va, vb, vc, 0, 0, 0);
+    return DistAcc{{o[0], o[1], o[2], o[3]}};
+#else
+    return c;  // (the host pass only parses the kernel)
+#endif
+}
+#endif
+#if !defined(__HIP_DEVICE_COMPILE__)
+inline void dist_tile_product(const DistFrag* A, const DistFrag* B, DistAcc* C) {  // 64 lanes each; C += A * B
+    for (int lane = 0; lane < 64; lane++)
+        for (int r = 0; r < 4; r++) {
+            const int row = dist_lane_row(lane, r), col = dist_lane_rc(lane);
+            int32_t sum = C[lane].r[r];
+            for (int g = 0; g < 4; g++) {  // k = 16 g + t lives in lane (g, row) of A and lane (g, col) of B
+                int8_t ab[16], bb[16];
+                std::memcpy(ab, &A[16 * g + row], 16);
+                std::memcpy(bb, &B[16 * g + col], 16);
+                for (int t = 0; t < 16; t++) sum += (int32_t)ab[t] * (int32_t)bb[t];
+            }
+            C[lane].r[r] = sum;
+        }
+}
+#endif
+
+// ---- the epilogue of one lane for one replicate tile: combine, divide, store both triangles (and the diagonal, by the
+// first tile of each taxon).  b0: the first replicate of the TILE.
+template <int P, bool MISSING>
+FNN_HD void dist_lane_store(const DistArgs& a, const DistTile& t, int64_t b0, int lane, const DistAcc* mism, const DistAcc* valid) {
+    const int64_t b = b0 + dist_lane_rc(lane);
+    if (b >= a.cnt || t.i >= a.n) return;
+    double* D = a.out + b * a.stride;
+    if (t.j0 == t.i + 1 && lane < 16) D[dist_store_index(t.i, t.i, a.ld)] = 0.0;
+    for (int r = 0; r < 4; r++) {
+        const int32_t j = t.j0 + dist_lane_row(lane, r);
+        if (j >= a.n) continue;
+        const int64_t m = dist_combine<P>(mism, r);
+        const int64_t v = MISSING ? dist_combine<P>(valid, r) : a.total[b];
+        double d;
+        if (v == 0) { a.bad[b] = 1; d = __builtin_nan(""); }
+        else d = dist_divide(m, v);
+        D[dist_store_index(t.i, j, a.ld)] = d;
+        D[dist_store_index(j, t.i, a.ld)] = d;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+// tiles of taxon i: j0 = i + 1 + 16 t while j0 < n, and at least one (it stores the diagonal entry); filled up to a
+// multiple of DIST_WAVES with {n, n}
+inline std::vector<DistTile> dist_tiles(int32_t n) {
+    std::vector<DistTile> t;
+    for (int32_t i = 0; i < n; i++) {
+        t.push_back(DistTile{i, i + 1});
+        for (int64_t j0 = (int64_t)i + 1 + DIST_TILE; j0 < n; j0 += DIST_TILE) t.push_back(DistTile{i, (int32_t)j0});
+    }
+    while (t.size() % DIST_WAVES) t.push_back(DistTile{n, n});
+    return t;
+}
+inline bool dist_force_missing() {
+    const char* e = std::getenv("FNN_DIST_FORCE_MISSING");
+    return e && std::atoi(e) == 1;
+}
+inline int32_t dist_fail_no_site(const std::string& W, int64_t b, int64_t i, int64_t j) {
+    return fail(FNN_EINVAL, W + "no site with both taxa present (valid == 0) at (b, i, j) = (" + std::to_string(b) + ", " + std::to_string(i) +
+                                ", " + std::to_string(j) + ")");
+}
+
+// fnn_bootstrap_counts: replicate b draws k = 0 ... L - 1 and increments site floor(x L / 2^64), x = splitmix64_at(seed, b L + k)
+inline int32_t dist_bootstrap_counts(const char* who, int64_t L, int64_t batch, uint64_t seed, uint16_t* counts_out) {
+    const std::string W = std::string(who) + ": ";
+    if (L <= 0 || batch < 0) return fail(FNN_EINVAL, W + "needs L > 0 and batch >= 0");
+    if (batch == 0) return FNN_OK;
+    if (!counts_out) return fail(FNN_EINVAL, W + "NULL argument");
+    std::vector<uint32_t> row((size_t)L);
+    for (int64_t b = 0; b < batch; b++) {
+        std::fill(row.begin(), row.end(), 0u);
+        for (int64_t k = 0; k < L; k++) {
+            const uint64_t x = splitmix64_at(seed, (uint64_t)b * (uint64_t)L + (uint64_t)k);
+            row[(size_t)(uint64_t)(((unsigned __int128)x * (unsigned __int128)(uint64_t)L) >> 64)]++;
+        }
+        for (int64_t s = 0; s < L; s++) {
+            if (row[(size_t)s] > 65535u) return fail(FNN_EINVAL, W + "replicate " + std::to_string(b) + ": a site was drawn more than 65535 times");
+            counts_out[b * L + s] = (uint16_t)row[(size_t)s];
+        }
+    }
+    return FNN_OK;
+}
+
+// fnn_alignment_distances_batch[_device]_f64 over a backend B (HIP: fnn_dist.hip; CPU driver: tests/emu):
+//   open(device); alloc; h2d / d2h; run(digits, missing, args, tile groups, replicate groups, &t_kernel_s); err()
+// The host variant writes D_out only when the whole call has succeeded.
+template <class B>
+int32_t dist_batch(B& be, const char* who, const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts, int64_t batch,
+                   int64_t ldc, int32_t model, int32_t device, double* D_out, bool on_device, int64_t ld, int64_t stride, fnn_dist_stats* stats) {
+    const double t0 = now_s();
+    const std::string W = std::string(who) + ": ";
+    fnn_dist_stats st{};
+    if (n <= 0 || L <= 0 || batch < 0) return fail(FNN_EINVAL, W + "needs n > 0, L > 0 and batch >= 0");
+    if (model != FNN_DIST_P) return fail(FNN_EINVAL, W + "unknown model");
+    if (L > (((int64_t)1 << 31) - 1) / 127) return fail(FNN_EINVAL, W + "too many sites: 127 L must stay below 2^31 (the int32 digit accumulators)");
+    if (batch == 0) { if (stats) *stats = st; return FNN_OK; }
+    if (!seq || !counts || !D_out) return fail(FNN_EINVAL, W + "NULL argument");
+    if (lds < L || ldc < L) return fail(FNN_EINVAL, W + "needs lds >= L and ldc >= L");
+    if (ld < n || stride < (int64_t)n * ld) return fail(FNN_EINVAL, W + "needs ld >= n and stride >= n * ld");
+    st.n_problems = batch;
+    st.n_pairs = (int64_t)n * (n - 1) / 2;
+    st.n_sites = L;
+    st.block_threads = DIST_THREADS;
+
+    // one look at the inputs: a missing byte, the largest count, every replicate's total
+    bool missing = dist_force_missing();
+    for (int32_t i = 0; i < n && !missing; i++) missing = std::memchr(seq + (int64_t)i * lds, FNN_SITE_MISSING, (size_t)L) != nullptr;
+    st.has_missing = missing ? 1 : 0;
+    std::vector<int64_t> total((size_t)batch, 0);
+    uint16_t cmax = 0;
+    for (int64_t b = 0; b < batch; b++) {
+        const uint16_t* c = counts + b * ldc;
+        int64_t t = 0;
+        for (int64_t s = 0; s < L; s++) { t += c[s]; cmax = c[s] > cmax ? c[s] : cmax; }
+        total[(size_t)b] = t;
+    }
+    const int32_t P = cmax <= 127 ? 1 : (cmax <= 16383 ? 2 : 3);
+    st.digit_passes = P;
+    // valid is the total: an empty replicate has valid == 0 for every pair, (0, 1) the lowest (with missing bytes the
+    // kernel flags it, so that a lower replicate with one empty pair is named first)
+    if (n >= 2 && !missing)
+        for (int64_t b = 0; b < batch; b++)
+            if (total[(size_t)b] == 0) return dist_fail_no_site(W, b, 0, 1);
+
+    int32_t rc = be.open(device);
+    if (rc != FNN_OK) return fail(rc, W + be.err());
+    const double tu0 = now_s();
+    const int64_t lpad = round_up(L, (int64_t)DIST_K), nn = (int64_t)n * n;
+    const std::vector<DistTile> tiles = dist_tiles(n);
+    const int64_t chunk = batch_chunk(batch, 8 * nn + (int64_t)P * lpad, false), cpad = round_up(chunk, (int64_t)DIST_REPS);
+    const size_t seq_bytes = (size_t)(n + DIST_PAD_ROWS) * (size_t)lpad, plane_bytes = (size_t)cpad * (size_t)lpad;
+    uint8_t* d_seq = (uint8_t*)be.alloc(seq_bytes);
+    DistTile* d_tiles = (DistTile*)be.alloc(sizeof(DistTile) * tiles.size());
+    int8_t* d_planes = (int8_t*)be.alloc(plane_bytes * (size_t)P);
+    int64_t* d_total = (int64_t*)be.alloc(sizeof(int64_t) * (size_t)cpad);
+    int32_t* d_bad = (int32_t*)be.alloc(sizeof(int32_t) * (size_t)cpad);
+    double* d_out = on_device ? nullptr : (double*)be.alloc(sizeof(double) * (size_t)nn * (size_t)chunk);
+    if (!d_seq || !d_tiles || !d_planes || !d_total || !d_bad || (!on_device && !d_out)) return fail(FNN_ENOMEM, W + "device allocation failed");
+    {
+        std::vector<uint8_t> img(seq_bytes, (uint8_t)FNN_SITE_MISSING);
+        for (int32_t i = 0; i < n; i++) std::memcpy(&img[(size_t)i * (size_t)lpad], seq + (int64_t)i * lds, (size_t)L);
+        if (be.h2d(d_seq, img.data(), seq_bytes) != FNN_OK || be.h2d(d_tiles, tiles.data(), sizeof(DistTile) * tiles.size()) != FNN_OK)
+            return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
+    }
+    st.t_upload_s += now_s() - tu0;
+    std::vector<int8_t> planes(plane_bytes * (size_t)P);
+    std::vector<int64_t> tot((size_t)cpad);
+    std::vector<int32_t> bad((size_t)cpad);
+    std::vector<double> stage(on_device ? 0 : (size_t)nn * (size_t)batch), one;
+    for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+        const int64_t cnt = batch - b0 < chunk ? batch - b0 : chunk;
+        st.chunks++;
+        const double tu = now_s();
+        std::memset(planes.data(), 0, planes.size());  // (padding: zero counts)
+        std::fill(tot.begin(), tot.end(), (int64_t)0);
+        std::fill(bad.begin(), bad.end(), 0);
+        for (int64_t b = 0; b < cnt; b++) {
+            const uint16_t* c = counts + (b0 + b) * ldc;
+            tot[(size_t)b] = total[(size_t)(b0 + b)];
+            for (int d = 0; d < P; d++) {
+                int8_t* row = &planes[(size_t)d * plane_bytes + (size_t)b * (size_t)lpad];
+                for (int64_t s = 0; s < L; s++) row[s] = dist_digit(c[s], d);
+            }
+        }
+        if (be.h2d(d_planes, planes.data(), planes.size()) != FNN_OK || be.h2d(d_total, tot.data(), sizeof(int64_t) * (size_t)cpad) != FNN_OK ||
+            be.h2d(d_bad, bad.data(), sizeof(int32_t) * (size_t)cpad) != FNN_OK)
+            return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
+        st.t_upload_s += now_s() - tu;
+        DistArgs a{};
+        a.seq = d_seq; a.lpad = lpad; a.tiles = d_tiles; a.planes = d_planes; a.plane_stride = (int64_t)plane_bytes; a.total = d_total;
+        a.n = n; a.cnt = cnt; a.bad = d_bad;
+        if (on_device) { a.out = D_out + b0 * stride; a.ld = ld; a.stride = stride; }
+        else { a.out = d_out; a.ld = n; a.stride = nn; }
+        double tk = 0.0;
+        if (be.run(P, missing, a, (int64_t)(tiles.size() / DIST_WAVES), round_up(cnt, (int64_t)DIST_REPS) / DIST_REPS, &tk) != FNN_OK)
+            return fail(FNN_EHIP, W + "kernel failed (" + be.err() + ")");
+        st.t_kernel_s += tk;
+        if (be.d2h(bad.data(), d_bad, sizeof(int32_t) * (size_t)cnt) != FNN_OK) return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
+        for (int64_t b = 0; b < cnt; b++) {
+            if (!bad[(size_t)b]) continue;
+            // the lowest replicate with an empty pair: its matrix names the pair (NaN entries)
+            const size_t span = (size_t)((int64_t)(n - 1) * a.ld + n);
+            one.resize(span);
+            if (be.d2h(one.data(), a.out + b * a.stride, sizeof(double) * span) != FNN_OK) return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
+            for (int32_t i = 0; i < n; i++)
+                for (int32_t j = i + 1; j < n; j++)
+                    if (one[(size_t)dist_store_index(i, j, a.ld)] != one[(size_t)dist_store_index(i, j, a.ld)]) return dist_fail_no_site(W, b0 + b, i, j);
+            return fail(FNN_EHIP, W + "replicate " + std::to_string(b0 + b) + ": flagged without an empty pair");
+        }
+        if (!on_device && be.d2h(&stage[(size_t)b0 * (size_t)nn], d_out, sizeof(double) * (size_t)nn * (size_t)cnt) != FNN_OK)
+            return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
+    }
+    if (!on_device)
+        for (int64_t b = 0; b < batch; b++)
+            for (int32_t r = 0; r < n; r++)
+                std::memcpy(D_out + b * stride + (int64_t)r * ld, &stage[(size_t)b * (size_t)nn + (size_t)r * (size_t)n], sizeof(double) * (size_t)n);
+    st.t_total_s = now_s() - t0;
+    if (stats) *stats = st;
+    return FNN_OK;
+}
+
+}  // namespace fnn
+#endif

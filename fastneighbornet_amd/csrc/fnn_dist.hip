@@ -1,0 +1,95 @@
+// fnn_dist.hip -- p-distance matrices of bootstrap replicates from one alignment on the int8 matrix cores (the per-lane
+// steps and the host side of the call are fnn_dist.h).
+//
+// k_dist<P, MISSING>: a workgroup is 4 waves; wave w takes pair tile 4 * (tile group) + w (taxon i against j0 ... j0 + 15)
+// and the workgroup's 64 replicates as 4 tiles of 16.  Per 64 sites a lane loads 16 bytes of row i and of its row j, makes
+// the 0/1 operand bytes in registers, loads 16 bytes of each digit plane of each of its 4 replicates and issues
+// 4 x P (x 2 with MISSING) v_mfma_i32_16x16x64_i8.  No LDS, no atomics, no hand-over; vector stores and plain C++ only.
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "fnn_dist.h"
+#include "fnn_ragged_hip.h"
+
+namespace fnn {
+
+// grid: (tile groups) x (replicate groups) workgroups in one dimension, the replicate group the slow index: workgroups
+// that run at the same time read the same rows of the planes
+template <int P, bool MISSING>
+__global__ __launch_bounds__(DIST_THREADS) void k_dist(const DistArgs a, const uint32_t tile_groups) {
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    const uint32_t rg = blockIdx.x / tile_groups, tg = blockIdx.x - rg * tile_groups;
+    const DistTile t = a.tiles[(size_t)tg * DIST_WAVES + (size_t)wave];
+    const int64_t b0 = (int64_t)rg * DIST_REPS;
+    DistAcc am[DIST_RT][P], av[DIST_RT][MISSING ? P : 1];
+    for (int rt = 0; rt < DIST_RT; rt++)
+        for (int d = 0; d < P; d++) {
+            am[rt][d] = DistAcc{{0, 0, 0, 0}};
+            av[rt][MISSING ? d : 0] = DistAcc{{0, 0, 0, 0}};
+        }
+    for (int64_t s = 0; s < a.lpad; s += DIST_K) {
+        DistFrag fm, fv;
+        dist_lane_a<MISSING>(a, t, lane, s, fm, fv);
+#pragma unroll
+        for (int rt = 0; rt < DIST_RT; rt++)
+#pragma unroll
+            for (int d = 0; d < P; d++) {
+                const DistFrag fb = dist_lane_b(a, b0, rt, d, lane, s);
+                am[rt][d] = dist_mma(fm, fb, am[rt][d]);
+                if (MISSING) av[rt][d] = dist_mma(fv, fb, av[rt][d]);
+            }
+    }
+#pragma unroll
+    for (int rt = 0; rt < DIST_RT; rt++) dist_lane_store<P, MISSING>(a, t, b0 + DIST_TILE * rt, lane, am[rt], av[rt]);
+}
+
+struct DistHipBackend : HipBatchBase {
+    template <int P, bool MISSING>
+    int32_t launch(const DistArgs& a, int64_t tile_groups, int64_t rep_groups, double* t_kernel_s) {
+        return timed_launch(reinterpret_cast<const void*>(&k_dist<P, MISSING>), "k_dist", 0, [&] {
+            hipLaunchKernelGGL((k_dist<P, MISSING>), dim3((unsigned)(tile_groups * rep_groups)), dim3(DIST_THREADS), 0, stream, a, (uint32_t)tile_groups);
+        }, t_kernel_s);
+    }
+    int32_t run(int32_t P, bool missing, const DistArgs& a, int64_t tile_groups, int64_t rep_groups, double* t_kernel_s) {
+        if (tile_groups * rep_groups >= ((int64_t)1 << 31)) { last = "too many workgroups for one launch"; return FNN_EHIP; }
+        switch (P * 2 + (missing ? 1 : 0)) {
+            case 2: return launch<1, false>(a, tile_groups, rep_groups, t_kernel_s);
+            case 3: return launch<1, true>(a, tile_groups, rep_groups, t_kernel_s);
+            case 4: return launch<2, false>(a, tile_groups, rep_groups, t_kernel_s);
+            case 5: return launch<2, true>(a, tile_groups, rep_groups, t_kernel_s);
+            case 6: return launch<3, false>(a, tile_groups, rep_groups, t_kernel_s);
+            case 7: return launch<3, true>(a, tile_groups, rep_groups, t_kernel_s);
+        }
+        last = "no kernel for " + std::to_string(P) + " digits";
+        return FNN_EHIP;
+    }
+};
+
+}  // namespace fnn
+
+extern "C" {
+
+int32_t fnn_alignment_distances_batch_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts, int64_t batch, int64_t ldc,
+                                          int32_t model, int32_t device, double* D_out, int64_t ld, int64_t stride, fnn_dist_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch(be, "fnn_alignment_distances_batch_f64", seq, n, L, lds, counts, batch, ldc, model, device, D_out, false, ld, stride, stats);
+    )
+}
+
+int32_t fnn_alignment_distances_batch_device_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts, int64_t batch,
+                                                 int64_t ldc, int32_t model, int32_t device, double* d_D_out, int64_t ld, int64_t stride,
+                                                 fnn_dist_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch(be, "fnn_alignment_distances_batch_device_f64", seq, n, L, lds, counts, batch, ldc, model, device, d_D_out, true, ld, stride, stats);
+    )
+}
+
+int32_t fnn_bootstrap_counts(int64_t L, int64_t batch, uint64_t seed, uint16_t* counts_out) {
+    FNN_BATCH_TRY(return fnn::dist_bootstrap_counts("fnn_bootstrap_counts", L, batch, seed, counts_out);)
+}
+
+}  // extern "C"

@@ -480,6 +480,50 @@ int32_t fnn_split_weights_ragged_device_f64(const double* d_D, const int64_t* of
                                             int64_t batch, const int32_t* orderings, int32_t device, double* weights_out,
                                             fnn_sw_stats* stats_out, fnn_sw_batch_stats* stats);
 
+/* ---- distance matrices of bootstrap replicates from one alignment ------------
+ * The first stage of a bootstrap / jackknife / sliding-window run: one alignment and per-replicate site multiplicities go
+ * in, `batch` p-distance matrices come out in the layout the batch calls above read.
+ * seq: n x L bytes, row i at seq + i * lds (lds >= L; padding is never read).  Byte 255 (FNN_SITE_MISSING) means "no
+ * state here" (gap, N, ambiguity: the caller maps those); every other byte is a state, compared by equality only.
+ * counts: batch x L uint16_t, row b at counts + b * ldc (ldc >= L): how often site s occurs in replicate b (bootstrap
+ * resampling, 0 / 1 for a jackknife or a window, pattern counts of a compressed alignment).  Both are HOST arrays in both
+ * variants.  For replicate b and taxa i != j, as exact integers,
+ *     valid = sum_s counts[b][s] * [seq[i][s] != 255 and seq[j][s] != 255]
+ *     mism  = sum_s counts[b][s] * [both present and seq[i][s] != seq[j][s]]
+ * and with model FNN_DIST_P (the only one so far; any other value is FNN_EINVAL) D_b[i][j] = D_b[j][i] =
+ * (double)mism / (double)valid, one correctly rounded division; D_b[i][i] = 0.  Replicate b is written at D_out + b * stride
+ * with row stride ld (ld >= n, stride >= n * ld), padding untouched.
+ * FNN_EINVAL: n <= 0, L <= 0, batch < 0, lds < L, ldc < L, ld < n, stride < n * ld, a NULL array, an unknown model,
+ * 127 L >= 2^31 (the counts are summed per base-128 digit in int32) - all of these before any device use -, and
+ * valid == 0 for some (b, i, j): fnn_last_error() names the lowest such (b, i, j) in lexicographic order.  batch == 0 is
+ * FNN_OK; n == 1 writes the single zero.
+ * The host variant writes D_out only when the whole call has succeeded and works in chunks of at most 2 GiB of device
+ * output (FNN_BATCH_CHUNK=<problems> overrides the chunk size, for tests).  The device variant writes D_out (device memory)
+ * in place: when it FAILS THE CONTENTS OF D_out ARE UNSPECIFIED.  It has synchronised its own stream before it returns, so
+ * a batch call on D_out may follow directly.  Both run on `device` and leave the caller's current HIP device as they found
+ * it.  stats: digit_passes = base-128 digits of the largest count of the call (1 up to 127 - every bootstrap -, 2 up to
+ * 16383, else 3); has_missing = 1: the alignment holds a byte 255 and the kernel counts `valid` per pair (otherwise it is
+ * the replicate's total; FNN_DIST_FORCE_MISSING=1 takes the counting kernel anyway, for tests). */
+#define FNN_SITE_MISSING 255
+enum { FNN_DIST_P = 0 };
+typedef struct fnn_dist_stats {
+    int64_t n_problems, n_pairs, n_sites;
+    int32_t digit_passes, has_missing, block_threads, chunks;
+    double  t_upload_s, t_kernel_s, t_total_s;
+    int64_t reserved[4];
+} fnn_dist_stats;
+int32_t fnn_alignment_distances_batch_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds,
+                                          const uint16_t* counts, int64_t batch, int64_t ldc, int32_t model, int32_t device,
+                                          double* D_out, int64_t ld, int64_t stride, fnn_dist_stats* stats /* may be NULL */);
+int32_t fnn_alignment_distances_batch_device_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds,
+                                                 const uint16_t* counts, int64_t batch, int64_t ldc, int32_t model, int32_t device,
+                                                 double* d_D_out, int64_t ld, int64_t stride, fnn_dist_stats* stats);
+/* Reproducible bootstrap multiplicities, host only (no device needed): replicate b draws k = 0 ... L - 1 and increments
+ * site floor(x L / 2^64) (the high half of the 128-bit product), x = the (b L + k)-th output of SplitMix64 for `seed`
+ * (z = seed + (b L + k + 1) * 0x9E3779B97F4A7C15, then the usual two multiply-xorshift rounds).  counts_out: batch x L,
+ * dense.  A count above 65535 is FNN_EINVAL. */
+int32_t fnn_bootstrap_counts(int64_t L, int64_t batch, uint64_t seed, uint16_t* counts_out /* batch x L */);
+
 /* Diagnostic: the exact block-parallel evaluation of the sequential fp64 sum
  * (((0 + b[0]) + b[1]) + ...) used for ComputeRx / u.Sx (NetMakerOriginal.java:551-560,
  * :532), run on an arbitrary host buffer.  ept = addends per thread (32, fixed by the

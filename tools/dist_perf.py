@@ -1,0 +1,128 @@
+"""Bootstrap replicates from an alignment: distance matrices on the device against numpy on the host.
+
+B = 1024 bootstrap replicates of random 4-state alignments at about 10 % divergence, n = 32, 64, 140 taxa, L = 1000 and
+10000 sites, once without and once with 2 % missing bytes.  For each shape:
+  (a) the product's route from a host alignment to host orders: fnn_alignment_distances_batch_device_f64 into a tensor on
+      the GPU, then fnn_canonical_order_batch_device_f64 on that tensor;
+  (b) what a user does without the distance call: the same B matrices with numpy in its best form - the 0/1 pair-by-site
+      matrix times counts^T as ONE float64 matmul (two with missing bytes), on the threads the machine gives -, then
+      fnn_canonical_order_batch_f64 through the host entry.
+Matrices and orders of (a) and (b) are compared, equal bitwise.  Prints one JSON line per shape: the kernel's time, the
+distance call's time, both routes and their ratio.  The condition: (a) faster than (b) at every shape.
+
+    python tools/dist_perf.py [--batch 1024] [--sizes 32,64,140] [--sites 1000,10000] [--missing 0,0.02] [--out FILE]
+                              [--only-a]
+
+--only-a runs route (a) alone (for a kernel trace of one shape); --out appends the JSON lines to FILE as well."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch  # first: torch's HIP runtime then serves the product's library too (as in bench.py)
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import fastneighbornet_amd as fa  # noqa: E402
+
+
+def alignment(n, L, seed, missing):
+    r = np.random.default_rng(seed)
+    base = r.integers(0, 4, L)
+    seq = np.where(r.random((n, L)) < 0.1, r.integers(0, 4, (n, L)), base[None, :])
+    seq = np.frombuffer(b"ACGT", dtype=np.uint8)[seq].copy()
+    if missing:
+        seq[r.random((n, L)) < missing] = 255
+    return seq
+
+
+def route_a(seq, counts):
+    t0 = time.perf_counter()
+    T, st = fa.alignment_distances_batch(seq, counts, out="torch")
+    t1 = time.perf_counter()
+    orders = fa.canonical_order_batch(T)
+    t2 = time.perf_counter()
+    return T, orders, st, t1 - t0, t2 - t0
+
+
+def numpy_matrices(seq, counts):
+    n, B = seq.shape[0], counts.shape[0]
+    iu, ju = np.triu_indices(n, 1)
+    w = counts.astype(np.float64).T                                   # L x B
+    si, sj = seq[iu], seq[ju]
+    if (seq == 255).any():
+        both = (si != 255) & (sj != 255)
+        valid = both.astype(np.float64) @ w                           # pairs x B, exact: integers below 2^53
+        mism = (both & (si != sj)).astype(np.float64) @ w
+    else:
+        mism = (si != sj).astype(np.float64) @ w
+        valid = np.broadcast_to(w.sum(axis=0)[None, :], mism.shape)
+    d = (mism / valid).T                                              # B x pairs
+    D = np.zeros((B, n, n))
+    D[:, iu, ju] = d
+    D[:, ju, iu] = d
+    return D
+
+
+def route_b(seq, counts):
+    t0 = time.perf_counter()
+    D = numpy_matrices(seq, counts)
+    t1 = time.perf_counter()
+    orders = fa.canonical_order_batch(D)
+    t2 = time.perf_counter()
+    return D, orders, t1 - t0, t2 - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--sizes", default="32,64,140")
+    ap.add_argument("--sites", default="1000,10000")
+    ap.add_argument("--missing", default="0,0.02")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--only-a", action="store_true")
+    args = ap.parse_args()
+    B = args.batch
+    # warm both routes: the runtime, the kernels' code objects, numpy's thread pool
+    s0 = alignment(8, 256, 1, 0.0)
+    c0 = fa.bootstrap_counts(256, 64, 1)
+    route_a(s0, c0)
+    route_b(s0, c0)
+    lines = []
+    for miss in [float(x) for x in args.missing.split(",")]:
+        for n in [int(x) for x in args.sizes.split(",")]:
+            for L in [int(x) for x in args.sites.split(",")]:
+                seq = alignment(n, L, 1000 + n + L, miss)
+                counts = fa.bootstrap_counts(L, B, 7)
+                best = None
+                for _ in range(2):   # (the better of two runs of each route)
+                    T, oa, st, ta_call, ta = route_a(seq, counts)
+                    if best is None or ta < best[0]:
+                        best = (ta, ta_call, st)
+                    Ta = T.cpu().numpy()
+                    del T
+                ta, ta_call, st = best
+                rec = {"n": n, "L": L, "B": B, "missing": miss, "digit_passes": st["digit_passes"], "has_missing": st["has_missing"],
+                       "chunks": st["chunks"], "t_kernel_ms": st["t_kernel_s"] * 1e3, "t_upload_ms": st["t_upload_s"] * 1e3,
+                       "t_call_ms": ta_call * 1e3, "t_route_a_ms": ta * 1e3, "out_bytes": B * n * n * 8}
+                if not args.only_a:
+                    tb_best = None
+                    for _ in range(2):
+                        Db, ob, tb_np, tb = route_b(seq, counts)
+                        if tb_best is None or tb < tb_best[0]:
+                            tb_best = (tb, tb_np)
+                    rec.update({"t_numpy_ms": tb_best[1] * 1e3, "t_route_b_ms": tb_best[0] * 1e3, "ratio_b_over_a": tb_best[0] / ta,
+                                "matrices_bitwise_equal": bool((Ta.view(np.int64) == Db.view(np.int64)).all()),
+                                "orders_equal": bool((oa == ob).all())})
+                line = json.dumps(rec)
+                print(line, flush=True)
+                lines.append(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
