@@ -259,8 +259,70 @@ def run_bootstrap_counts(a: Api, L: int, batch: int, seed: int) -> np.ndarray:
     return counts
 
 
+class FnnSupportStats(C.Structure):
+    _fields_ = [("n_problems", C.c_int64), ("n_records", C.c_int64), ("n_splits", C.c_int64),
+                ("words", C.c_int32), ("route", C.c_int32), ("hash_retries", C.c_int32), ("chunks", C.c_int32),
+                ("table_slots", C.c_int64), ("t_upload_s", C.c_double), ("t_kernel_s", C.c_double), ("t_total_s", C.c_double),
+                ("reserved", C.c_int64 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+SUPPORT_ROUTES = ("kernel", "host")
+_SUPPORT_ARGS = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(FnnSupportStats)]
+
+
+def bind_support(a: Api) -> Api:
+    """The split-support entry points of include/fastnn.h (the distinct splits of many problems, tallied) on `a`."""
+    a._fn("split_support_max_n", C.c_int32, [])
+    a._fn("split_support_min_work", C.c_int64, [])
+    a._fn("split_support_f64", C.c_int32, _SUPPORT_ARGS)
+    a._fn("split_support_device_f64", C.c_int32, _SUPPORT_ARGS)
+    a._fn("split_keys", C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+    return a
+
+
+def support_words(n: int) -> int:
+    return (n + 63) // 64
+
+
+def run_support(a: Api, n: int, batch: int, orders, weights, threshold: float, lead: int, capacity: int, device: int = 0,
+                on_device: bool = False, fill: int = 0):
+    """One split-support call on raw addresses (orders: host memory; weights: host memory, or device memory with on_device).
+    The output arrays hold `capacity` rows and are filled with `fill` bytes first.  Returns (table, S, stats): the table's
+    arrays keep all `capacity` rows; on failure FnnError carries them as `.table`."""
+    words = support_words(max(n, 1))
+    byte = np.uint8(fill & 0xFF)
+    table = {"keys": np.full((capacity, words * 8), byte, dtype=np.uint8).view(np.uint64).reshape(capacity, words),
+             "first_b": np.full((capacity, 8), byte, dtype=np.uint8).view(np.int64).reshape(capacity),
+             "first_k": np.full((capacity, 8), byte, dtype=np.uint8).view(np.int64).reshape(capacity),
+             "count": np.full((capacity, 8), byte, dtype=np.uint8).view(np.int64).reshape(capacity),
+             "weight_sum": np.full((capacity, 8), byte, dtype=np.uint8).view(np.float64).reshape(capacity)}
+    S = C.c_int64(-1)
+    st = FnnSupportStats()
+    fn = a.split_support_device_f64 if on_device else a.split_support_f64
+    rc = fn(n, batch, orders, weights, threshold, lead, device, *(table[k].ctypes.data for k in ("keys", "first_b", "first_k", "count", "weight_sum")),
+            capacity, C.addressof(S), C.byref(st))
+    try:
+        a.check(rc)
+    except FnnError as e:
+        e.table = table
+        raise
+    return table, S.value, st
+
+
+def run_split_keys(a: Api, n: int, order, ks) -> np.ndarray:
+    order = np.ascontiguousarray(order, dtype=np.int32)
+    ks = np.ascontiguousarray(ks, dtype=np.int64)
+    out = np.zeros((len(ks), support_words(max(n, 1))), dtype=np.uint64)
+    a.check(a.split_keys(n, order.ctypes.data, ks.ctypes.data, len(ks), out.ctypes.data))
+    return out
+
+
 _lp = C.POINTER(C.c_int64)
-_RAGGED_ARGS = [C.c_void_p, _lp, _ip, _lp, C.c_int64, C.POINTER(FnnOpts), _ip, C.c_void_p, _ip, C.POINTER(FnnBatchStats)]
+_RAGGED_ARGS =[C.c_void_p, _lp, _ip, _lp, C.c_int64, C.POINTER(FnnOpts), _ip, C.c_void_p, _ip, C.POINTER(FnnBatchStats)]
 _SPLITS_RAGGED_ARGS = [C.c_void_p, _lp, _ip, _lp, C.c_int64, _ip, C.c_int32, _dp, C.POINTER(FnnSwStats), C.POINTER(FnnSwBatchStats)]
 
 

@@ -13,11 +13,12 @@ SRC_SPLITS = os.path.join(HERE, "csrc", "fnn_splits.hip")  # circular split weig
 SRC_BATCH = os.path.join(HERE, "csrc", "fnn_batch.hip")    # many small problems, one workgroup each
 SRC_SPLITS_BATCH = os.path.join(HERE, "csrc", "fnn_splits_batch.hip")  # split weights of many small problems
 SRC_DIST = os.path.join(HERE, "csrc", "fnn_dist.hip")    # distance matrices of bootstrap replicates from an alignment
-SOURCES = (SRC, SRC_SPLITS, SRC_BATCH, SRC_SPLITS_BATCH, SRC_DIST)
-DEPS = [SRC, SRC_SPLITS, SRC_BATCH, SRC_SPLITS_BATCH, SRC_DIST, os.path.join(HERE, "csrc", "fnn_core.h"), os.path.join(HERE, "csrc", "fnn_engine.h"),
+SRC_SUPPORT = os.path.join(HERE, "csrc", "fnn_support.hip")  # split support: the distinct splits of many problems, tallied
+SOURCES = (SRC, SRC_SPLITS, SRC_BATCH, SRC_SPLITS_BATCH, SRC_DIST, SRC_SUPPORT)
+DEPS = [SRC, SRC_SPLITS, SRC_BATCH, SRC_SPLITS_BATCH, SRC_DIST, SRC_SUPPORT, os.path.join(HERE, "csrc", "fnn_core.h"), os.path.join(HERE, "csrc", "fnn_engine.h"),
         os.path.join(HERE, "csrc", "fnn_chain.h"), os.path.join(HERE, "csrc", "fnn_small.h"), os.path.join(HERE, "csrc", "fnn_small_global.h"),
         os.path.join(HERE, "csrc", "fnn_small_splits.h"), os.path.join(HERE, "csrc", "fnn_ragged_hip.h"), os.path.join(HERE, "csrc", "fnn_dist.h"),
-        os.path.join(ROOT, "include", "fastnn.h")]
+        os.path.join(HERE, "csrc", "fnn_support.h"), os.path.join(ROOT, "include", "fastnn.h")]
 
 # -ffp-contract=off: one rounding per fp64 operation on host and device (parity with Java doubles)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
@@ -100,7 +101,8 @@ def build_host(force: bool = False) -> None:
 OBJ_DIR = os.path.join(HERE, "csrc", "build")  # objects are kept (git-ignored): a source is recompiled only when it or a header changed
 HEADERS = [os.path.join(HERE, "csrc", "fnn_core.h"), os.path.join(HERE, "csrc", "fnn_engine.h"), os.path.join(HERE, "csrc", "fnn_chain.h"),
            os.path.join(HERE, "csrc", "fnn_small.h"), os.path.join(HERE, "csrc", "fnn_small_global.h"), os.path.join(HERE, "csrc", "fnn_small_splits.h"),
-           os.path.join(HERE, "csrc", "fnn_ragged_hip.h"), os.path.join(HERE, "csrc", "fnn_dist.h"), os.path.join(ROOT, "include", "fastnn.h")]
+           os.path.join(HERE, "csrc", "fnn_ragged_hip.h"), os.path.join(HERE, "csrc", "fnn_dist.h"), os.path.join(HERE, "csrc", "fnn_support.h"),
+           os.path.join(ROOT, "include", "fastnn.h")]
 
 
 def toolchain_stamp() -> str:

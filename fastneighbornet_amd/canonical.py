@@ -403,3 +403,82 @@ def bootstrap(seq, B: int, seed: int, weights: bool = True, device: int = 0):
     if weights:
         W, stats["splits"] = split_weights_batch(D, orders, device=device)
     return orders, W, stats
+
+
+# ---- split support: the distinct splits of many problems, tallied
+
+def split_support(orders, W, threshold: float = 1e-6, lead: int = 0, device: int = 0):
+    """The table of the distinct splits of B problems over one taxon set (`fnn_split_support_f64`): `orders` (B, n + 1) as
+    `canonical_order_batch` returns them, `W` (B, n(n-1)/2) as `split_weights_batch` returns it - a numpy array (host entry) or
+    a torch.float64 tensor on the GPU (device entry, after torch.cuda.synchronize()).  A weight counts when it is above
+    `threshold`; the first `lead` problems define rows but are not tallied (lead=1 with the original data as problem 0: the
+    rows with first_b == 0 are the reference network's splits, each with its bootstrap support).  Returns (table, stats):
+    table is a dict of numpy arrays in order of first appearance - keys (S, words) uint64 (bit t - 1 of the key = taxon t, on
+    the side without taxon 1; `key_taxa`), first_b, first_k, count, weight_sum (the sum over the counted problems in
+    ascending b, one rounding per addition) and support = count / (B - lead); stats holds the fnn_support_stats fields and
+    "method" ("kernel" or "host")."""
+    from . import api
+    a = api()
+    if hasattr(orders, "cpu") and hasattr(orders, "numpy"):
+        orders = orders.cpu().numpy()
+    orders = np.ascontiguousarray(orders, dtype=np.int32)
+    if orders.ndim != 2 or orders.shape[1] < 3:
+        raise ValueError("orders must have shape (B, n + 1) with n >= 2")
+    B, n = orders.shape[0], orders.shape[1] - 1
+    K = n * (n - 1) // 2
+    on_device = False
+    if hasattr(W, "is_cuda") and hasattr(W, "data_ptr"):  # a torch tensor
+        import torch
+        if W.is_cuda:
+            if W.dtype != torch.float64:
+                raise TypeError("a tensor on the GPU must be torch.float64")
+            W = W.contiguous()
+            torch.cuda.synchronize(W.device)  # the call is not ordered against the stream that produced W
+            if W.device.index is not None:
+                device = W.device.index
+            on_device, ptr = True, W.data_ptr()
+        else:
+            W = W.numpy()
+    if not on_device:
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        ptr = W.ctypes.data
+    if tuple(W.shape) != (B, K):
+        raise ValueError(f"W must have shape ({B}, {K})")
+    # room for an upper bound of S: the counting records (a NaN threshold is the call's to refuse)
+    cap = int((W > float(threshold)).sum()) if B else 0
+    table, S, st = _capi.run_support(a, n, B, orders.ctypes.data, ptr if B else None, float(threshold), int(lead), cap, device=device,
+                                     on_device=on_device)
+    table = {k: v[:S].copy() for k, v in table.items()}
+    table["support"] = table["count"] / float(B - lead) if B > lead else np.zeros(S, dtype=np.float64)
+    out = st.as_dict()
+    out["method"] = _capi.SUPPORT_ROUTES[st.route]
+    return table, out
+
+
+def split_keys(order, ks) -> np.ndarray:
+    """The keys (len(ks), words) uint64 of the splits `ks` (indices k of `split_weights`) of one ordering (`fnn_split_keys`:
+    host only), as the rows of `split_support`'s table hold them."""
+    from . import api
+    order = np.ascontiguousarray(order, dtype=np.int32)
+    return _capi.run_split_keys(api(), len(order) - 1, order, ks)
+
+
+def key_taxa(key) -> list:
+    """The sorted 1-based taxon ids of one key (a row of table["keys"])."""
+    return [64 * w + b + 1 for w, x in enumerate(np.asarray(key, dtype=np.uint64).tolist()) for b in range(64) if (x >> b) & 1]
+
+
+def bootstrap_support(seq, B: int, seed: int, threshold: float = 1e-6, device: int = 0):
+    """A bootstrap run with its result: the original alignment as problem 0 (every site once) in front of the B replicates of
+    `bootstrap_counts(L, B, seed)`, through distances, orders and split weights as `bootstrap` runs them, then
+    `split_support(..., lead=1)`.  Returns (order, weights, table, stats): the order and the weights of the original data, the
+    table - its rows with first_b == 0 are the original network's splits above `threshold` in ascending k, `support` the share
+    of the B replicates that hold each - and stats = {"distances", "splits", "support"}."""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    L = seq.shape[1]
+    counts = np.concatenate([np.ones((1, L), dtype=np.uint16), bootstrap_counts(L, B, seed)])
+    D, dst = alignment_distances_batch(seq, counts, device=device, out="torch")
+    orders = canonical_order_batch(D, device=device)
+    W, sst = split_weights_batch(D, orders, device=device)
+    table, ust = split_support(orders, W, threshold=threshold, lead=1, device=device)
+    return orders[0], W[0], table, {"distances": dst, "splits": sst, "support": ust}

@@ -524,6 +524,66 @@ int32_t fnn_alignment_distances_batch_device_f64(const uint8_t* seq, int32_t n, 
  * dense.  A count above 65535 is FNN_EINVAL. */
 int32_t fnn_bootstrap_counts(int64_t L, int64_t batch, uint64_t seed, uint16_t* counts_out /* batch x L */);
 
+/* ---- split support: how often each split occurs among many problems ---------
+ * The last stage of a bootstrap run: the orderings and split weights of `batch` problems over ONE taxon set go in, one
+ * table of the distinct splits comes out, each with the number of problems that hold it and the sum of its weights there.
+ * orderings: batch x (n + 1), host memory, row b as the order batch returns it ([1..n] a permutation of 1..n).  weights:
+ * batch x n(n-1)/2, dense, row b in the index order of fnn_split_weights_f64 (k <-> (i, j), 0 <= i < j <= n - 1, row-major;
+ * split k of problem b = taxa orderings[b][i+1 .. j] against the rest); host memory, or device memory for the _device_
+ * variant, which is not ordered against the stream that produced the weights: synchronise the producer first.
+ * A record (b, k) COUNTS iff weights[b][k] > threshold in IEEE arithmetic (a NaN never counts; the reference keeps
+ * x > 1e-6).  Its KEY is the split as an n-bit set, bit t - 1 for taxon t, of the side that does NOT contain taxon 1, in
+ * words = ceil(n / 64) uint64_t, word 0 = taxa 1 ... 64, unused high bits zero.  Within one problem distinct k have
+ * distinct keys, so a problem holds a split at most once.
+ * The table has S rows, one per distinct key among the counting records of ALL problems, in order of first appearance
+ * (ascending (b, k) of the lowest counting record with that key): keys_out[s * words ...], first_b_out[s], first_k_out[s],
+ * counts_out[s] = the number of problems b >= lead that hold the split, weight_sum_out[s] = ((0 + w_b1) + w_b2) + ... over
+ * exactly those problems in ascending b, fp64, one rounding per addition (the sequential sum).  The first `lead` problems
+ * define rows - which therefore come first - but are not tallied: with lead = 1 and the original data as problem 0 the rows
+ * with first_b == 0 are the reference network's splits in its own order, each with its bootstrap support; rows that only
+ * lead problems hold have count 0 and sum +0.0.  lead = 0: the plain consensus tally.
+ * *count_out = S.  When S > capacity the first `capacity` rows are filled and the status is still FNN_OK (call again with
+ * more room); with capacity == 0 the five output arrays may be NULL.  Outputs are written only when the whole call has
+ * succeeded.  Two calls on the same input give the same bytes, whatever the chunking or the route.
+ * FNN_EINVAL, all before any device use: a NULL array, n < 2, n > fnn_split_support_max_n(), batch < 0, lead < 0 or
+ * lead > batch, a NaN threshold, capacity < 0, a row of `orderings` that is not a permutation of 1..n (fnn_last_error()
+ * names the lowest such b).  batch == 0 is FNN_OK with S = 0.  The call runs on `device` and leaves the caller's current
+ * HIP device as it found it.
+ * Routes (stats->route): FNN_SUPPORT_ROUTE_KERNEL - per chunk of problems (at most 2 GiB of weights; FNN_BATCH_CHUNK=<problems>
+ * overrides, for tests; tallies and sums carry across chunks) a sequence of kernels: count the records, emit them in
+ * (b, k) order with their keys into a hash table of 63-bit key hashes, compare every record's full key with the key of
+ * its slot's first record, number the rows by a scan, scatter the tallied records into per-row segments, put each segment
+ * in ascending b by rank and add it up in order.  No float atomics; kernel boundaries are the only synchronisation.  Two
+ * distinct keys with one hash are detected, never resolved silently: the chunk is repeated with another hash seed
+ * (hash_retries), and after 3 repeats the call takes FNN_SUPPORT_ROUTE_HOST - the same table from an ordered map in plain
+ * C++ on the host (the device variant downloads the weights for it) -, which also serves calls below
+ * fnn_split_support_min_work() in batch * n * n (the measured crossover).  For tests:
+ * FNN_SUPPORT_ROUTE=kernel|host overrides the choice; FNN_SUPPORT_HASH_BITS=<1..64> keeps only that many bits of the hash,
+ * so that distinct keys collide, the repeats run out and the host route takes over. */
+enum { FNN_SUPPORT_ROUTE_KERNEL = 0, FNN_SUPPORT_ROUTE_HOST = 1 };
+typedef struct fnn_support_stats {
+    int64_t n_problems, n_records, n_splits;   /* n_records: counting records; n_splits: S */
+    int32_t words, route, hash_retries, chunks;
+    int64_t table_slots;                       /* hash slots of the largest chunk (a power of two >= 2 x its records) */
+    double  t_upload_s, t_kernel_s, t_total_s;
+    int64_t reserved[4];
+} fnn_support_stats;
+int32_t fnn_split_support_max_n(void);     /* 1024: 16 words; the limit of the batched order kernels */
+int64_t fnn_split_support_min_work(void);  /* the smallest batch * n * n that takes the kernels by default */
+int32_t fnn_split_support_f64(int32_t n, int64_t batch, const int32_t* orderings /* batch x (n+1) */,
+                              const double* weights /* batch x n(n-1)/2 */, double threshold, int64_t lead, int32_t device,
+                              uint64_t* keys_out /* capacity x words */, int64_t* first_b_out, int64_t* first_k_out,
+                              int64_t* counts_out, double* weight_sum_out, int64_t capacity, int64_t* count_out,
+                              fnn_support_stats* stats /* may be NULL */);
+int32_t fnn_split_support_device_f64(int32_t n, int64_t batch, const int32_t* orderings, const double* d_weights,
+                                     double threshold, int64_t lead, int32_t device, uint64_t* keys_out, int64_t* first_b_out,
+                                     int64_t* first_k_out, int64_t* counts_out, double* weight_sum_out, int64_t capacity,
+                                     int64_t* count_out, fnn_support_stats* stats);
+/* Host only, no device: the keys of the splits k[0 .. count) of one ordering (n + 1 entries), keys_out: count x
+ * ceil(n / 64) words, as defined above.  FNN_EINVAL: n < 2, count < 0, a NULL array with count > 0, an ordering that is
+ * not a permutation, a k outside 0 ... n(n-1)/2 - 1. */
+int32_t fnn_split_keys(int32_t n, const int32_t* ordering, const int64_t* k, int64_t count, uint64_t* keys_out);
+
 /* Diagnostic: the exact block-parallel evaluation of the sequential fp64 sum
  * (((0 + b[0]) + b[1]) + ...) used for ComputeRx / u.Sx (NetMakerOriginal.java:551-560,
  * :532), run on an arbitrary host buffer.  ept = addends per thread (32, fixed by the

@@ -2,7 +2,7 @@
 hipcc -Rpass-analysis=kernel-resource-usage, as a markdown table.   usage: tools/isa_resources.py [out.md]"""
 import hashlib, json, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = [os.path.join(ROOT, "fastneighbornet_amd", "csrc", f) for f in ("fnn_hip.hip", "fnn_splits.hip", "fnn_dist.hip")]
+SRC = [os.path.join(ROOT, "fastneighbornet_amd", "csrc", f) for f in ("fnn_hip.hip", "fnn_splits.hip", "fnn_dist.hip", "fnn_support.hip")]
 
 
 def demangle(names):
