@@ -18,7 +18,7 @@ SOURCES = (SRC, SRC_SPLITS, SRC_BATCH, SRC_SPLITS_BATCH, SRC_DIST, SRC_SUPPORT)
 DEPS = [SRC, SRC_SPLITS, SRC_BATCH, SRC_SPLITS_BATCH, SRC_DIST, SRC_SUPPORT, os.path.join(HERE, "csrc", "fnn_core.h"), os.path.join(HERE, "csrc", "fnn_engine.h"),
         os.path.join(HERE, "csrc", "fnn_chain.h"), os.path.join(HERE, "csrc", "fnn_small.h"), os.path.join(HERE, "csrc", "fnn_small_global.h"),
         os.path.join(HERE, "csrc", "fnn_small_splits.h"), os.path.join(HERE, "csrc", "fnn_ragged_hip.h"), os.path.join(HERE, "csrc", "fnn_dist.h"),
-        os.path.join(HERE, "csrc", "fnn_support.h"), os.path.join(ROOT, "include", "fastnn.h")]
+        os.path.join(HERE, "csrc", "fnn_support.h"), os.path.join(HERE, "csrc", "fnn_splits_plan.h"), os.path.join(ROOT, "include", "fastnn.h")]
 
 # -ffp-contract=off: one rounding per fp64 operation on host and device (parity with Java doubles)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
@@ -102,7 +102,7 @@ OBJ_DIR = os.path.join(HERE, "csrc", "build")  # objects are kept (git-ignored):
 HEADERS = [os.path.join(HERE, "csrc", "fnn_core.h"), os.path.join(HERE, "csrc", "fnn_engine.h"), os.path.join(HERE, "csrc", "fnn_chain.h"),
            os.path.join(HERE, "csrc", "fnn_small.h"), os.path.join(HERE, "csrc", "fnn_small_global.h"), os.path.join(HERE, "csrc", "fnn_small_splits.h"),
            os.path.join(HERE, "csrc", "fnn_ragged_hip.h"), os.path.join(HERE, "csrc", "fnn_dist.h"), os.path.join(HERE, "csrc", "fnn_support.h"),
-           os.path.join(ROOT, "include", "fastnn.h")]
+           os.path.join(HERE, "csrc", "fnn_splits_plan.h"), os.path.join(ROOT, "include", "fastnn.h")]
 
 
 def toolchain_stamp() -> str:

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "fnn_engine.h"  // fnn::fail / the thread-local error message shared with fnn_hip.hip
+#include "fnn_splits_plan.h"  // the switches, the capacity plan and the block method's pure host steps
 
 namespace fnnsw {
 
@@ -451,12 +452,7 @@ struct TriStore {
         const int64_t q = col / pw, q0 = q * pw;
         return base + off(q) + (col - q0) * ld(q) + (row - q0);
     }
-    static int64_t elems(int64_t cap, int64_t pw) {
-        int64_t tot = 0;
-        for (int64_t q0 = 0; q0 < cap; q0 += pw) tot += std::min(pw, cap - q0) * (cap - q0);
-        return tot;
-    }
-};
+};  // (its size in doubles: tri_elems of fnn_splits_plan.h)
 // Y[:, q] = W[0:f, list[q]] for a panel-stored factor (rows above the column's panel are zeros)
 __global__ __launch_bounds__(T) void k_gather_cols_tri(TriStore W, int64_t f, const int32_t* list, int64_t cnt, double* Y, int64_t ldy) {
     const int64_t r = (int64_t)blockIdx.x * T + threadIdx.x;
@@ -781,34 +777,33 @@ struct Solver {
     void dot_partials(const double* a, const double* b, const double* skip) {
         hipLaunchKernelGGL(k_reduce<RD_DOT>, gred, dim3(T), 0, s, a, b, act, 0.0, n, ld, partial, bpartial, skip);
     }
+    // the per-workgroup partials of the reduction just launched, on the host (the three folds below are their callers' own)
+    template <class Tp>
+    std::vector<Tp> fetch_partials(const Tp* dev) {
+        std::vector<Tp> h((size_t)gred.x * gred.y);
+        (void)hipMemcpyAsync(h.data(), dev, sizeof(Tp) * h.size(), hipMemcpyDeviceToHost, s);
+        (void)hipStreamSynchronize(s);
+        return h;
+    }
     template <int RD>
     double reduce_sum(const double* a, const double* b, double s0 = 0.0) {
         hipLaunchKernelGGL(k_reduce<RD>, gred, dim3(T), 0, s, a, b, act, s0, n, ld, partial, bpartial, (const double*)nullptr);
-        std::vector<double> h((size_t)gred.x * gred.y);
-        (void)hipMemcpyAsync(h.data(), partial, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s);
-        (void)hipStreamSynchronize(s);
         double acc = 0.0;
-        for (double v : h) acc += v;
+        for (double v : fetch_partials(partial)) acc += v;
         return acc;
     }
     template <int RD>
     Best reduce_best(const double* a, const double* b) {
         hipLaunchKernelGGL(k_reduce<RD>, gred, dim3(T), 0, s, a, b, act, 0.0, n, ld, partial, bpartial, (const double*)nullptr);
-        std::vector<Best> h((size_t)gred.x * gred.y);
-        (void)hipMemcpyAsync(h.data(), bpartial, sizeof(Best) * h.size(), hipMemcpyDeviceToHost, s);
-        (void)hipStreamSynchronize(s);
         Best best{INFINITY, INT64_MAX};
-        for (const Best& o : h)
+        for (const Best& o : fetch_partials(bpartial))
             if (o.v < best.v || (o.v == best.v && o.k < best.k)) best = o;
         return best;
     }
     double min_negative(const double* a) {
         hipLaunchKernelGGL(k_minneg, gred, dim3(T), 0, s, a, n, ld, partial);
-        std::vector<double> h((size_t)gred.x * gred.y);
-        (void)hipMemcpyAsync(h.data(), partial, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s);
-        (void)hipStreamSynchronize(s);
         double mn = 0.0;
-        for (double v : h) if (v < mn) mn = v;
+        for (double v : fetch_partials(partial)) if (v < mn) mn = v;
         return mn;
     }
 
@@ -874,24 +869,11 @@ struct Solver {
         return true;
     }
 
-    // ------------------------------------------------------------ block active-set method (see the comment above h_entry)
+    // ------------------------------------------------------------ what the block active-set method (BlockMethod, below) leaves here
+    // A call may make several attempts at growing capacities, each a fresh BlockMethod: the counters, the timers, gemm_flops and
+    // f_peak ACCUMULATE over the attempts of one call; giveup, capacity and t_alloc_s are the last attempt's.
     int64_t st_lh_steps = 0, st_lh_refactor = 0, st_solves = 0, st_adds = 0, st_dels = 0, st_rejects = 0, st_ratio_steps = 0, st_screened = 0, st_dead_wanting = 0, st_revived = 0, st_dels_new = 0;
     double t_ops = 0, t_sel = 0, t_append = 0, t_solve = 0, t_dead = 0, t_refactor = 0;  // host wall clock per phase (FNN_SW_LOG)
-    struct Blk {
-        rocblas_handle bh = nullptr;
-        int64_t cap = 0, kmax = 0, rcap = 0, f = 0, r = 0, pw = 0;
-        TriStore Ws{nullptr, 0, 0}, LCs{nullptr, 0, 0};  // the factor (column panels) and the Gram factor (one panel = square)
-        double *W = nullptr, *B = nullptr, *Tb = nullptr, *X = nullptr, *S = nullptr, *S0 = nullptr, *Li = nullptr, *tmp2 = nullptr;
-        double *Y = nullptr, *CR = nullptr, *LC = nullptr, *CRb = nullptr, *CRw = nullptr;
-        double *z = nullptr, *v = nullptr, *xs = nullptr, *cK = nullptr, *lam = nullptr, *gF = nullptr;
-        int2 *dF = nullptr, *dscr = nullptr;
-        int32_t *dlist = nullptr, *dlist2 = nullptr;
-        double *wk = nullptr, *sk1 = nullptr, *sk2 = nullptr;
-        int64_t* dinfo = nullptr;
-        double* ckey = nullptr; double* ckey2 = nullptr; int64_t* cidx = nullptr; int64_t* cidx2 = nullptr;
-        unsigned long long* ccount = nullptr; void* sort_tmp = nullptr; size_t sort_bytes = 0; int64_t ccap = 0;
-    } bk;
-    bool blas_ok = true;
     double gemm_flops = 0.0;
     int64_t cap_want = 0;        // > 0: the factor's capacity for this attempt (a retry after FNN_SW_GIVEUP_CAPACITY), else the default for n
     int giveup = 0;              // FNN_SW_GIVEUP_* of the block method
@@ -899,106 +881,6 @@ struct Solver {
     double final_tol_rel = 0.0, t_alloc_s = 0.0;
     int64_t n_set_aside = 0, f_peak = 0, capacity = 0;
     bool have_atwd = false;
-    static int64_t up64(int64_t v) { return (v + 63) / 64 * 64; }
-    static dim3 g1(int64_t c) { return dim3((unsigned)((c + T - 1) / T)); }
-    static dim3 g2(int64_t rows, int64_t cols) { return dim3((unsigned)((rows + T - 1) / T), (unsigned)std::max<int64_t>(1, std::min<int64_t>(cols, 16384))); }
-    void gemm(rocblas_operation ta, rocblas_operation tb, int64_t m, int64_t nn, int64_t k, double alpha, const double* A, int64_t lda, const double* Bm,
-              int64_t ldb, double beta, double* Cm, int64_t ldc) {
-        if (m <= 0 || nn <= 0) return;
-        gemm_flops += 2.0 * (double)m * (double)nn * (double)k;
-        if (rocblas_dgemm_64(bk.bh, ta, tb, m, nn, k, &alpha, A, lda, Bm, ldb, &beta, Cm, ldc) != rocblas_status_success) blas_ok = false;
-    }
-    void gemv(rocblas_operation ta, int64_t m, int64_t nn, double alpha, const double* A, int64_t lda, const double* xv, double beta, double* yv) {
-        if (m <= 0 || nn <= 0) return;
-        if (rocblas_dgemv_64(bk.bh, ta, m, nn, &alpha, A, lda, xv, 1, &beta, yv, 1) != rocblas_status_success) blas_ok = false;
-    }
-    // panels that skip the zero half of a lower-triangular operand
-    // out (f x k, ldo) = Wl (f x f lower triangular, panel-stored) * Bm (f x k, ldb): panel by panel, each adding into the rows it reaches
-    void tri_times(const TriStore& Wl, int64_t f, const double* Bm, int64_t ldb, int64_t k, double* out, int64_t ldo) {
-        const int64_t chunks = (f + SK_CHUNK - 1) / SK_CHUNK;
-        if (k <= SMALLK && chunks * k * f <= bk.cap * bk.kmax) {  // a few columns: one pass over Wl (partial sums per column chunk in bk.X)
-            (void)hipMemsetAsync(bk.X, 0, sizeof(double) * (size_t)(chunks * k * f), s);
-            hipLaunchKernelGGL(k_tri_times_small, dim3((unsigned)((f + T - 1) / T), (unsigned)chunks), dim3(T), 0, s, Wl, f, Bm, ldb, (int)k, bk.X);
-            hipLaunchKernelGGL(k_sum_parts, g2(f, k), dim3(T), 0, s, bk.X, k * f, (int)chunks, f, k, 1.0, 0.0, out, ldo);
-            return;
-        }
-        // column chunks of about f / 8 (never across a storage panel): the zero triangle above a chunk's diagonal is the only waste
-        const int64_t gw = std::min(Wl.pw, std::max<int64_t>(1024, up64((f + 7) / 8)));
-        for (int64_t c0 = 0; c0 < f;) {
-            const int64_t q = c0 / Wl.pw, c1 = std::min({c0 + gw, (q + 1) * Wl.pw, f});
-            gemm(rocblas_operation_none, rocblas_operation_none, f - c0, k, c1 - c0, 1.0, Wl.at(c0, c0), Wl.ld(q), Bm + c0, ldb, c0 == 0 ? 0.0 : 1.0, out + c0, ldo);
-            c0 = c1;
-        }
-    }
-    // out (k x f, ldo) = Tm^T (Tm: f x k, ldt) * Wl (f x f lower triangular, panel-stored)
-    void t_times_tri(const double* Tm, int64_t ldt, int64_t k, const TriStore& Wl, int64_t f, double* out, int64_t ldo) {
-        if (k <= SMALLK) {
-            hipLaunchKernelGGL(k_t_times_tri_small, dim3((unsigned)f), dim3(T), 0, s, Tm, ldt, (int)k, Wl, f, out, ldo);
-            return;
-        }
-        const int64_t gw = std::min(Wl.pw, std::max<int64_t>(1024, up64((f + 7) / 8)));
-        for (int64_t c0 = 0; c0 < f;) {
-            const int64_t q = c0 / Wl.pw, c1 = std::min({c0 + gw, (q + 1) * Wl.pw, f});
-            gemm(rocblas_operation_transpose, rocblas_operation_none, k, c1 - c0, f - c0, 1.0, Tm + c0, ldt, Wl.at(c0, c0), Wl.ld(q), 0.0, out + c0 * ldo, ldo);
-            c0 = c1;
-        }
-    }
-    // C (m x nn) = beta C + alpha A^T B with a long inner dimension kk (A: kk x m, B: kk x nn): rocBLAS has no split-K form of
-    // this shape (3 TF/s); here the inner dimension is cut into slices that run as one strided-batched GEMM into partial
-    // products (workspace bk.X), added up in slice order
-    void tn_splitk(int64_t m, int64_t nn, int64_t kk, double alpha, const double* A, int64_t lda, const double* Bm, int64_t ldb, double beta, double* Cm,
-                   int64_t ldc) {
-        if (m <= 0 || nn <= 0) return;
-        const int64_t room = (bk.cap * bk.kmax) / std::max<int64_t>(m * nn, 1);
-        int64_t parts = std::min<int64_t>({room, (int64_t)32, (kk + 1023) / 1024});
-        if (parts < 2 || m * nn > (int64_t)1 << 26) {
-            gemm(rocblas_operation_transpose, rocblas_operation_none, m, nn, kk, alpha, A, lda, Bm, ldb, beta, Cm, ldc);
-            return;
-        }
-        const int64_t slice = kk / parts, rest = kk - slice * parts;  // `parts` equal slices, the remainder as one more
-        const double one = 1.0, zero = 0.0;
-        if (rocblas_dgemm_strided_batched_64(bk.bh, rocblas_operation_transpose, rocblas_operation_none, m, nn, slice, &one, A, lda, slice, Bm, ldb, slice, &zero,
-                                             bk.X, m, m * nn, parts) != rocblas_status_success) blas_ok = false;
-        int np = (int)parts;
-        if (rest > 0 && parts < room) {
-            gemm(rocblas_operation_transpose, rocblas_operation_none, m, nn, rest, 1.0, A + slice * parts, lda, Bm + slice * parts, ldb, 0.0, bk.X + parts * m * nn, m);
-            np++;
-        } else if (rest > 0) {
-            gemm(rocblas_operation_transpose, rocblas_operation_none, m, nn, rest, 1.0, A + slice * parts, lda, Bm + slice * parts, ldb, 1.0, bk.X + (parts - 1) * m * nn, m);
-        }
-        hipLaunchKernelGGL(k_sum_parts, g2(m, nn), dim3(T), 0, s, bk.X, m * nn, np, m, nn, alpha, beta, Cm, ldc);
-    }
-    // Li = inverse of the Cholesky factor of S (m x m, lower triangle read, destroyed), zeros above the diagonal: recursive halves,
-    // GEMMs and the in-LDS kernel for blocks of <= 64.  Everything is enqueued; a block that is not positive definite leaves the
-    // 1-based position of its first bad pivot in *bk.dinfo (read it with invchol_info() after the call).
-    void invchol_rec(double* S, int64_t lds, double* Li, int64_t ldl, int64_t m, int64_t off) {
-        if (m <= TRI_NB) {
-            hipLaunchKernelGGL(k_invchol_small, dim3(1), dim3(TRI_NB), 0, s, S, lds, Li, ldl, (int)m, (long long)off, (long long*)bk.dinfo);
-            return;
-        }
-        const int64_t m1 = std::min(m - 1, up64((m + 1) / 2)), m2 = m - m1;
-        double *S21 = S + m1, *S22 = S + m1 + m1 * lds, *Li21 = Li + m1, *Li22 = Li + m1 + m1 * ldl;
-        double *t1 = bk.tmp2, *t2 = bk.tmp2 + m2 * m1;
-        invchol_rec(S, lds, Li, ldl, m1, off);
-        gemm(rocblas_operation_none, rocblas_operation_transpose, m2, m1, m1, 1.0, S21, lds, Li, ldl, 0.0, t1, m2);           // L21 = S21 Li11^T
-        const double mone = -1.0, one = 1.0;
-        if (rocblas_dsyrk_64(bk.bh, rocblas_fill_lower, rocblas_operation_none, m2, m1, &mone, t1, m2, &one, S22, lds) != rocblas_status_success) blas_ok = false;
-        gemm(rocblas_operation_none, rocblas_operation_none, m2, m1, m1, 1.0, t1, m2, Li, ldl, 0.0, t2, m2);                    // L21 Li11
-        invchol_rec(S22, lds, Li22, ldl, m2, off + m1);
-        gemm(rocblas_operation_none, rocblas_operation_none, m2, m1, m2, -1.0, Li22, ldl, t2, m2, 0.0, Li21, ldl);              // Li21 = -Li22 L21 Li11
-        hipLaunchKernelGGL(k_fill2d, g2(m1, m2), dim3(T), 0, s, Li + m1 * ldl, ldl, m1, m2, 0.0);
-    }
-    int64_t invchol(double* S, int64_t lds, double* Li, int64_t ldl, int64_t m) {  // 0, or the 1-based position of the first pivot that is not positive
-        if (m <= 0) return 0;
-        const int64_t big = INT64_MAX;
-        (void)hipMemcpyAsync(bk.dinfo, &big, sizeof(big), hipMemcpyHostToDevice, s);
-        (void)hipStreamSynchronize(s);
-        invchol_rec(S, lds, Li, ldl, m, 0);
-        int64_t info = 0;
-        (void)hipMemcpyAsync(&info, bk.dinfo, sizeof(info), hipMemcpyDeviceToHost, s);
-        (void)hipStreamSynchronize(s);
-        return info == INT64_MAX ? 0 : info;
-    }
     double wall() { (void)hipStreamSynchronize(s); return fnn::now_s(); }
     std::map<std::string, double> tsub;  // finer split of the phases (FNN_SW_LOG)
     double t_lap = 0.0;
@@ -1010,137 +892,281 @@ struct Solver {
         t_lap = t;
     }
 
-    bool block_active_set() {
-        const bool log = std::getenv("FNN_SW_LOG") != nullptr;
-        lap_on = log;
-        auto envd = [](const char* k, double dflt) { const char* e = std::getenv(k); return e ? std::atof(e) : dflt; };
-        const double kfrac = envd("FNN_SW_KFRAC", 0.20);
-        double rfrac = envd("FNN_SW_RFRAC", 0.15);
-        const int rad = (int)envd("FNN_SW_NMS", 3);
-        const int64_t N = (int64_t)n * (n - 1) / 2;
-        Blk& b = bk;
-        b = Blk{};  // (a retry with a larger capacity starts from nothing)
-        giveup = 0; giveup_text = ""; blas_ok = true; ok = true;
-        block_mark = allocs.size();
-        // Capacity of the factor (splits that are in + the departed ones still inside + the entering block): random distances end
-        // with ~2.4 n positive splits, tree-like ones with more (tree + 5 % noise: 3.8 n) - as many as device memory allows, up
-        // to 6 n: the factor takes cap^2 doubles, the block buffers, the departed columns and their Gram matrices 0.61 cap^2 more.
-        auto sized = [&](double factor, int kdiv, int rdiv) {
-            b.cap = up64(std::min<int64_t>(N, std::max<int64_t>({(int64_t)(factor * n) + 1024, std::min<int64_t>(8 * (int64_t)n + 64, 20000), 512})));
-            if (cap_want > 0) b.cap = up64(std::min<int64_t>(N, cap_want));
-            b.kmax = std::min<int64_t>({b.cap, std::max<int64_t>(64, up64(b.cap / kdiv)), (int64_t)8192});  // (a block costs 4 k^2 f beside its 4 k f^2: keep k / f small)
-            b.rcap = std::min<int64_t>(b.cap, up64(b.cap / rdiv) + 64);
-            b.pw = std::max<int64_t>(1024, up64(b.cap / 8));
-            if (const char* e = std::getenv("FNN_SW_PANEL")) { const int64_t v = std::atoll(e); if (v >= 64) b.pw = up64(v); }
-            return 8.0 * ((double)TriStore::elems(b.cap, b.pw) + 3.0 * (double)b.cap * b.kmax + (double)b.cap * b.rcap + 4.0 * (double)b.rcap * b.rcap + 3.0 * (double)b.kmax * b.kmax +
-                          0.5 * (double)std::max(b.rcap, b.kmax) * std::max(b.rcap, b.kmax)) + 64.0 * (double)b.cap + 48.0 * (double)std::max<int64_t>(1 << 16, N / 16 + 1024);
-        };
-        size_t free_b = 0, total_b = 0;
-        if (!SWOK(hipMemGetInfo(&free_b, &total_b))) free_b = 0;
-        free_b += pool().pooled(dev);  // (handed out again to this very call, or flushed if the sizes differ)
-        const double budget = 0.92 * (double)free_b;
-        const double want = envd("FNN_SW_CAP", 0.0);
-        // {capacity / n, block = capacity / kdiv, departed columns = capacity / rdiv}: the roomy shapes first; where memory is
-        // short (32768 taxa) a shape with smaller side buffers buys capacity (4 n instead of 3.5 n)
-        struct Shape { double f; int kdiv, rdiv; };
-        const Shape shapes[] = {{6.0, 12, 5}, {5.0, 12, 5}, {4.5, 12, 5}, {4.0, 12, 5}, {4.0, 16, 8}, {3.5, 12, 5}, {3.25, 12, 5}};
-        Shape pick = shapes[6];
-        if (cap_want > 0) {
-            // a retry with a larger factor: the wanted capacity with the roomiest side buffers that fit, else as much as fits
-            const Shape tries[] = {{0.0, 12, 5}, {0.0, 16, 8}, {0.0, 24, 12}};
-            bool fits = false;
-            for (int round = 0; round < 40 && !fits; round++) {
-                for (const Shape& sh : tries) { pick = sh; if (sized(0.0, sh.kdiv, sh.rdiv) <= budget) { fits = true; break; } }
-                if (!fits) cap_want = (int64_t)(0.9 * (double)cap_want);
+    // ---------------------------------------------------------------- the block active-set method (see the comment above h_entry)
+    // One attempt at one capacity.  The state is grouped by what owns it - the factor, the departed columns, the candidates,
+    // scratch, the policy of the step loop -; run() is the step loop, a sequence of named steps.  The implicit operators, the
+    // reductions, the allocator, the stream and the counters that outlive an attempt are the Solver's.
+    struct BlockMethod {
+        Solver& sv;
+        const Knobs& kn;
+        const int n;
+        const int64_t ld, N;
+        const hipStream_t s;
+        const bool log;
+        rocblas_handle bh = nullptr;
+        bool blas_ok = true;
+        bool good = true, done = false;  // good: no give-up so far; done: no candidate is left
+
+        // The factor: the free set's normal equations H_FF = L L^T held as Ws = L^-1 (lower triangular, column panels)
+        struct Factor {
+            std::vector<int2> F;     // the factor's splits in factor order
+            std::vector<double> xw;  // weight per factor position (0 for the splits that left)
+            std::vector<double> cF;  // c = A^T d at the factor positions
+            int64_t f = 0, cap = 0, kmax = 0, pw = 0;  // splits inside, capacity, the largest block, panel width
+            TriStore Ws{nullptr, 0, 0};
+            int2* dF = nullptr;      // F on the device
+            double *z = nullptr, *xs = nullptr, *cK = nullptr, *gF = nullptr;  // z = W c; the sub-problem's solution; c and A^T A x at splits
+        } fac;
+        // The departed columns: the splits that left are constrained to zero, not eliminated
+        struct Departed {
+            std::vector<uint8_t> dead;      // per factor position
+            std::vector<int32_t> deadlist;  // factor positions of the splits that left, in the order of Y's columns
+            int64_t r = 0, rcap = 0;
+            double *Y = nullptr, *CR = nullptr, *LC = nullptr, *CRb = nullptr, *CRw = nullptr;  // Y = W[:, R], its Gram matrix, the Gram factor; copies
+            TriStore LCs{nullptr, 0, 0};    // (LC as one panel = square)
+            double* lam = nullptr;
+            int32_t* dlist = nullptr;       // deadlist on the device
+        } dep;
+        // The candidates: local maxima of the multiplier, unsorted and sorted
+        struct Candidates {
+            double *ckey = nullptr, *ckey2 = nullptr;
+            int64_t *cidx = nullptr, *cidx2 = nullptr;
+            unsigned long long* ccount = nullptr;
+            void* sort_tmp = nullptr;
+            size_t sort_bytes = 0;
+            int64_t ccap = 0;
+        } cand;
+        // Scratch: nothing here outlives the call that fills it
+        struct Scratch {
+            double *B = nullptr, *Tb = nullptr, *X = nullptr, *S = nullptr, *S0 = nullptr, *Li = nullptr, *tmp2 = nullptr;
+            int2* dscr = nullptr;
+            int32_t* dlist2 = nullptr;
+            double *wk = nullptr, *sk1 = nullptr, *sk2 = nullptr, *v = nullptr;
+            int64_t* dinfo = nullptr;
+        } scr;
+        // The policy of the step loop: everything a rule of run() reads or changes
+        struct Policy {
+            double tol = 0.0, tol_cap = 0.0, cmax = 0.0;  // multipliers above tol are candidates (raised to the measured noise floor, up to tol_cap)
+            double phi = 0.0;               // objective - c_F . x_F / 2 of the current point (a sub-problem's exact minimiser)
+            int64_t k_limit = 0, kmin = 0;
+            double rfrac_buf = 0.0;
+            bool ratio_mode = false;
+            bool fresh = false;             // the point comes straight from a rebuilt factor
+            int stall = 0;                  // steps in a row whose descent is not measurable (below 1e-13 |objective|)
+            std::vector<int2> banned;       // splits set aside: masked, but not in the factor
+            bool banned_rechecked = false;
+            bool revive_blocked = false;    // a step that only brought departed splits back did not descend: not again before a step moves
+            bool force_rebuild = false;     // a step ran out of room for its departed columns (taken back): rebuild before the next one
+            bool over_rcap = false;         // settle_all failed for lack of room for the departed columns (not a numerical failure)
+            int64_t f_step0 = 0;            // (statistics: factor size before this step's block entered)
+        } pol;
+        std::vector<double> sbuf;           // the minimiser of the last sub-problem solved
+
+        BlockMethod(Solver& solver, const Knobs& knobs)
+            : sv(solver), kn(knobs), n(solver.n), ld(solver.ld), N((int64_t)solver.n * (solver.n - 1) / 2), s(solver.s), log(knobs.log) {}
+        ~BlockMethod() { if (bh) rocblas_destroy_handle(bh); }
+        BlockMethod(const BlockMethod&) = delete;
+
+        static dim3 g1(int64_t c) { return dim3((unsigned)((c + T - 1) / T)); }
+        static dim3 g2(int64_t rows, int64_t cols) { return dim3((unsigned)((rows + T - 1) / T), (unsigned)std::max<int64_t>(1, std::min<int64_t>(cols, 16384))); }
+        bool give(int why, const char* text) { sv.giveup = why; sv.giveup_text = text; good = false; return false; }
+
+        // ------------------------------------------------------------ dense algebra on the stream
+        void gemm(rocblas_operation ta, rocblas_operation tb, int64_t m, int64_t nn, int64_t k, double alpha, const double* A, int64_t lda, const double* Bm,
+                  int64_t ldb, double beta, double* Cm, int64_t ldc) {
+            if (m <= 0 || nn <= 0) return;
+            sv.gemm_flops += 2.0 * (double)m * (double)nn * (double)k;
+            if (rocblas_dgemm_64(bh, ta, tb, m, nn, k, &alpha, A, lda, Bm, ldb, &beta, Cm, ldc) != rocblas_status_success) blas_ok = false;
+        }
+        void gemv(rocblas_operation ta, int64_t m, int64_t nn, double alpha, const double* A, int64_t lda, const double* xv, double beta, double* yv) {
+            if (m <= 0 || nn <= 0) return;
+            if (rocblas_dgemv_64(bh, ta, m, nn, &alpha, A, lda, xv, 1, &beta, yv, 1) != rocblas_status_success) blas_ok = false;
+        }
+        // panels that skip the zero half of a lower-triangular operand
+        // out (f x k, ldo) = Wl (f x f lower triangular, panel-stored) * Bm (f x k, ldb): panel by panel, each adding into the rows it reaches
+        void tri_times(const TriStore& Wl, int64_t f, const double* Bm, int64_t ldb, int64_t k, double* out, int64_t ldo) {
+            const int64_t chunks = (f + SK_CHUNK - 1) / SK_CHUNK;
+            if (k <= SMALLK && chunks * k * f <= fac.cap * fac.kmax) {  // a few columns: one pass over Wl (partial sums per column chunk in scr.X)
+                (void)hipMemsetAsync(scr.X, 0, sizeof(double) * (size_t)(chunks * k * f), s);
+                hipLaunchKernelGGL(k_tri_times_small, dim3((unsigned)((f + T - 1) / T), (unsigned)chunks), dim3(T), 0, s, Wl, f, Bm, ldb, (int)k, scr.X);
+                hipLaunchKernelGGL(k_sum_parts, g2(f, k), dim3(T), 0, s, scr.X, k * f, (int)chunks, f, k, 1.0, 0.0, out, ldo);
+                return;
             }
-            if (!fits) { giveup = FNN_SW_GIVEUP_SETUP; giveup_text = "no factor fits the device memory"; return false; }
-        } else {
-        for (const Shape& sh : shapes) {
-            pick = sh;
-            if (want > 0.0) { pick.f = want; break; }
-            if (sized(sh.f, sh.kdiv, sh.rdiv) <= budget) break;
+            // column chunks of about f / 8 (never across a storage panel): the zero triangle above a chunk's diagonal is the only waste
+            const int64_t gw = std::min(Wl.pw, std::max<int64_t>(1024, up64((f + 7) / 8)));
+            for (int64_t c0 = 0; c0 < f;) {
+                const int64_t q = c0 / Wl.pw, c1 = std::min({c0 + gw, (q + 1) * Wl.pw, f});
+                gemm(rocblas_operation_none, rocblas_operation_none, f - c0, k, c1 - c0, 1.0, Wl.at(c0, c0), Wl.ld(q), Bm + c0, ldb, c0 == 0 ? 0.0 : 1.0, out + c0, ldo);
+                c0 = c1;
+            }
         }
+        // out (k x f, ldo) = Tm^T (Tm: f x k, ldt) * Wl (f x f lower triangular, panel-stored)
+        void t_times_tri(const double* Tm, int64_t ldt, int64_t k, const TriStore& Wl, int64_t f, double* out, int64_t ldo) {
+            if (k <= SMALLK) {
+                hipLaunchKernelGGL(k_t_times_tri_small, dim3((unsigned)f), dim3(T), 0, s, Tm, ldt, (int)k, Wl, f, out, ldo);
+                return;
+            }
+            const int64_t gw = std::min(Wl.pw, std::max<int64_t>(1024, up64((f + 7) / 8)));
+            for (int64_t c0 = 0; c0 < f;) {
+                const int64_t q = c0 / Wl.pw, c1 = std::min({c0 + gw, (q + 1) * Wl.pw, f});
+                gemm(rocblas_operation_transpose, rocblas_operation_none, k, c1 - c0, f - c0, 1.0, Tm + c0, ldt, Wl.at(c0, c0), Wl.ld(q), 0.0, out + c0 * ldo, ldo);
+                c0 = c1;
+            }
         }
-        (void)sized(pick.f, pick.kdiv, pick.rdiv);
-        // (the departed columns' buffers bound how many may stay in the factor: up to this share of it whatever its size, and beyond
-        //  that share as long as the buffers keep room for one more block's departures - the rebuild rule in the loop below)
-        const double rfrac_buf = 0.75 * (double)b.rcap / (double)b.cap;
-        if (log) std::fprintf(stderr, "  [sw] capacity %lld splits (%.2f n), block <= %lld, departed <= %lld; device memory free %.1f GB\n", (long long)b.cap,
-                              (double)b.cap / n, (long long)b.kmax, (long long)b.rcap, (double)free_b * 1e-9);
-        capacity = b.cap;
-        if (rocblas_create_handle(&b.bh) != rocblas_status_success) { giveup = FNN_SW_GIVEUP_SETUP; giveup_text = "rocblas_create_handle failed"; return false; }
-        struct HandleGuard { rocblas_handle h; ~HandleGuard() { rocblas_destroy_handle(h); } } guard{b.bh};
-        rocblas_set_stream(b.bh, s);
-        rocblas_set_pointer_mode(b.bh, rocblas_pointer_mode_host);
-        const double t_alloc0 = wall();
-        b.W = alloc<double>((size_t)TriStore::elems(b.cap, b.pw));
-        b.Ws = TriStore{b.W, b.cap, b.pw};
-        b.B = alloc<double>((size_t)b.cap * b.kmax); b.Tb = alloc<double>((size_t)b.cap * b.kmax); b.X = alloc<double>((size_t)b.cap * b.kmax);
-        b.S = alloc<double>((size_t)b.kmax * b.kmax); b.S0 = alloc<double>((size_t)b.kmax * b.kmax); b.Li = alloc<double>((size_t)b.kmax * b.kmax);
-        b.tmp2 = alloc<double>((size_t)(std::max(b.rcap, b.kmax) * std::max(b.rcap, b.kmax) / 2 + 4096));
-        b.Y = alloc<double>((size_t)b.cap * b.rcap);
-        b.CR = alloc<double>((size_t)b.rcap * b.rcap); b.LC = alloc<double>((size_t)b.rcap * b.rcap);
-        b.LCs = TriStore{b.LC, b.rcap, b.rcap}; b.CRb = alloc<double>((size_t)b.rcap * b.rcap); b.CRw = alloc<double>((size_t)b.rcap * b.rcap);
-        b.z = alloc<double>((size_t)b.cap); b.v = alloc<double>((size_t)b.cap); b.xs = alloc<double>((size_t)b.cap); b.cK = alloc<double>((size_t)b.cap);
-        b.lam = alloc<double>((size_t)b.rcap); b.gF = alloc<double>((size_t)b.cap);
-        b.dF = alloc<int2>((size_t)b.cap); b.dscr = alloc<int2>((size_t)b.cap); b.dlist = alloc<int32_t>((size_t)b.cap); b.dlist2 = alloc<int32_t>((size_t)b.cap);
-        b.wk = alloc<double>((size_t)b.cap); b.sk1 = alloc<double>((size_t)b.cap); b.sk2 = alloc<double>((size_t)b.cap); b.dinfo = alloc<int64_t>(1);
-        b.ccap = std::min<int64_t>(N, std::max<int64_t>(1 << 16, N / 16 + 1024));
-        b.ckey = alloc<double>((size_t)b.ccap); b.ckey2 = alloc<double>((size_t)b.ccap);
-        b.cidx = alloc<int64_t>((size_t)b.ccap); b.cidx2 = alloc<int64_t>((size_t)b.ccap);
-        b.ccount = alloc<unsigned long long>(1);
-        if (hipcub::DeviceRadixSort::SortPairsDescending(nullptr, b.sort_bytes, b.ckey, b.ckey2, b.cidx, b.cidx2, (int)std::min<int64_t>(b.ccap, INT32_MAX), 0,
-                                                         64, s) != hipSuccess) { giveup = FNN_SW_GIVEUP_SETUP; giveup_text = "hipcub size query failed"; return false; }
-        b.sort_tmp = alloc<uint8_t>(b.sort_bytes + 16);
-        if (!ok) { giveup = FNN_SW_GIVEUP_SETUP; giveup_text = "device allocation of the factor's buffers failed"; return false; }
-        t_alloc_s = wall() - t_alloc0;
-        if (log) std::fprintf(stderr, "  [sw] buffers allocated in %.2f s\n", t_alloc_s);
-
-        // host state: the factor's splits in factor order, their weights, who left
-        std::vector<int2> F;
-        std::vector<double> xw;         // weight per factor position (0 for the splits that left)
-        std::vector<double> cF;         // c = A^T d at the factor positions
-        std::vector<uint8_t> dead;
-        std::vector<int32_t> deadlist;  // factor positions of the splits that left, in the order of Y's columns
-        std::vector<int2> banned;
-        double phi = 0.0;               // objective - c_F . x_F / 2 of the current point (a sub-problem's exact minimiser)
-
-        Atx(d, atwd);  // c = A^T d
-        (void)hipMemsetAsync(act, 0, (size_t)n * (size_t)ld, s);
-        double cmax = 0.0;
-        { const Best bb = reduce_best<RD_MAX_UNMASKED>(atwd, nullptr); cmax = bb.k == INT64_MAX ? 0.0 : -bb.v; }
-        double tol = 1e-12 * (cmax > 0.0 ? cmax : 1.0);  // multipliers above it are candidates (raised to the measured noise floor, below)
-        const double tol_cap = 1e-10 * (cmax > 0.0 ? cmax : 1.0);
-
-        auto upload_F = [&](int64_t from, int64_t to) {
-            if (to > from) (void)hipMemcpyAsync(b.dF + from, F.data() + from, sizeof(int2) * (size_t)(to - from), hipMemcpyHostToDevice, s);
-        };
-        auto set_mask = [&](const std::vector<int2>& list, uint8_t v) {  // (through the scratch list: the factor's own list stays as it is)
-            if (list.empty()) return;
-            (void)hipMemcpyAsync(b.dscr, list.data(), sizeof(int2) * list.size(), hipMemcpyHostToDevice, s);
-            hipLaunchKernelGGL(k_mask, g1((int64_t)list.size()), dim3(T), 0, s, b.dscr, (int64_t)list.size(), act, ld, v);
+        // C (m x nn) = beta C + alpha A^T B with a long inner dimension kk (A: kk x m, B: kk x nn): rocBLAS has no split-K form of
+        // this shape (3 TF/s); here the inner dimension is cut into slices that run as one strided-batched GEMM into partial
+        // products (workspace scr.X), added up in slice order
+        void tn_splitk(int64_t m, int64_t nn, int64_t kk, double alpha, const double* A, int64_t lda, const double* Bm, int64_t ldb, double beta, double* Cm,
+                       int64_t ldc) {
+            if (m <= 0 || nn <= 0) return;
+            const int64_t room = (fac.cap * fac.kmax) / std::max<int64_t>(m * nn, 1);
+            int64_t parts = std::min<int64_t>({room, (int64_t)32, (kk + 1023) / 1024});
+            if (parts < 2 || m * nn > (int64_t)1 << 26) {
+                gemm(rocblas_operation_transpose, rocblas_operation_none, m, nn, kk, alpha, A, lda, Bm, ldb, beta, Cm, ldc);
+                return;
+            }
+            const int64_t slice = kk / parts, rest = kk - slice * parts;  // `parts` equal slices, the remainder as one more
+            const double one = 1.0, zero = 0.0;
+            if (rocblas_dgemm_strided_batched_64(bh, rocblas_operation_transpose, rocblas_operation_none, m, nn, slice, &one, A, lda, slice, Bm, ldb, slice, &zero,
+                                                 scr.X, m, m * nn, parts) != rocblas_status_success) blas_ok = false;
+            int np = (int)parts;
+            if (rest > 0 && parts < room) {
+                gemm(rocblas_operation_transpose, rocblas_operation_none, m, nn, rest, 1.0, A + slice * parts, lda, Bm + slice * parts, ldb, 0.0, scr.X + parts * m * nn, m);
+                np++;
+            } else if (rest > 0) {
+                gemm(rocblas_operation_transpose, rocblas_operation_none, m, nn, rest, 1.0, A + slice * parts, lda, Bm + slice * parts, ldb, 1.0, scr.X + (parts - 1) * m * nn, m);
+            }
+            hipLaunchKernelGGL(k_sum_parts, g2(m, nn), dim3(T), 0, s, scr.X, m * nn, np, m, nn, alpha, beta, Cm, ldc);
+        }
+        // Li = inverse of the Cholesky factor of S (m x m, lower triangle read, destroyed), zeros above the diagonal: recursive halves,
+        // GEMMs and the in-LDS kernel for blocks of <= 64.  Everything is enqueued; a block that is not positive definite leaves the
+        // 1-based position of its first bad pivot in *scr.dinfo (invchol() reads it after the call).
+        void invchol_rec(double* S, int64_t lds, double* Li, int64_t ldl, int64_t m, int64_t off) {
+            if (m <= TRI_NB) {
+                hipLaunchKernelGGL(k_invchol_small, dim3(1), dim3(TRI_NB), 0, s, S, lds, Li, ldl, (int)m, (long long)off, (long long*)scr.dinfo);
+                return;
+            }
+            const int64_t m1 = std::min(m - 1, up64((m + 1) / 2)), m2 = m - m1;
+            double *S21 = S + m1, *S22 = S + m1 + m1 * lds, *Li21 = Li + m1, *Li22 = Li + m1 + m1 * ldl;
+            double *t1 = scr.tmp2, *t2 = scr.tmp2 + m2 * m1;
+            invchol_rec(S, lds, Li, ldl, m1, off);
+            gemm(rocblas_operation_none, rocblas_operation_transpose, m2, m1, m1, 1.0, S21, lds, Li, ldl, 0.0, t1, m2);           // L21 = S21 Li11^T
+            const double mone = -1.0, one = 1.0;
+            if (rocblas_dsyrk_64(bh, rocblas_fill_lower, rocblas_operation_none, m2, m1, &mone, t1, m2, &one, S22, lds) != rocblas_status_success) blas_ok = false;
+            gemm(rocblas_operation_none, rocblas_operation_none, m2, m1, m1, 1.0, t1, m2, Li, ldl, 0.0, t2, m2);                    // L21 Li11
+            invchol_rec(S22, lds, Li22, ldl, m2, off + m1);
+            gemm(rocblas_operation_none, rocblas_operation_none, m2, m1, m2, -1.0, Li22, ldl, t2, m2, 0.0, Li21, ldl);              // Li21 = -Li22 L21 Li11
+            hipLaunchKernelGGL(k_fill2d, g2(m1, m2), dim3(T), 0, s, Li + m1 * ldl, ldl, m1, m2, 0.0);
+        }
+        int64_t invchol(double* S, int64_t lds, double* Li, int64_t ldl, int64_t m) {  // 0, or the 1-based position of the first pivot that is not positive
+            if (m <= 0) return 0;
+            const int64_t big = INT64_MAX;
+            (void)hipMemcpyAsync(scr.dinfo, &big, sizeof(big), hipMemcpyHostToDevice, s);
             (void)hipStreamSynchronize(s);
-        };
+            invchol_rec(S, lds, Li, ldl, m, 0);
+            int64_t info = 0;
+            (void)hipMemcpyAsync(&info, scr.dinfo, sizeof(info), hipMemcpyDeviceToHost, s);
+            (void)hipStreamSynchronize(s);
+            return info == INT64_MAX ? 0 : info;
+        }
+
+        // ------------------------------------------------------------ setup: the capacity plan, the rocBLAS handle, the buffers
+        bool setup() {
+            sv.lap_on = log;
+            sv.giveup = 0; sv.giveup_text = ""; sv.ok = true;
+            sv.block_mark = sv.allocs.size();
+            size_t free_b = 0, total_b = 0;
+            if (!SWOK(hipMemGetInfo(&free_b, &total_b))) free_b = 0;
+            free_b += pool().pooled(sv.dev);  // (handed out again to this very call, or flushed if the sizes differ)
+            const bool retry = sv.cap_want > 0;
+            const CapacityPlan pl = plan_capacity(n, 0.92 * (double)free_b, sv.cap_want, kn);
+            if (retry) sv.cap_want = pl.cap_want;
+            if (retry && !pl.fits) return give(FNN_SW_GIVEUP_SETUP, "no factor fits the device memory");
+            fac.cap = pl.cap; fac.kmax = pl.kmax; fac.pw = pl.pw; dep.rcap = pl.rcap;
+            // (the departed columns' buffers bound how many may stay in the factor: up to this share of it whatever its size, and beyond
+            //  that share as long as the buffers keep room for one more block's departures - the rebuild rule of the step loop)
+            pol.rfrac_buf = 0.75 * (double)dep.rcap / (double)fac.cap;
+            if (log) std::fprintf(stderr, "  [sw] capacity %lld splits (%.2f n), block <= %lld, departed <= %lld; device memory free %.1f GB\n", (long long)fac.cap,
+                                  (double)fac.cap / n, (long long)fac.kmax, (long long)dep.rcap, (double)free_b * 1e-9);
+            sv.capacity = fac.cap;
+            if (rocblas_create_handle(&bh) != rocblas_status_success) { bh = nullptr; return give(FNN_SW_GIVEUP_SETUP, "rocblas_create_handle failed"); }
+            rocblas_set_stream(bh, s);
+            rocblas_set_pointer_mode(bh, rocblas_pointer_mode_host);
+            const double t_alloc0 = sv.wall();
+            // (order and byte counts as they are: the pool hands a buffer back to a request of exactly its size)
+            const int64_t cap = fac.cap, kmax = fac.kmax, rcap = dep.rcap;
+            fac.Ws = TriStore{sv.alloc<double>((size_t)tri_elems(cap, fac.pw)), cap, fac.pw};
+            scr.B = sv.alloc<double>((size_t)cap * kmax); scr.Tb = sv.alloc<double>((size_t)cap * kmax); scr.X = sv.alloc<double>((size_t)cap * kmax);
+            scr.S = sv.alloc<double>((size_t)kmax * kmax); scr.S0 = sv.alloc<double>((size_t)kmax * kmax); scr.Li = sv.alloc<double>((size_t)kmax * kmax);
+            scr.tmp2 = sv.alloc<double>((size_t)(std::max(rcap, kmax) * std::max(rcap, kmax) / 2 + 4096));
+            dep.Y = sv.alloc<double>((size_t)cap * rcap);
+            dep.CR = sv.alloc<double>((size_t)rcap * rcap); dep.LC = sv.alloc<double>((size_t)rcap * rcap);
+            dep.LCs = TriStore{dep.LC, rcap, rcap}; dep.CRb = sv.alloc<double>((size_t)rcap * rcap); dep.CRw = sv.alloc<double>((size_t)rcap * rcap);
+            fac.z = sv.alloc<double>((size_t)cap); scr.v = sv.alloc<double>((size_t)cap); fac.xs = sv.alloc<double>((size_t)cap); fac.cK = sv.alloc<double>((size_t)cap);
+            dep.lam = sv.alloc<double>((size_t)rcap); fac.gF = sv.alloc<double>((size_t)cap);
+            fac.dF = sv.alloc<int2>((size_t)cap); scr.dscr = sv.alloc<int2>((size_t)cap); dep.dlist = sv.alloc<int32_t>((size_t)cap); scr.dlist2 = sv.alloc<int32_t>((size_t)cap);
+            scr.wk = sv.alloc<double>((size_t)cap); scr.sk1 = sv.alloc<double>((size_t)cap); scr.sk2 = sv.alloc<double>((size_t)cap); scr.dinfo = sv.alloc<int64_t>(1);
+            cand.ccap = std::min<int64_t>(N, std::max<int64_t>(1 << 16, N / 16 + 1024));
+            cand.ckey = sv.alloc<double>((size_t)cand.ccap); cand.ckey2 = sv.alloc<double>((size_t)cand.ccap);
+            cand.cidx = sv.alloc<int64_t>((size_t)cand.ccap); cand.cidx2 = sv.alloc<int64_t>((size_t)cand.ccap);
+            cand.ccount = sv.alloc<unsigned long long>(1);
+            if (hipcub::DeviceRadixSort::SortPairsDescending(nullptr, cand.sort_bytes, cand.ckey, cand.ckey2, cand.cidx, cand.cidx2, (int)std::min<int64_t>(cand.ccap, INT32_MAX), 0,
+                                                             64, s) != hipSuccess) return give(FNN_SW_GIVEUP_SETUP, "hipcub size query failed");
+            cand.sort_tmp = sv.alloc<uint8_t>(cand.sort_bytes + 16);
+            if (!sv.ok) return give(FNN_SW_GIVEUP_SETUP, "device allocation of the factor's buffers failed");
+            sv.t_alloc_s = sv.wall() - t_alloc0;
+            if (log) std::fprintf(stderr, "  [sw] buffers allocated in %.2f s\n", sv.t_alloc_s);
+            return true;
+        }
+        // c = A^T d, the empty mask, the candidates' threshold
+        void start() {
+            sv.Atx(sv.d, sv.atwd);  // c = A^T d
+            (void)hipMemsetAsync(sv.act, 0, (size_t)n * (size_t)ld, s);
+            { const Best bb = sv.reduce_best<RD_MAX_UNMASKED>(sv.atwd, nullptr); pol.cmax = bb.k == INT64_MAX ? 0.0 : -bb.v; }
+            pol.tol = 1e-12 * (pol.cmax > 0.0 ? pol.cmax : 1.0);
+            pol.tol_cap = 1e-10 * (pol.cmax > 0.0 ? pol.cmax : 1.0);
+            pol.kmin = std::max<int64_t>(8, n / 32);
+            pol.k_limit = fac.kmax;
+        }
+
+        // ------------------------------------------------------------ the factor and the departed columns: what a step is made of
+        void upload_F(int64_t from, int64_t to) {
+            if (to > from) (void)hipMemcpyAsync(fac.dF + from, fac.F.data() + from, sizeof(int2) * (size_t)(to - from), hipMemcpyHostToDevice, s);
+        }
+        void set_mask(const std::vector<int2>& list, uint8_t v) {  // (through the scratch list: the factor's own list stays as it is)
+            if (list.empty()) return;
+            (void)hipMemcpyAsync(scr.dscr, list.data(), sizeof(int2) * list.size(), hipMemcpyHostToDevice, s);
+            hipLaunchKernelGGL(k_mask, g1((int64_t)list.size()), dim3(T), 0, s, scr.dscr, (int64_t)list.size(), sv.act, ld, v);
+            (void)hipStreamSynchronize(s);
+        }
+        // the weights xw of the factor's splits onto the grid sv.x, zeros elsewhere (enqueued)
+        void weights_to_grid() {
+            (void)hipMemsetAsync(sv.x, 0, sizeof(double) * (size_t)n * (size_t)ld, s);
+            if (fac.f) {
+                (void)hipMemcpyAsync(fac.xs, fac.xw.data(), sizeof(double) * (size_t)fac.f, hipMemcpyHostToDevice, s);
+                hipLaunchKernelGGL(k_scatter, g1(fac.f), dim3(T), 0, s, fac.dF, fac.f, fac.xs, sv.x, ld);
+            }
+        }
         // LC = inverse of the Cholesky factor of the Gram matrix CR of the departed columns (lower triangular), from scratch
-        auto factor_gram = [&]() -> bool {
-            if (b.r == 0) return true;
-            hipLaunchKernelGGL(k_copy_lower, g2(b.r, b.r), dim3(T), 0, s, b.CR, b.rcap, b.CRw, b.rcap, b.r);
-            return invchol(b.CRw, b.rcap, b.LC, b.rcap, b.r) == 0;
-        };
+        bool factor_gram() {
+            if (dep.r == 0) return true;
+            hipLaunchKernelGGL(k_copy_lower, g2(dep.r, dep.r), dim3(T), 0, s, dep.CR, dep.rcap, dep.CRw, dep.rcap, dep.r);
+            return invchol(dep.CRw, dep.rcap, dep.LC, dep.rcap, dep.r) == 0;
+        }
         // The core of an append, shared by the factor W (rows for splits that enter) and by LC (rows for columns that depart).
         // phase 1: T = Wi Bc, S = S - T^T T for a lower-triangular inverse factor Wi (f x f); phase 2: rows f .. f + k of Wi
         // from T, the Cholesky factor's inverse Li of S:  [-Li T^T Wi | Li], zeros above.
-        auto rows_phase1 = [&](const TriStore& Wi, int64_t f, const double* Bc, int64_t ldb, int64_t k, double* Tm, int64_t ldt, double* Sm, int64_t lds) {
+        void rows_phase1(const TriStore& Wi, int64_t f, const double* Bc, int64_t ldb, int64_t k, double* Tm, int64_t ldt, double* Sm, int64_t lds) {
             if (f == 0) return;
             tri_times(Wi, f, Bc, ldb, k, Tm, ldt);
             tn_splitk(k, k, f, -1.0, Tm, ldt, Tm, ldt, 1.0, Sm, lds);
-        };
-        auto rows_phase2 = [&](const TriStore& Wi, int64_t f, const double* Tm, int64_t ldt, const double* Lim, int64_t ldl, int64_t k) {
+        }
+        void rows_phase2(const TriStore& Wi, int64_t f, const double* Tm, int64_t ldt, const double* Lim, int64_t ldl, int64_t k) {
             if (f > 0) {
-                t_times_tri(Tm, ldt, k, Wi, f, b.X, b.kmax);  // X = T^T Wi
+                t_times_tri(Tm, ldt, k, Wi, f, scr.X, fac.kmax);  // X = T^T Wi
                 for (int64_t q = 0, q0 = 0; q0 < f; q++, q0 += Wi.pw) {  // new rows -Li X, panel by panel
                     const int64_t w = std::min(Wi.pw, f - q0);
-                    gemm(rocblas_operation_none, rocblas_operation_none, k, w, k, -1.0, Lim, ldl, b.X + q0 * b.kmax, b.kmax, 0.0, Wi.panel(q) + (f - q0), Wi.ld(q));
+                    gemm(rocblas_operation_none, rocblas_operation_none, k, w, k, -1.0, Lim, ldl, scr.X + q0 * fac.kmax, fac.kmax, 0.0, Wi.panel(q) + (f - q0), Wi.ld(q));
                 }
             }
             for (int64_t c0 = f; c0 < f + k;) {  // the new columns: zeros above (inside their panel), then Li
@@ -1152,473 +1178,490 @@ struct Solver {
                 hipLaunchKernelGGL(k_copy2d, g2(f + k - r0, c1 - c0), dim3(T), 0, s, Lim + (c0 - f) * ldl + (r0 - f), ldl, Wi.at(r0, c0), Wi.ld(q), f + k - r0, c1 - c0);
                 c0 = c1;
             }
-        };
-        // append the k splits at b.dF[f .. f + k) with multipliers wK (device, may be null: no screening).  Screening: the block's
+        }
+        // the block's Schur complement and multipliers follow the kept splits (append's screening)
+        void regather_block(const std::vector<int32_t>& kept, const double* wK) {
+            const int64_t kk = (int64_t)kept.size();
+            (void)hipMemcpyAsync(scr.dlist2, kept.data(), sizeof(int32_t) * kept.size(), hipMemcpyHostToDevice, s);
+            hipLaunchKernelGGL(k_gather_sym, g2(kk, kk), dim3(T), 0, s, scr.S0, fac.kmax, scr.dlist2, kk, scr.S, fac.kmax);
+            if (wK) hipLaunchKernelGGL(k_gather_vec, g1(kk), dim3(T), 0, s, wK, scr.dlist2, kk, scr.wk);
+            (void)hipStreamSynchronize(s);
+        }
+        // append the k splits at fac.dF[f .. f + k) with multipliers wK (device, may be null: no screening).  Screening: the block's
         // weights in the joint sub-problem are S^-1 w_K with S the block's Schur complement - known before the rows are formed;
         // splits whose weight would not be positive are dropped here, at half the price and without ever entering the factor.
         // `kept` receives the indices (into the block) of the splits that entered; returns their number, -1 on failure.
-        auto append = [&](int64_t k, const double* wK, std::vector<int32_t>& kept) -> int64_t {
-            const double t0 = log ? wall() : 0.0;
-            const int64_t f = b.f;
-            int2* dK = b.dF + f;
+        int64_t append(int64_t k, const double* wK, std::vector<int32_t>& kept) {
+            const double t0 = log ? sv.wall() : 0.0;
+            const int64_t f = fac.f;
+            int2* dK = fac.dF + f;
             kept.resize((size_t)k);
             for (int64_t q = 0; q < k; q++) kept[(size_t)q] = (int32_t)q;
-            lap(nullptr);
-            hipLaunchKernelGGL(k_hblock, g2(k, k), dim3(T), 0, s, dK, k, dK, k, n, b.S, b.kmax, 0);
-            if (f > 0) hipLaunchKernelGGL(k_hblock, g2(f, k), dim3(T), 0, s, b.dF, f, dK, k, n, b.B, b.cap, 0);
-            lap("append.hblock");
-            rows_phase1(b.Ws, f, b.B, b.cap, k, b.Tb, b.cap, b.S, b.kmax);  // T = L^-1 B = L21^T, S = H_KK - L21 L21^T
-            lap("append.W*B+syrk");
-            hipLaunchKernelGGL(k_copy2d, g2(k, k), dim3(T), 0, s, b.S, b.kmax, b.S0, b.kmax, k, k);
+            sv.lap(nullptr);
+            hipLaunchKernelGGL(k_hblock, g2(k, k), dim3(T), 0, s, dK, k, dK, k, n, scr.S, fac.kmax, 0);
+            if (f > 0) hipLaunchKernelGGL(k_hblock, g2(f, k), dim3(T), 0, s, fac.dF, f, dK, k, n, scr.B, fac.cap, 0);
+            sv.lap("append.hblock");
+            rows_phase1(fac.Ws, f, scr.B, fac.cap, k, scr.Tb, fac.cap, scr.S, fac.kmax);  // T = L^-1 B = L21^T, S = H_KK - L21 L21^T
+            sv.lap("append.W*B+syrk");
+            hipLaunchKernelGGL(k_copy2d, g2(k, k), dim3(T), 0, s, scr.S, fac.kmax, scr.S0, fac.kmax, k, k);
             const double* wcur = wK;
             std::vector<double> sK;
             bool changed = false;
             for (int round = 0;; round++) {
                 const int64_t kk = (int64_t)kept.size();
-                const int64_t info = invchol(b.S, b.kmax, b.Li, b.kmax, kk);  // Li = L22^-1
+                const int64_t info = invchol(scr.S, fac.kmax, scr.Li, fac.kmax, kk);  // Li = L22^-1
                 if (info > 0) {  // not positive definite at split `info`: the block ends in front of it
                     kept.resize((size_t)(info - 1)); changed = true;
                     if (kept.empty()) return 0;
-                    (void)hipMemcpyAsync(b.dlist2, kept.data(), sizeof(int32_t) * kept.size(), hipMemcpyHostToDevice, s);
-                    hipLaunchKernelGGL(k_gather_sym, g2((int64_t)kept.size(), (int64_t)kept.size()), dim3(T), 0, s, b.S0, b.kmax, b.dlist2, (int64_t)kept.size(), b.S, b.kmax);
-                    if (wK) { hipLaunchKernelGGL(k_gather_vec, g1((int64_t)kept.size()), dim3(T), 0, s, wK, b.dlist2, (int64_t)kept.size(), b.wk); wcur = b.wk; }
-                    (void)hipStreamSynchronize(s);
+                    regather_block(kept, wK);
+                    if (wK) wcur = scr.wk;
                     continue;
                 }
                 if (!wK || round >= 12) break;
                 // the block's weights in the joint sub-problem: S^-1 w_K = Li^T (Li w_K)
-                gemv(rocblas_operation_none, kk, kk, 1.0, b.Li, b.kmax, wcur, 0.0, b.sk1);
-                gemv(rocblas_operation_transpose, kk, kk, 1.0, b.Li, b.kmax, b.sk1, 0.0, b.sk2);
+                gemv(rocblas_operation_none, kk, kk, 1.0, scr.Li, fac.kmax, wcur, 0.0, scr.sk1);
+                gemv(rocblas_operation_transpose, kk, kk, 1.0, scr.Li, fac.kmax, scr.sk1, 0.0, scr.sk2);
                 sK.resize((size_t)kk);
-                (void)hipMemcpyAsync(sK.data(), b.sk2, sizeof(double) * (size_t)kk, hipMemcpyDeviceToHost, s);
+                (void)hipMemcpyAsync(sK.data(), scr.sk2, sizeof(double) * (size_t)kk, hipMemcpyDeviceToHost, s);
                 (void)hipStreamSynchronize(s);
                 std::vector<int32_t> nk;
                 for (int64_t q = 0; q < kk; q++) if (sK[(size_t)q] > 0.0) nk.push_back(kept[(size_t)q]);
                 if ((int64_t)nk.size() == kk) break;
-                st_screened += kk - (int64_t)nk.size();
+                sv.st_screened += kk - (int64_t)nk.size();
                 if (nk.empty()) nk.push_back(kept[0]);  // (a single split with a positive multiplier always gets a positive weight)
                 kept.swap(nk); changed = true;
-                (void)hipMemcpyAsync(b.dlist2, kept.data(), sizeof(int32_t) * kept.size(), hipMemcpyHostToDevice, s);
-                hipLaunchKernelGGL(k_gather_sym, g2((int64_t)kept.size(), (int64_t)kept.size()), dim3(T), 0, s, b.S0, b.kmax, b.dlist2, (int64_t)kept.size(), b.S, b.kmax);
-                hipLaunchKernelGGL(k_gather_vec, g1((int64_t)kept.size()), dim3(T), 0, s, wK, b.dlist2, (int64_t)kept.size(), b.wk);
-                wcur = b.wk;
-                (void)hipStreamSynchronize(s);
+                regather_block(kept, wK);
+                wcur = scr.wk;
             }
-            lap("append.potrf+trtri+screen");
+            sv.lap("append.potrf+trtri+screen");
             k = (int64_t)kept.size();
-            const double* Tuse = b.Tb;
-            if (changed) {  // T's columns and the split list follow the kept ones (b.B is free now)
-                (void)hipMemcpyAsync(b.dlist2, kept.data(), sizeof(int32_t) * kept.size(), hipMemcpyHostToDevice, s);
-                if (f > 0) { hipLaunchKernelGGL(k_gather_cols, g2(f, k), dim3(T), 0, s, b.Tb, b.cap, f, b.dlist2, k, b.B, b.cap); Tuse = b.B; }
-                hipLaunchKernelGGL(k_gather_int2, g1(k), dim3(T), 0, s, dK, b.dlist2, k, b.dscr);
-                (void)hipMemcpyAsync(dK, b.dscr, sizeof(int2) * (size_t)k, hipMemcpyDeviceToDevice, s);
+            const double* Tuse = scr.Tb;
+            if (changed) {  // T's columns and the split list follow the kept ones (scr.B is free now)
+                (void)hipMemcpyAsync(scr.dlist2, kept.data(), sizeof(int32_t) * kept.size(), hipMemcpyHostToDevice, s);
+                if (f > 0) { hipLaunchKernelGGL(k_gather_cols, g2(f, k), dim3(T), 0, s, scr.Tb, fac.cap, f, scr.dlist2, k, scr.B, fac.cap); Tuse = scr.B; }
+                hipLaunchKernelGGL(k_gather_int2, g1(k), dim3(T), 0, s, dK, scr.dlist2, k, scr.dscr);
+                (void)hipMemcpyAsync(dK, scr.dscr, sizeof(int2) * (size_t)k, hipMemcpyDeviceToDevice, s);
                 (void)hipStreamSynchronize(s);
             }
-            hipLaunchKernelGGL(k_gather, g1(k), dim3(T), 0, s, dK, k, atwd, ld, b.cK);
-            rows_phase2(b.Ws, f, Tuse, b.cap, b.Li, b.kmax, k);
-            if (f > 0) gemv(rocblas_operation_transpose, f, k, -1.0, Tuse, b.cap, b.z, 1.0, b.cK);  // c_K - L21 z
-            gemv(rocblas_operation_none, k, k, 1.0, b.Li, b.kmax, b.cK, 0.0, b.z + f);                // z_K = L22^-1 (c_K - L21 z)
-            lap("append.rows");
-            if (b.r > 0) {  // the departed columns grow by the new rows; so does their Gram matrix
-                hipLaunchKernelGGL(k_gather_rows_tri, g2(k, b.r), dim3(T), 0, s, b.Ws, f, k, b.dlist, b.r, b.Y, b.cap);
+            hipLaunchKernelGGL(k_gather, g1(k), dim3(T), 0, s, dK, k, sv.atwd, ld, fac.cK);
+            rows_phase2(fac.Ws, f, Tuse, fac.cap, scr.Li, fac.kmax, k);
+            if (f > 0) gemv(rocblas_operation_transpose, f, k, -1.0, Tuse, fac.cap, fac.z, 1.0, fac.cK);  // c_K - L21 z
+            gemv(rocblas_operation_none, k, k, 1.0, scr.Li, fac.kmax, fac.cK, 0.0, fac.z + f);                // z_K = L22^-1 (c_K - L21 z)
+            sv.lap("append.rows");
+            if (dep.r > 0) {  // the departed columns grow by the new rows; so does their Gram matrix
+                hipLaunchKernelGGL(k_gather_rows_tri, g2(k, dep.r), dim3(T), 0, s, fac.Ws, f, k, dep.dlist, dep.r, dep.Y, fac.cap);
                 const double one = 1.0;
-                if (rocblas_dsyrk_64(b.bh, rocblas_fill_lower, rocblas_operation_transpose, b.r, k, &one, b.Y + f, b.cap, &one, b.CR, b.rcap) != rocblas_status_success)
+                if (rocblas_dsyrk_64(bh, rocblas_fill_lower, rocblas_operation_transpose, dep.r, k, &one, dep.Y + f, fac.cap, &one, dep.CR, dep.rcap) != rocblas_status_success)
                     blas_ok = false;
                 if (!factor_gram()) return -1;
-                lap("append.gram");
+                sv.lap("append.gram");
             }
-            b.f = f + k;
-            if (log) t_append += wall() - t0;
+            fac.f = f + k;
+            if (log) sv.t_append += sv.wall() - t0;
             return blas_ok ? k : -1;
-        };
+        }
+        void log_departed_positions() const {  // where in the factor did the departed splits sit?
+            std::vector<double> pos;
+            for (size_t p = 0; p < fac.F.size(); p++) if (dep.dead[p]) pos.push_back((double)p / (double)fac.F.size());
+            if (!pos.empty())
+                std::fprintf(stderr, "  [sw] rebuild at %zu with %zu departed; their positions: 10%% %.2f 25%% %.2f 50%% %.2f 75%% %.2f\n", fac.F.size(), pos.size(),
+                             pos[pos.size() / 10], pos[pos.size() / 4], pos[pos.size() / 2], pos[pos.size() * 3 / 4]);
+        }
         // rebuild the factor from H's closed form for the splits that are still in: the compacted list appended in blocks
-        auto refactor = [&]() -> bool {
-            const double t0 = log ? wall() : 0.0;
-            st_lh_refactor++;
-            if (log) {  // where in the factor did the departed splits sit?
-                std::vector<double> pos;
-                for (size_t p = 0; p < F.size(); p++) if (dead[p]) pos.push_back((double)p / (double)F.size());
-                if (!pos.empty())
-                    std::fprintf(stderr, "  [sw] rebuild at %zu with %zu departed; their positions: 10%% %.2f 25%% %.2f 50%% %.2f 75%% %.2f\n", F.size(), pos.size(),
-                                 pos[pos.size() / 10], pos[pos.size() / 4], pos[pos.size() / 2], pos[pos.size() * 3 / 4]);
-            }
+        bool refactor() {
+            const double t0 = log ? sv.wall() : 0.0;
+            sv.st_lh_refactor++;
+            if (log) log_departed_positions();
             std::vector<int2> gone;
-            size_t q = 0;
-            for (size_t p = 0; p < F.size(); p++) {
-                if (dead[p]) { gone.push_back(F[p]); continue; }
-                F[q] = F[p]; xw[q] = xw[p]; cF[q] = cF[p]; q++;
-            }
-            F.resize(q); xw.resize(q); cF.resize(q); dead.assign(q, 0); deadlist.clear();
+            compact_live(fac.F, fac.xw, fac.cF, dep.dead, dep.deadlist, gone);
+            const size_t q = fac.F.size();
             set_mask(gone, 0);  // they may enter again
-            b.f = 0; b.r = 0;
+            fac.f = 0; dep.r = 0;
             if (q == 0) return true;
             upload_F(0, (int64_t)q);
             std::vector<int32_t> kept;
-            while (b.f < (int64_t)q) {
-                const int64_t k = std::min<int64_t>({b.kmax, (int64_t)4096, (int64_t)q - b.f});
+            while (fac.f < (int64_t)q) {
+                const int64_t k = std::min<int64_t>({fac.kmax, (int64_t)4096, (int64_t)q - fac.f});
                 if (append(k, nullptr, kept) != k) return false;
             }
             (void)hipStreamSynchronize(s);
-            if (log) { const double dt = wall() - t0; t_refactor += dt; t_append -= dt; }
+            if (log) { const double dt = sv.wall() - t0; sv.t_refactor += dt; sv.t_append -= dt; }
             return blas_ok;
-        };
+        }
         // the splits at the factor positions `idxs` leave: their columns join Y, the Gram matrix and its factor grow
-        auto depart = [&](const std::vector<int32_t>& idxs) -> bool {
-            const double t0 = log ? wall() : 0.0;
-            const int64_t nn = (int64_t)idxs.size(), r = b.r, f = b.f;
-            lap(nullptr);
-            (void)hipMemcpyAsync(b.dlist + r, idxs.data(), sizeof(int32_t) * (size_t)nn, hipMemcpyHostToDevice, s);
-            hipLaunchKernelGGL(k_gather_cols_tri, g2(f, nn), dim3(T), 0, s, b.Ws, f, b.dlist + r, nn, b.Y + r * b.cap, b.cap);
+        bool depart(const std::vector<int32_t>& idxs) {
+            const double t0 = log ? sv.wall() : 0.0;
+            const int64_t nn = (int64_t)idxs.size(), r = dep.r, f = fac.f;
+            sv.lap(nullptr);
+            (void)hipMemcpyAsync(dep.dlist + r, idxs.data(), sizeof(int32_t) * (size_t)nn, hipMemcpyHostToDevice, s);
+            hipLaunchKernelGGL(k_gather_cols_tri, g2(f, nn), dim3(T), 0, s, fac.Ws, f, dep.dlist + r, nn, dep.Y + r * fac.cap, fac.cap);
             // CR[r : r + nn, 0 : r + nn] = YN^T [Y, YN]
-            tn_splitk(nn, r + nn, f, 1.0, b.Y + r * b.cap, b.cap, b.Y, b.cap, 0.0, b.CR + r, b.rcap);
+            tn_splitk(nn, r + nn, f, 1.0, dep.Y + r * fac.cap, fac.cap, dep.Y, fac.cap, 0.0, dep.CR + r, dep.rcap);
             (void)hipStreamSynchronize(s);  // (idxs may be a temporary)
-            lap("depart.gather+gram");
-            for (int32_t p : idxs) { dead[(size_t)p] = 1; xw[(size_t)p] = 0.0; deadlist.push_back(p); }
+            sv.lap("depart.gather+gram");
+            for (int32_t p : idxs) { dep.dead[(size_t)p] = 1; fac.xw[(size_t)p] = 0.0; dep.deadlist.push_back(p); }
             bool fine = true;
-            if (r == 0 || nn > b.kmax) { b.r = r + nn; fine = factor_gram(); }
+            if (r == 0 || nn > fac.kmax) { dep.r = r + nn; fine = factor_gram(); }
             else {  // border the inverse factor: cross block CR[r:, 0:r]^T, diagonal block CR[r:, r:]
-                hipLaunchKernelGGL(k_transpose_small, g2(nn, r), dim3(T), 0, s, b.CR + r, b.rcap, nn, r, b.B, b.cap);  // (r x nn)
-                hipLaunchKernelGGL(k_copy2d, g2(nn, nn), dim3(T), 0, s, b.CR + r + r * b.rcap, b.rcap, b.S, b.kmax, nn, nn);
-                rows_phase1(b.LCs, r, b.B, b.cap, nn, b.Tb, b.cap, b.S, b.kmax);
-                if (invchol(b.S, b.kmax, b.Li, b.kmax, nn) != 0) { b.r = r + nn; fine = factor_gram(); }
+                hipLaunchKernelGGL(k_transpose_small, g2(nn, r), dim3(T), 0, s, dep.CR + r, dep.rcap, nn, r, scr.B, fac.cap);  // (r x nn)
+                hipLaunchKernelGGL(k_copy2d, g2(nn, nn), dim3(T), 0, s, dep.CR + r + r * dep.rcap, dep.rcap, scr.S, fac.kmax, nn, nn);
+                rows_phase1(dep.LCs, r, scr.B, fac.cap, nn, scr.Tb, fac.cap, scr.S, fac.kmax);
+                if (invchol(scr.S, fac.kmax, scr.Li, fac.kmax, nn) != 0) { dep.r = r + nn; fine = factor_gram(); }
                 else {
-                    rows_phase2(b.LCs, r, b.Tb, b.cap, b.Li, b.kmax, nn);
-                    b.r = r + nn;
+                    rows_phase2(dep.LCs, r, scr.Tb, fac.cap, scr.Li, fac.kmax, nn);
+                    dep.r = r + nn;
                 }
             }
-            lap("depart.gram_factor");
-            if (log) t_dead += wall() - t0;
+            sv.lap("depart.gram_factor");
+            if (log) sv.t_dead += sv.wall() - t0;
             return fine && blas_ok;
-        };
+        }
         // Departed splits (factor positions `rev`) come BACK: a split that left is only constrained to zero - its row is still in the
         // factor - so un-constraining it costs the compaction of Y's columns and of the Gram matrix and a fresh Gram factor
         // (r^3, milliseconds), where the route through a rebuild and the candidates re-appends it at f^2 per split.
-        auto revive = [&](const std::vector<int32_t>& rev) -> bool {
-            const double t0 = log ? wall() : 0.0;
-            const int64_t r = b.r, f = b.f;
-            std::vector<uint8_t> back((size_t)f, 0);
-            for (int32_t p : rev) { back[(size_t)p] = 1; dead[(size_t)p] = 0; }
+        bool revive(const std::vector<int32_t>& rev) {
+            const double t0 = log ? sv.wall() : 0.0;
+            const int64_t r = dep.r, f = fac.f;
             std::vector<int32_t> keepcols, newdead;
-            for (int64_t q = 0; q < r; q++)
-                if (!back[(size_t)deadlist[(size_t)q]]) { keepcols.push_back((int32_t)q); newdead.push_back(deadlist[(size_t)q]); }
+            revival_lists(rev, f, dep.dead, dep.deadlist, keepcols, newdead);
             const int64_t rn = (int64_t)keepcols.size();
-            st_revived += r - rn;
+            sv.st_revived += r - rn;
             if (rn > 0) {
-                (void)hipMemcpyAsync(b.dlist2, keepcols.data(), sizeof(int32_t) * (size_t)rn, hipMemcpyHostToDevice, s);
-                hipLaunchKernelGGL(k_gather_sym, g2(rn, rn), dim3(T), 0, s, b.CR, b.rcap, b.dlist2, rn, b.CRw, b.rcap);
-                hipLaunchKernelGGL(k_copy2d, g2(rn, rn), dim3(T), 0, s, b.CRw, b.rcap, b.CR, b.rcap, rn, rn);
+                (void)hipMemcpyAsync(scr.dlist2, keepcols.data(), sizeof(int32_t) * (size_t)rn, hipMemcpyHostToDevice, s);
+                hipLaunchKernelGGL(k_gather_sym, g2(rn, rn), dim3(T), 0, s, dep.CR, dep.rcap, scr.dlist2, rn, dep.CRw, dep.rcap);
+                hipLaunchKernelGGL(k_copy2d, g2(rn, rn), dim3(T), 0, s, dep.CRw, dep.rcap, dep.CR, dep.rcap, rn, rn);
                 // (a kept column's new index is never larger than its old one: chunks of new columns can be written in place)
-                for (int64_t c0 = 0; c0 < rn; c0 += b.kmax) {
-                    const int64_t cnt = std::min<int64_t>(b.kmax, rn - c0);
-                    hipLaunchKernelGGL(k_gather_cols, g2(f, cnt), dim3(T), 0, s, b.Y, b.cap, f, b.dlist2 + c0, cnt, b.B, b.cap);
-                    hipLaunchKernelGGL(k_copy2d, g2(f, cnt), dim3(T), 0, s, b.B, b.cap, b.Y + c0 * b.cap, b.cap, f, cnt);
+                for (int64_t c0 = 0; c0 < rn; c0 += fac.kmax) {
+                    const int64_t cnt = std::min<int64_t>(fac.kmax, rn - c0);
+                    hipLaunchKernelGGL(k_gather_cols, g2(f, cnt), dim3(T), 0, s, dep.Y, fac.cap, f, scr.dlist2 + c0, cnt, scr.B, fac.cap);
+                    hipLaunchKernelGGL(k_copy2d, g2(f, cnt), dim3(T), 0, s, scr.B, fac.cap, dep.Y + c0 * fac.cap, fac.cap, f, cnt);
                 }
-                (void)hipMemcpyAsync(b.dlist, newdead.data(), sizeof(int32_t) * (size_t)rn, hipMemcpyHostToDevice, s);
+                (void)hipMemcpyAsync(dep.dlist, newdead.data(), sizeof(int32_t) * (size_t)rn, hipMemcpyHostToDevice, s);
                 (void)hipStreamSynchronize(s);  // (the host vectors are temporaries)
             }
-            deadlist.swap(newdead);
-            b.r = rn;
+            dep.deadlist.swap(newdead);
+            dep.r = rn;
             const bool fine = factor_gram();
-            if (log) t_dead += wall() - t0;
+            if (log) sv.t_dead += sv.wall() - t0;
             return fine && blas_ok;
-        };
+        }
         // minimiser of the sub-problem on the splits that are in: xs = W^T (z - Y (Y^T Y)^-1 Y^T z), copied to `out`
-        auto solve = [&](std::vector<double>& out) -> bool {
-            const double t0 = log ? wall() : 0.0;
-            st_solves++;
-            const int64_t f = b.f, r = b.r;
+        bool solve(std::vector<double>& out) {
+            const double t0 = log ? sv.wall() : 0.0;
+            sv.st_solves++;
+            const int64_t f = fac.f, r = dep.r;
             out.assign((size_t)f, 0.0);
             if (f == 0) return true;
-            const double* vv = b.z;
+            const double* vv = fac.z;
             if (r > 0) {
-                gemv(rocblas_operation_transpose, f, r, 1.0, b.Y, b.cap, b.z, 0.0, b.lam);
-                gemv(rocblas_operation_none, r, r, 1.0, b.LC, b.rcap, b.lam, 0.0, b.sk1);       // (Y^T Y)^-1 = LC^T LC
-                gemv(rocblas_operation_transpose, r, r, 1.0, b.LC, b.rcap, b.sk1, 0.0, b.lam);
-                (void)hipMemcpyAsync(b.v, b.z, sizeof(double) * (size_t)f, hipMemcpyDeviceToDevice, s);
-                gemv(rocblas_operation_none, f, r, -1.0, b.Y, b.cap, b.lam, 1.0, b.v);
-                vv = b.v;
+                gemv(rocblas_operation_transpose, f, r, 1.0, dep.Y, fac.cap, fac.z, 0.0, dep.lam);
+                gemv(rocblas_operation_none, r, r, 1.0, dep.LC, dep.rcap, dep.lam, 0.0, scr.sk1);       // (Y^T Y)^-1 = LC^T LC
+                gemv(rocblas_operation_transpose, r, r, 1.0, dep.LC, dep.rcap, scr.sk1, 0.0, dep.lam);
+                (void)hipMemcpyAsync(scr.v, fac.z, sizeof(double) * (size_t)f, hipMemcpyDeviceToDevice, s);
+                gemv(rocblas_operation_none, f, r, -1.0, dep.Y, fac.cap, dep.lam, 1.0, scr.v);
+                vv = scr.v;
             }
-            for (int64_t q = 0, q0 = 0; q0 < f; q++, q0 += b.Ws.pw) {
-                const int64_t w = std::min(b.Ws.pw, f - q0);
-                gemv(rocblas_operation_transpose, f - q0, w, 1.0, b.Ws.panel(q), b.Ws.ld(q), vv + q0, 0.0, b.xs + q0);
+            for (int64_t q = 0, q0 = 0; q0 < f; q++, q0 += fac.Ws.pw) {
+                const int64_t w = std::min(fac.Ws.pw, f - q0);
+                gemv(rocblas_operation_transpose, f - q0, w, 1.0, fac.Ws.panel(q), fac.Ws.ld(q), vv + q0, 0.0, fac.xs + q0);
             }
-            (void)hipMemcpyAsync(out.data(), b.xs, sizeof(double) * (size_t)f, hipMemcpyDeviceToHost, s);
+            (void)hipMemcpyAsync(out.data(), fac.xs, sizeof(double) * (size_t)f, hipMemcpyDeviceToHost, s);
             (void)hipStreamSynchronize(s);
-            for (size_t p = 0; p < (size_t)f; p++) if (dead[p]) out[p] = 0.0;
-            if (log) t_solve += wall() - t0;
+            for (size_t p = 0; p < (size_t)f; p++) if (dep.dead[p]) out[p] = 0.0;
+            if (log) sv.t_solve += sv.wall() - t0;
             return blas_ok;
-        };
-        auto objective = [&](const std::vector<double>& xs) {
-            double acc = 0.0;
-            for (size_t p = 0; p < xs.size(); p++) if (!dead[p]) acc += cF[p] * xs[p];
-            return -0.5 * acc;
-        };
-        std::vector<double> sbuf;
+        }
+        // the members `out` leave, if the departed columns' buffers have room for them (false: no room, or the departure failed)
+        bool depart_counted(const std::vector<int32_t>& out, bool& no_room) {
+            no_room = dep.r + (int64_t)out.size() > dep.rcap;
+            if (no_room) return false;
+            sv.st_dels += (int64_t)out.size();
+            for (int32_t p : out) sv.st_dels_new += p >= pol.f_step0 ? 1 : 0;
+            return depart(out);
+        }
         // every weight that is not positive leaves, until the sub-problem's minimiser is feasible (false: out of room / failure)
-        bool over_rcap = false;  // settle_all failed for lack of room for the departed columns (not a numerical failure)
-        int64_t f_step0 = 0;     // (statistics: factor size before this step's block entered)
-        auto settle_all = [&]() -> bool {
-            over_rcap = false;
+        bool settle_all() {
+            pol.over_rcap = false;
             for (;;) {
                 if (!solve(sbuf)) return false;
                 std::vector<int32_t> out;
-                for (size_t p = 0; p < sbuf.size(); p++) if (!dead[p] && !(sbuf[p] > 0.0)) out.push_back((int32_t)p);
+                for (size_t p = 0; p < sbuf.size(); p++) if (!dep.dead[p] && !(sbuf[p] > 0.0)) out.push_back((int32_t)p);
                 if (out.empty()) return true;
-                if (b.r + (int64_t)out.size() > b.rcap) { over_rcap = true; return false; }
-                st_dels += (int64_t)out.size();
-                for (int32_t p : out) st_dels_new += p >= f_step0 ? 1 : 0;
-                if (!depart(out)) return false;
+                if (!depart_counted(out, pol.over_rcap)) return false;
             }
-        };
+        }
+        // Lawson & Hanson: as far towards the sub-problem's minimiser as feasibility allows; what reaches zero leaves
+        bool ratio_loop() {
+            std::vector<double> xcur = fac.xw;
+            std::vector<int32_t> out;
+            for (;;) {
+                if (!solve(sbuf)) return false;
+                if (ratio_step(xcur, sbuf, dep.dead, out) > 1.0) return true;
+                sv.st_ratio_steps++;
+                bool no_room = false;
+                if (!depart_counted(out, no_room)) { if (no_room) pol.force_rebuild = true; return false; }
+            }
+        }
 
-        const int64_t kmin = std::max<int64_t>(8, n / 32);
-        int64_t k_limit = b.kmax;
-        bool ratio_mode = false, done = false, good = ok, fresh = false, banned_rechecked = false;
-        // FNN_SW_REVIVE: 0 = departed splits only come back through a rebuild (round 3), 1 = at the start of every step, 2 = only when no
-        // candidate is left (the case that used to force a rebuild "to look again")
-        const int revive_mode = (int)envd("FNN_SW_REVIVE", 2.0);
-        const bool revive_on = revive_mode != 0;
-        const int64_t revive_min_f = (int64_t)envd("FNN_SW_REVIVE_MINF", 0.0);
-        bool revive_blocked = false;   // a step that only brought departed splits back did not descend: not again before a step moves
-        bool force_rebuild = false;    // a step ran out of room for its departed columns (taken back): rebuild before the next one
-
-        auto give = [&](int why, const char* text) { giveup = why; giveup_text = text; good = false; };
-        int stall = 0;  // steps in a row whose descent is not measurable (below 1e-13 |objective|)
-        const int64_t max_outer = 40 * (int64_t)n + 1000;
-        while (good && !done && st_lh_steps < max_outer) {
-            st_lh_steps++;
-            f_step0 = INT64_MAX;
-            // ---- multipliers: r = c - A^T A x on the grid; the entries at the factor's splits go to the host
-            double t0 = log ? wall() : 0.0;
-            (void)hipMemsetAsync(this->x, 0, sizeof(double) * (size_t)n * (size_t)ld, s);
-            if (b.f) {
-                (void)hipMemcpyAsync(b.xs, xw.data(), sizeof(double) * (size_t)b.f, hipMemcpyHostToDevice, s);
-                hipLaunchKernelGGL(k_scatter, g1(b.f), dim3(T), 0, s, b.dF, b.f, b.xs, this->x, ld);
-            }
-            Ab(this->x, y);
-            Atx(y, r);
-            std::vector<double> gF((size_t)b.f);
-            if (b.f) {
-                hipLaunchKernelGGL(k_gather, g1(b.f), dim3(T), 0, s, b.dF, b.f, r, ld, b.gF);
-                (void)hipMemcpyAsync(gF.data(), b.gF, sizeof(double) * (size_t)b.f, hipMemcpyDeviceToHost, s);
-            }
-            vec<OP_R_INIT>(r, nullptr, atwd, nullptr);  // r = masked ? 0 : c - r
-            if (log) t_ops += wall() - t0;
-            t0 = log ? wall() : 0.0;
-            (void)hipMemsetAsync(b.ccount, 0, sizeof(unsigned long long), s);
-            hipLaunchKernelGGL(k_candidates, grid2, dim3(T), 0, s, r, act, n, ld, tol, rad, b.ckey, b.cidx, b.ccount, (unsigned long long)b.ccap);
-            unsigned long long ncand64 = 0;
-            (void)hipMemcpyAsync(&ncand64, b.ccount, sizeof(ncand64), hipMemcpyDeviceToHost, s);
-            (void)hipStreamSynchronize(s);
-            const int64_t ncand = (int64_t)std::min<unsigned long long>(ncand64, (unsigned long long)b.ccap);
-            // (gF holds A^T A x at the factor's splits: c - gF is the multiplier of a split that left, the drift at one that is in)
-            double drift = 0.0, wdead = 0.0;
+        // ------------------------------------------------------------ the steps of the loop
+        struct Look {               // what step 1 sees
+            int64_t ncand = 0;      // local maxima of the multiplier above the threshold
+            double drift = 0.0;     // largest |multiplier| on the splits that are in
+            double wdead = 0.0;     // largest multiplier of a departed split
             int64_t dead_wanting = 0;
             std::vector<int32_t> rev;  // departed splits whose multiplier is positive again: they come back with this step (revive)
-            for (size_t p = 0; p < (size_t)b.f; p++) {
-                const double g = cF[p] - gF[p];
-                if (dead[p]) {
-                    wdead = std::max(wdead, g); dead_wanting += g > tol ? 1 : 0;
-                    // (FNN_SW_REVIVE_MINF: only from that many splits on - 8192 was tried: 82.2 s instead of 73.0 s at 32768 taxa)
-                    if (g > tol && revive_on && !revive_blocked && b.f >= revive_min_f) rev.push_back((int32_t)p);
-                } else drift = std::max(drift, std::fabs(g));
+            double t0 = 0.0;        // (FNN_SW_LOG: start of the selection phase)
+        };
+        // 1. multipliers: r = c - A^T A x on the grid; the entries at the factor's splits go to the host; the candidates
+        Look look() {
+            Look lk;
+            double t0 = log ? sv.wall() : 0.0;
+            weights_to_grid();
+            sv.Ab(sv.x, sv.y);
+            sv.Atx(sv.y, sv.r);
+            std::vector<double> gF((size_t)fac.f);
+            if (fac.f) {
+                hipLaunchKernelGGL(k_gather, g1(fac.f), dim3(T), 0, s, fac.dF, fac.f, sv.r, ld, fac.gF);
+                (void)hipMemcpyAsync(gF.data(), fac.gF, sizeof(double) * (size_t)fac.f, hipMemcpyDeviceToHost, s);
             }
-            st_dead_wanting += dead_wanting;
-            if (revive_mode == 2 && ncand != 0) rev.clear();
-            const int64_t nlive = b.f - b.r;
-            int64_t k = (int64_t)std::min<double>((double)b.kmax, std::max<double>((double)kmin, kfrac * (double)std::max<int64_t>(nlive, 1)));
-            k = std::max<int64_t>(1, std::min<int64_t>({k, ncand, k_limit}));
-            const bool no_cand = ncand == 0;
-            if (!no_cand && b.r == 0 && b.f + k > b.cap && b.f < b.cap) k = b.cap - b.f;  // (nothing to rebuild away: fill the factor to the brim first)
+            sv.vec<OP_R_INIT>(sv.r, nullptr, sv.atwd, nullptr);  // r = masked ? 0 : c - r
+            if (log) sv.t_ops += sv.wall() - t0;
+            lk.t0 = log ? sv.wall() : 0.0;
+            (void)hipMemsetAsync(cand.ccount, 0, sizeof(unsigned long long), s);
+            hipLaunchKernelGGL(k_candidates, sv.grid2, dim3(T), 0, s, sv.r, sv.act, n, ld, pol.tol, kn.nms, cand.ckey, cand.cidx, cand.ccount, (unsigned long long)cand.ccap);
+            unsigned long long ncand64 = 0;
+            (void)hipMemcpyAsync(&ncand64, cand.ccount, sizeof(ncand64), hipMemcpyDeviceToHost, s);
+            (void)hipStreamSynchronize(s);
+            lk.ncand = (int64_t)std::min<unsigned long long>(ncand64, (unsigned long long)cand.ccap);
+            // (gF holds A^T A x at the factor's splits: c - gF is the multiplier of a split that left, the drift at one that is in)
+            for (size_t p = 0; p < (size_t)fac.f; p++) {
+                const double g = fac.cF[p] - gF[p];
+                if (dep.dead[p]) {
+                    lk.wdead = std::max(lk.wdead, g); lk.dead_wanting += g > pol.tol ? 1 : 0;
+                    // (tried: returns only once the factor holds 8192 splits - 82.2 s instead of 73.0 s at 32768 taxa)
+                    if (g > pol.tol && kn.revive != 0 && !pol.revive_blocked) lk.rev.push_back((int32_t)p);
+                } else lk.drift = std::max(lk.drift, std::fabs(g));
+            }
+            sv.st_dead_wanting += lk.dead_wanting;
+            if (kn.revive == 2 && lk.ncand != 0) lk.rev.clear();
+            return lk;
+        }
+        // 2. the block size ...
+        int64_t block_size(const Look& lk) const {
+            const int64_t nlive = fac.f - dep.r;
+            int64_t k = (int64_t)std::min<double>((double)fac.kmax, std::max<double>((double)pol.kmin, kn.kfrac * (double)std::max<int64_t>(nlive, 1)));
+            k = std::max<int64_t>(1, std::min<int64_t>({k, lk.ncand, pol.k_limit}));
+            if (lk.ncand != 0 && dep.r == 0 && fac.f + k > fac.cap && fac.f < fac.cap) k = fac.cap - fac.f;  // (nothing to rebuild away: fill the factor to the brim first)
+            return k;
+        }
+        // ... and the rebuild rule: a split that left wants back in, the factor has drifted or is full of departed splits
+        bool rebuild_due(const Look& lk, int64_t k) const {
+            const bool no_cand = lk.ncand == 0;
             // (the drift of the gradient on the splits that are in: half of what the solver's own Kuhn-Tucker check allows at the end)
             // (departed splits in the factor: each costs every append 4 k f flops and every departure its share of the Gram matrix; a
             //  rebuild costs 2/3 f^3 - FNN_SW_RFRAC is the share of the factor at which the rebuild is taken)
-            const double r_limit = std::min(rfrac * (double)b.f, std::max(rfrac_buf * (double)b.f, (double)b.rcap - 1.5 * (double)k));
-            if ((no_cand && rev.empty() && (wdead > tol || (drift > 5e-10 * cmax && !fresh))) ||
-                (!no_cand && (b.f + k > b.cap || (double)(b.r - (int64_t)rev.size()) > r_limit || (force_rebuild && b.r > 0)))) {
-                force_rebuild = false;
-                // a split that left wants back in, the factor has drifted or is full of departed splits: rebuild it, solve, look again
-                if (!no_cand && b.r == 0) { give(FNN_SW_GIVEUP_CAPACITY, "the free set outgrew the dense factor"); break; }  // the caller decides about the reference's route
-                if (!refactor()) { give(FNN_SW_GIVEUP_NUMERIC, "rebuild of the factor failed"); break; }
-                if (!settle_all()) { give(over_rcap ? FNN_SW_GIVEUP_DEPARTED : FNN_SW_GIVEUP_NUMERIC, over_rcap ? "departed splits outgrew their buffers after a rebuild" : "sub-problem solve failed"); break; }
-                xw = sbuf; phi = objective(xw); fresh = true;
-                continue;
+            const double r_limit = std::min(kn.rfrac * (double)fac.f, std::max(pol.rfrac_buf * (double)fac.f, (double)dep.rcap - 1.5 * (double)k));
+            return (no_cand && lk.rev.empty() && (lk.wdead > pol.tol || (lk.drift > 5e-10 * pol.cmax && !pol.fresh))) ||
+                   (!no_cand && (fac.f + k > fac.cap || (double)(dep.r - (int64_t)lk.rev.size()) > r_limit || (pol.force_rebuild && dep.r > 0)));
+        }
+        // rebuild the factor, solve, look again
+        void rebuild(const Look& lk) {
+            pol.force_rebuild = false;
+            if (lk.ncand != 0 && dep.r == 0) { give(FNN_SW_GIVEUP_CAPACITY, "the free set outgrew the dense factor"); return; }  // the caller decides about the reference's route
+            if (!refactor()) { give(FNN_SW_GIVEUP_NUMERIC, "rebuild of the factor failed"); return; }
+            if (!settle_all()) { give(pol.over_rcap ? FNN_SW_GIVEUP_DEPARTED : FNN_SW_GIVEUP_NUMERIC, pol.over_rcap ? "departed splits outgrew their buffers after a rebuild" : "sub-problem solve failed"); return; }
+            fac.xw = sbuf; pol.phi = objective(fac.xw, fac.cF, dep.dead); pol.fresh = true;
+        }
+        // 3. no candidate left, nothing to bring back.  Splits that were set aside (numerically dependent on the factor at the time, or
+        // no measurable descent) are still masked: before the method may call this the optimum they get one more look against the
+        // current factor.
+        void no_candidate_left() {
+            if (!pol.banned.empty() && !pol.banned_rechecked) { set_mask(pol.banned, 0); pol.banned.clear(); pol.banned_rechecked = true; return; }
+            sv.n_set_aside = (int64_t)pol.banned.size();
+            done = true;
+        }
+        // The state a block that does not descend is taken back to (the appended rows are simply dropped)
+        struct Snapshot {
+            int64_t f0 = 0, r0 = 0;
+            std::vector<uint8_t> dead0;
+            std::vector<double> x0;
+            std::vector<int32_t> deadlist0;
+            void save(BlockMethod& m) {  // (the Gram matrix of the departed columns goes to its copy CRb)
+                f0 = m.fac.f; r0 = m.dep.r;
+                dead0 = m.dep.dead; x0 = m.fac.xw; deadlist0 = m.dep.deadlist;
+                if (r0 > 0) hipLaunchKernelGGL(k_copy2d, g2(r0, r0), dim3(T), 0, m.s, m.dep.CR, m.dep.rcap, m.dep.CRb, m.dep.rcap, r0, r0);
             }
-            if (no_cand && rev.empty()) {
-                // Splits that were set aside (numerically dependent on the factor at the time, or no measurable descent) are still
-                // masked: before the method may call this the optimum they get one more look against the current factor.
-                if (!banned.empty() && !banned_rechecked) { set_mask(banned, 0); banned.clear(); banned_rechecked = true; continue; }
-                n_set_aside = (int64_t)banned.size();
-                done = true; break;
+            bool restore(BlockMethod& m, bool revived) const {  // false: the Gram factor of the departed columns failed
+                Factor& fac = m.fac; Departed& dep = m.dep;
+                if (fac.f > f0) hipLaunchKernelGGL(k_mask, g1(fac.f - f0), dim3(T), 0, m.s, fac.dF + f0, fac.f - f0, m.sv.act, m.ld, (uint8_t)0);
+                fac.f = f0; dep.r = r0;
+                fac.F.resize((size_t)f0); dep.dead = dead0; fac.xw = x0; dep.deadlist = deadlist0; fac.cF.resize((size_t)f0);
+                if (r0 == 0) return true;
+                hipLaunchKernelGGL(k_copy2d, g2(r0, r0), dim3(T), 0, m.s, dep.CRb, dep.rcap, dep.CR, dep.rcap, r0, r0);
+                (void)hipMemcpyAsync(dep.dlist, dep.deadlist.data(), sizeof(int32_t) * (size_t)r0, hipMemcpyHostToDevice, m.s);
+                // (departed splits had come back with this step: Y's columns were compacted - fetch them from the factor again)
+                if (revived) hipLaunchKernelGGL(k_gather_cols_tri, g2(f0, r0), dim3(T), 0, m.s, fac.Ws, f0, dep.dlist, r0, dep.Y, fac.cap);
+                (void)hipStreamSynchronize(m.s);
+                return m.factor_gram();
             }
-            // ---- the block: the largest local maxima of the multiplier (none: a step that only brings departed splits back)
-            const int64_t f0 = b.f, r0 = b.r;
-            f_step0 = f0;
-            const std::vector<uint8_t> dead0 = dead;
-            const std::vector<double> x0 = xw;
-            const std::vector<int32_t> deadlist0 = deadlist;
-            if (r0 > 0) hipLaunchKernelGGL(k_copy2d, g2(r0, r0), dim3(T), 0, s, b.CR, b.rcap, b.CRb, b.rcap, r0, r0);
-            int64_t kin = 0;
-            int2 entered = make_int2(-1, -1);
-            if (!no_cand) {
-                if (hipcub::DeviceRadixSort::SortPairsDescending(b.sort_tmp, b.sort_bytes, b.ckey, b.ckey2, b.cidx, b.cidx2, (int)ncand, 0, 64, s) != hipSuccess) {
-                    give(FNN_SW_GIVEUP_NUMERIC, "candidate sort failed"); break;
-                }
-                hipLaunchKernelGGL(k_idx_to_split, g1(k), dim3(T), 0, s, b.cidx2, k, ld, b.dF + b.f);
-                F.resize((size_t)(b.f + k));
-                (void)hipMemcpyAsync(F.data() + b.f, b.dF + b.f, sizeof(int2) * (size_t)k, hipMemcpyDeviceToHost, s);
-                (void)hipStreamSynchronize(s);
-                // (tried: returns only for multipliers that would have made the block - fewer returns, but more one-split solves: 78.0 s
-                //  instead of 74.4 s at 32768 taxa)
-                if (log) t_sel += wall() - t0;
-                // ---- it enters, the weights that are not positive leave, the objective decides
-                const int2 first = F[(size_t)f0];
-                std::vector<int32_t> kept;
-                kin = append(k, b.ckey2, kept);
-                if (kin < 0) { give(FNN_SW_GIVEUP_NUMERIC, "append failed (BLAS / Cholesky)"); break; }
-                if (kin == 0) {  // the first split is numerically dependent on the factor: set it aside until progress is made
-                    F.resize((size_t)f0);
-                    banned.push_back(first); set_mask({first}, 1);
-                    if (rev.empty()) continue;
-                } else {
-                    for (int64_t q = 0; q < kin; q++) F[(size_t)(f0 + q)] = F[(size_t)(f0 + kept[(size_t)q])];
-                    F.resize((size_t)(f0 + kin));
-                    entered = F[(size_t)f0];
-                    hipLaunchKernelGGL(k_mask, g1(kin), dim3(T), 0, s, b.dF + f0, kin, act, ld, (uint8_t)1);
-                    st_adds += kin;
-                    xw.resize((size_t)b.f, 0.0); dead.resize((size_t)b.f, 0); cF.resize((size_t)b.f);
-                    hipLaunchKernelGGL(k_gather, g1(kin), dim3(T), 0, s, b.dF + f0, kin, atwd, ld, b.xs);
-                    (void)hipMemcpyAsync(cF.data() + f0, b.xs, sizeof(double) * (size_t)kin, hipMemcpyDeviceToHost, s);
-                    (void)hipStreamSynchronize(s);
-                }
+        };
+        struct Block { int64_t kin = 0; int2 entered = make_int2(-1, -1); bool proceed = true; };
+        // 4. the block enters: the k largest local maxima of the multiplier (none: a step that only brings departed splits back).
+        // proceed = false: the step ends here (a give-up, or the first split was set aside and nothing comes back)
+        Block enter(const Look& lk, int64_t k, int64_t f0) {
+            Block blk;
+            if (lk.ncand == 0) return blk;
+            blk.proceed = false;
+            if (hipcub::DeviceRadixSort::SortPairsDescending(cand.sort_tmp, cand.sort_bytes, cand.ckey, cand.ckey2, cand.cidx, cand.cidx2, (int)lk.ncand, 0, 64, s) != hipSuccess) {
+                give(FNN_SW_GIVEUP_NUMERIC, "candidate sort failed"); return blk;
             }
-            const bool revived = !rev.empty();
-            if (revived && !revive(rev)) { give(FNN_SW_GIVEUP_NUMERIC, "Gram factor of the departed columns failed"); break; }
-            bool feasible = true;
-            if (!ratio_mode) { feasible = settle_all(); if (!feasible && over_rcap) force_rebuild = true; }
-            else {  // Lawson & Hanson: as far towards the sub-problem's minimiser as feasibility allows; what reaches zero leaves
-                std::vector<double> xcur = xw;
-                for (;;) {
-                    if (!solve(sbuf)) { feasible = false; break; }
-                    double alpha = 2.0;
-                    for (size_t p = 0; p < sbuf.size(); p++)
-                        if (!dead[p] && !(sbuf[p] > 0.0)) alpha = std::min(alpha, xcur[p] / (xcur[p] - sbuf[p]));
-                    if (alpha > 1.0) break;
-                    st_ratio_steps++;
-                    std::vector<int32_t> out;
-                    for (size_t p = 0; p < sbuf.size(); p++) {
-                        if (dead[p]) continue;
-                        const bool neg = !(sbuf[p] > 0.0);
-                        const bool hit = neg && !(xcur[p] / (xcur[p] - sbuf[p]) > alpha);  // (0 / 0 counts as a hit)
-                        xcur[p] = hit ? 0.0 : xcur[p] + alpha * (sbuf[p] - xcur[p]);
-                        if (hit || (neg && !(xcur[p] > 0.0))) out.push_back((int32_t)p);
-                    }
-                    if (b.r + (int64_t)out.size() > b.rcap) { feasible = false; force_rebuild = true; break; }
-                    st_dels += (int64_t)out.size();
-                    for (int32_t p : out) st_dels_new += p >= f_step0 ? 1 : 0;
-                    if (!depart(out)) { feasible = false; break; }
-                }
+            hipLaunchKernelGGL(k_idx_to_split, g1(k), dim3(T), 0, s, cand.cidx2, k, ld, fac.dF + fac.f);
+            fac.F.resize((size_t)(fac.f + k));
+            (void)hipMemcpyAsync(fac.F.data() + fac.f, fac.dF + fac.f, sizeof(int2) * (size_t)k, hipMemcpyDeviceToHost, s);
+            (void)hipStreamSynchronize(s);
+            // (tried: returns only for multipliers that would have made the block - fewer returns, but more one-split solves: 78.0 s
+            //  instead of 74.4 s at 32768 taxa)
+            if (log) sv.t_sel += sv.wall() - lk.t0;
+            // ---- it enters, the weights that are not positive leave, the objective decides
+            const int2 first = fac.F[(size_t)f0];
+            std::vector<int32_t> kept;
+            blk.kin = append(k, cand.ckey2, kept);
+            if (blk.kin < 0) { give(FNN_SW_GIVEUP_NUMERIC, "append failed (BLAS / Cholesky)"); return blk; }
+            if (blk.kin == 0) {  // the first split is numerically dependent on the factor: set it aside until progress is made
+                fac.F.resize((size_t)f0);
+                pol.banned.push_back(first); set_mask({first}, 1);
+                blk.proceed = !lk.rev.empty();
+                return blk;
             }
-            if (!blas_ok) { give(FNN_SW_GIVEUP_NUMERIC, "a BLAS call failed"); break; }
-            f_peak = std::max(f_peak, b.f);
-            const double phi_new = feasible ? objective(sbuf) : INFINITY;
-            // Lawson & Hanson's step moves along the segment to the minimiser of a convex quadratic: it cannot ascend, so an
-            // "ascent" in the objective's last digits is rounding and the step is taken; the other step has to descend.
-            const double phi_eps = 1e-13 * std::fabs(phi);
-            if (!(ratio_mode ? phi_new < phi + phi_eps : phi_new < phi)) {  // no descent: the factor as it was before this block
-                st_rejects++;
-                if (log) std::fprintf(stderr, "  [sw] step %lld: block of %lld (+%lld departed splits back) at |F| = %lld taken back (%.17g vs %.17g)%s\n", (long long)st_lh_steps,
-                                      (long long)kin, (long long)rev.size(), (long long)(f0 - r0), phi_new, phi, ratio_mode ? " [ratio step]" : "");
-                if (b.f > f0) hipLaunchKernelGGL(k_mask, g1(b.f - f0), dim3(T), 0, s, b.dF + f0, b.f - f0, act, ld, (uint8_t)0);
-                b.f = f0; b.r = r0;
-                F.resize((size_t)f0); dead = dead0; xw = x0; deadlist = deadlist0; cF.resize((size_t)f0);
-                if (r0 > 0) {
-                    hipLaunchKernelGGL(k_copy2d, g2(r0, r0), dim3(T), 0, s, b.CRb, b.rcap, b.CR, b.rcap, r0, r0);
-                    (void)hipMemcpyAsync(b.dlist, deadlist.data(), sizeof(int32_t) * (size_t)r0, hipMemcpyHostToDevice, s);
-                    // (departed splits had come back with this step: Y's columns were compacted - fetch them from the factor again)
-                    if (revived) hipLaunchKernelGGL(k_gather_cols_tri, g2(f0, r0), dim3(T), 0, s, b.Ws, f0, b.dlist, r0, b.Y, b.cap);
-                    (void)hipStreamSynchronize(s);
-                    if (!factor_gram()) { give(FNN_SW_GIVEUP_NUMERIC, "Gram factor of the departed columns failed"); break; }
-                }
-                if (revived) revive_blocked = true;    // (no returns again before a step has moved)
-                if (revived && kin == 0) continue;     // (nothing had entered: only the returns are taken back)
-                // the same block once more with Lawson & Hanson's step, which cannot ascend; if that made no progress either (rounding
-                // noise at this level): a quarter of the block, and a single split that does not move is set aside
-                if (ratio_mode) {
-                    if (kin == 1) {
-                        // One split, the step that cannot ascend, and still no descent: the objective no longer resolves what this
-                        // multiplier is worth.  If the block's largest multiplier is below 1e-10 max|A^T d| (a tenth of what the
-                        // Kuhn-Tucker certificate of the tests allows), that level IS the noise floor of this problem - tree-like
-                        // distances at 32768 taxa: objective 9e10, changes in its 14th digit, thousands of such candidates, each
-                        // worth a step - and becomes the candidates' threshold; a larger one is set aside until a step moves.
-                        double wtop = 0.0;
-                        (void)hipMemcpyAsync(&wtop, b.ckey2, sizeof(double), hipMemcpyDeviceToHost, s);
-                        (void)hipStreamSynchronize(s);
-                        if (wtop <= tol_cap) {
-                            if (log) std::fprintf(stderr, "  [sw] noise floor: candidates' threshold %.3g -> %.3g (%.3g max|A^T d|)\n", tol, wtop, wtop / (cmax > 0.0 ? cmax : 1.0));
-                            tol = std::max(tol, wtop);
-                        } else {
-                            banned.push_back(entered); set_mask({entered}, 1);
-                        }
-                    }
-                    k_limit = std::max<int64_t>(1, kin / 4);
-                } else {
-                    ratio_mode = true; k_limit = kin;
-                }
-                continue;
-            }
-            const bool moved = phi - phi_new > phi_eps;  // (a descent in the last digits is not progress)
-            phi = phi_new; xw = sbuf; fresh = false;
-            stall = moved ? 0 : stall + 1;
-            if (stall >= 8) {
-                // Eight steps that the objective cannot tell apart: the candidates' multipliers are at the noise floor of this
-                // problem (tree-like distances at 32768 taxa: objective 9e10, thousands of candidates around 1e-11 max|A^T d|,
-                // each good for a step in the 14th digit).  Their level becomes the candidates' threshold, as long as it is
-                // below 1e-10 max|A^T d| (a tenth of what the tests' Kuhn-Tucker certificate allows); above that only after
-                // 200 such steps, with a line in the log, so that the method ends.
-                double wtop = 0.0;
-                (void)hipMemcpyAsync(&wtop, b.ckey2, sizeof(double), hipMemcpyDeviceToHost, s);
-                (void)hipStreamSynchronize(s);
-                if (wtop <= tol_cap || stall >= 200) {
-                    if (log || wtop > tol_cap) std::fprintf(stderr, "  [sw] noise floor after %d steps without measurable descent: candidates' threshold %.3g -> %.3g (%.3g max|A^T d|)\n",
-                                                            stall, tol, wtop, wtop / (cmax > 0.0 ? cmax : 1.0));
-                    tol = std::max(tol, wtop);
-                    stall = 0;
-                }
-            }
-            k_limit = k_limit > b.kmax / 2 ? b.kmax : 2 * k_limit;
+            const int64_t kin = blk.kin;
+            for (int64_t q = 0; q < kin; q++) fac.F[(size_t)(f0 + q)] = fac.F[(size_t)(f0 + kept[(size_t)q])];
+            fac.F.resize((size_t)(f0 + kin));
+            blk.entered = fac.F[(size_t)f0];
+            hipLaunchKernelGGL(k_mask, g1(kin), dim3(T), 0, s, fac.dF + f0, kin, sv.act, ld, (uint8_t)1);
+            sv.st_adds += kin;
+            fac.xw.resize((size_t)fac.f, 0.0); dep.dead.resize((size_t)fac.f, 0); fac.cF.resize((size_t)fac.f);
+            hipLaunchKernelGGL(k_gather, g1(kin), dim3(T), 0, s, fac.dF + f0, kin, sv.atwd, ld, fac.xs);
+            (void)hipMemcpyAsync(fac.cF.data() + f0, fac.xs, sizeof(double) * (size_t)kin, hipMemcpyDeviceToHost, s);
+            (void)hipStreamSynchronize(s);
+            blk.proceed = true;
+            return blk;
+        }
+        // 5. the two ways to feasibility: all weights that are not positive leave at once, or Lawson & Hanson's ratio step
+        bool make_feasible() {
+            if (pol.ratio_mode) return ratio_loop();
+            const bool feasible = settle_all();
+            if (!feasible && pol.over_rcap) pol.force_rebuild = true;
+            return feasible;
+        }
+        // The candidates' threshold rises to the block's largest multiplier - the noise floor of this problem - if that is below tol_cap,
+        // or if `forced`.  false: it is above, and the threshold stays.  (stalled: the steps without measurable descent, 0: a single split)
+        bool noise_floor(int stalled, bool forced) {
+            double wtop = 0.0;
+            (void)hipMemcpyAsync(&wtop, cand.ckey2, sizeof(double), hipMemcpyDeviceToHost, s);
+            (void)hipStreamSynchronize(s);
+            if (!(wtop <= pol.tol_cap || forced)) return false;
+            const double rel = wtop / (pol.cmax > 0.0 ? pol.cmax : 1.0);
+            if (stalled) {
+                if (log || wtop > pol.tol_cap) std::fprintf(stderr, "  [sw] noise floor after %d steps without measurable descent: candidates' threshold %.3g -> %.3g (%.3g max|A^T d|)\n",
+                                                            stalled, pol.tol, wtop, rel);
+            } else if (log) std::fprintf(stderr, "  [sw] noise floor: candidates' threshold %.3g -> %.3g (%.3g max|A^T d|)\n", pol.tol, wtop, rel);
+            pol.tol = std::max(pol.tol, wtop);
+            return true;
+        }
+        // 6. no descent: the factor as it was before this block, and what the next step does differently
+        void take_back(const Look& lk, const Block& blk, const Snapshot& snap, bool revived, double phi_new) {
+            const int64_t kin = blk.kin;
+            sv.st_rejects++;
+            if (log) std::fprintf(stderr, "  [sw] step %lld: block of %lld (+%lld departed splits back) at |F| = %lld taken back (%.17g vs %.17g)%s\n", (long long)sv.st_lh_steps,
+                                  (long long)kin, (long long)lk.rev.size(), (long long)(snap.f0 - snap.r0), phi_new, pol.phi, pol.ratio_mode ? " [ratio step]" : "");
+            if (!snap.restore(*this, revived)) { give(FNN_SW_GIVEUP_NUMERIC, "Gram factor of the departed columns failed"); return; }
+            if (revived) pol.revive_blocked = true;    // (no returns again before a step has moved)
+            if (revived && kin == 0) return;           // (nothing had entered: only the returns are taken back)
+            // the same block once more with Lawson & Hanson's step, which cannot ascend; if that made no progress either (rounding
+            // noise at this level): a quarter of the block, and a single split that does not move is set aside
+            if (!pol.ratio_mode) { pol.ratio_mode = true; pol.k_limit = kin; return; }
+            // One split, the step that cannot ascend, and still no descent: the objective no longer resolves what this
+            // multiplier is worth.  If the block's largest multiplier is below 1e-10 max|A^T d| (a tenth of what the
+            // Kuhn-Tucker certificate of the tests allows), that level IS the noise floor of this problem - tree-like
+            // distances at 32768 taxa: objective 9e10, changes in its 14th digit, thousands of such candidates, each
+            // worth a step - and becomes the candidates' threshold; a larger one is set aside until a step moves.
+            if (kin == 1 && !noise_floor(0, false)) { pol.banned.push_back(blk.entered); set_mask({blk.entered}, 1); }
+            pol.k_limit = std::max<int64_t>(1, kin / 4);
+        }
+        // 7. the step is taken
+        void accept(const Look& lk, const Block& blk, double phi_new, double phi_eps) {
+            const bool moved = pol.phi - phi_new > phi_eps;  // (a descent in the last digits is not progress)
+            pol.phi = phi_new; fac.xw = sbuf; pol.fresh = false;
+            pol.stall = moved ? 0 : pol.stall + 1;
+            // Eight steps that the objective cannot tell apart: the candidates' multipliers are at the noise floor of this
+            // problem (tree-like distances at 32768 taxa: objective 9e10, thousands of candidates around 1e-11 max|A^T d|,
+            // each good for a step in the 14th digit).  Their level becomes the candidates' threshold, as long as it is
+            // below 1e-10 max|A^T d| (a tenth of what the tests' Kuhn-Tucker certificate allows); above that only after
+            // 200 such steps, with a line in the log, so that the method ends.
+            if (pol.stall >= 8 && noise_floor(pol.stall, pol.stall >= 200)) pol.stall = 0;
+            pol.k_limit = pol.k_limit > fac.kmax / 2 ? fac.kmax : 2 * pol.k_limit;
             // near the end (few candidates, each displacing one split) the guaranteed step stays on.  (Tried, round 4: the guaranteed step
             // only for the retry of a block that did not descend, and for eight steps after three such blocks in a row - 75.6 s instead
             // of 73.0 s at 32768 taxa, 13.9 s instead of 13.4 s at 16384: the method's path is sensitive to such rules, +-10 %.)
-            ratio_mode = ratio_mode && ncand <= 2 * kmin;
-            if (moved) revive_blocked = false;
-            if (moved) banned_rechecked = false;
-            if (moved && !banned.empty()) { set_mask(banned, 0); banned.clear(); }  // progress: the splits set aside may be looked at again
-            if (log && (st_lh_steps % 10 == 0 || st_lh_steps < 5))
+            pol.ratio_mode = pol.ratio_mode && lk.ncand <= 2 * pol.kmin;
+            if (moved) pol.revive_blocked = false;
+            if (moved) pol.banned_rechecked = false;
+            if (moved && !pol.banned.empty()) { set_mask(pol.banned, 0); pol.banned.clear(); }  // progress: the splits set aside may be looked at again
+            if (log && (sv.st_lh_steps % 10 == 0 || sv.st_lh_steps < 5))
                 std::fprintf(stderr, "  [sw] step %lld: |F| = %lld (+%lld departed in the factor) candidates %lld block %lld solves %lld objective %.12g | ops %.2f sel %.2f "
-                             "append %.2f solve %.2f depart %.2f refactor %.2f s\n", (long long)st_lh_steps, (long long)(b.f - b.r), (long long)b.r, (long long)ncand,
-                             (long long)kin, (long long)st_solves, phi, t_ops, t_sel, t_append, t_solve, t_dead, t_refactor);
+                             "append %.2f solve %.2f depart %.2f refactor %.2f s\n", (long long)sv.st_lh_steps, (long long)(fac.f - dep.r), (long long)dep.r, (long long)lk.ncand,
+                             (long long)blk.kin, (long long)sv.st_solves, pol.phi, sv.t_ops, sv.t_sel, sv.t_append, sv.t_solve, sv.t_dead, sv.t_refactor);
         }
-        if (!done && good) give(FNN_SW_GIVEUP_STEPS, "step limit reached");
-        final_tol_rel = tol / (cmax > 0.0 ? cmax : 1.0);
-        have_atwd = true;
-        if (good) {  // the optimum on the grid
-            (void)hipMemsetAsync(this->x, 0, sizeof(double) * (size_t)n * (size_t)ld, s);
-            if (b.f) {
-                (void)hipMemcpyAsync(b.xs, xw.data(), sizeof(double) * (size_t)b.f, hipMemcpyHostToDevice, s);
-                hipLaunchKernelGGL(k_scatter, g1(b.f), dim3(T), 0, s, b.dF, b.f, b.xs, this->x, ld);
+        void log_summary() const {
+            std::fprintf(stderr, "  [sw] %s: %lld steps, %lld solves, %lld entered (%lld screened out before), %lld left, %lld taken back, %lld ratio steps, %lld factorisations; |F| = %lld | ops %.2f "
+                         "sel %.2f append %.2f solve %.2f depart %.2f refactor %.2f s\n", good ? "done" : "gave up", (long long)sv.st_lh_steps, (long long)sv.st_solves,
+                         (long long)sv.st_adds, (long long)sv.st_screened, (long long)sv.st_dels, (long long)sv.st_rejects, (long long)sv.st_ratio_steps, (long long)sv.st_lh_refactor, (long long)(fac.f - dep.r),
+                         sv.t_ops, sv.t_sel, sv.t_append, sv.t_solve, sv.t_dead, sv.t_refactor);
+            std::fprintf(stderr, "  [sw]   GEMM work through gemm(): %.3e flop; departed splits with a positive multiplier, summed over the steps: %lld; brought back: %lld; "
+                         "departures of splits in the step they entered: %lld\n", sv.gemm_flops, (long long)sv.st_dead_wanting, (long long)sv.st_revived, (long long)sv.st_dels_new);
+            for (const auto& kv : sv.tsub) std::fprintf(stderr, "  [sw]   %-28s %8.3f s\n", kv.first.c_str(), kv.second);
+        }
+
+        // true: the optimum's weights are on the grid sv.x; false: sv.giveup says why not
+        bool run() {
+            if (!setup()) return false;
+            start();
+            Snapshot snap;
+            const int64_t max_outer = 40 * (int64_t)n + 1000;
+            while (good && !done && sv.st_lh_steps < max_outer) {  // (st_lh_steps counts over the attempts of a call, as the other counters do)
+                sv.st_lh_steps++;
+                pol.f_step0 = INT64_MAX;
+                const Look lk = look();                                                   // 1. multipliers and candidates
+                const int64_t k = block_size(lk);                                         // 2. the block size; the rebuild where it is due
+                if (rebuild_due(lk, k)) { rebuild(lk); continue; }
+                if (lk.ncand == 0 && lk.rev.empty()) { no_candidate_left(); continue; }   // 3. no candidate left
+                snap.save(*this);
+                pol.f_step0 = snap.f0;
+                const Block blk = enter(lk, k, snap.f0);                                  // 4. the block enters
+                if (!blk.proceed) continue;
+                const bool revived = !lk.rev.empty();
+                if (revived && !revive(lk.rev)) { give(FNN_SW_GIVEUP_NUMERIC, "Gram factor of the departed columns failed"); continue; }
+                const bool feasible = make_feasible();                                    // 5. to feasibility
+                if (!blas_ok) { give(FNN_SW_GIVEUP_NUMERIC, "a BLAS call failed"); continue; }
+                sv.f_peak = std::max(sv.f_peak, fac.f);
+                const double phi_new = feasible ? objective(sbuf, fac.cF, dep.dead) : INFINITY;
+                // Lawson & Hanson's step moves along the segment to the minimiser of a convex quadratic: it cannot ascend, so an
+                // "ascent" in the objective's last digits is rounding and the step is taken; the other step has to descend.
+                const double phi_eps = 1e-13 * std::fabs(pol.phi);
+                if (!(pol.ratio_mode ? phi_new < pol.phi + phi_eps : phi_new < pol.phi)) take_back(lk, blk, snap, revived, phi_new);  // 6. no descent
+                else accept(lk, blk, phi_new, phi_eps);                                   // 7. acceptance
             }
-            (void)hipStreamSynchronize(s);
+            if (!done && good) give(FNN_SW_GIVEUP_STEPS, "step limit reached");
+            sv.final_tol_rel = pol.tol / (pol.cmax > 0.0 ? pol.cmax : 1.0);
+            sv.have_atwd = true;
+            if (good) {  // the optimum on the grid
+                weights_to_grid();
+                (void)hipStreamSynchronize(s);
+            }
+            if (log) log_summary();
+            return good;
         }
-        if (log) std::fprintf(stderr, "  [sw] %s: %lld steps, %lld solves, %lld entered (%lld screened out before), %lld left, %lld taken back, %lld ratio steps, %lld factorisations; |F| = %lld | ops %.2f "
-                              "sel %.2f append %.2f solve %.2f depart %.2f refactor %.2f s\n", good ? "done" : "gave up", (long long)st_lh_steps, (long long)st_solves,
-                              (long long)st_adds, (long long)st_screened, (long long)st_dels, (long long)st_rejects, (long long)st_ratio_steps, (long long)st_lh_refactor, (long long)(b.f - b.r),
-                              t_ops, t_sel, t_append, t_solve, t_dead, t_refactor);
-        if (log) std::fprintf(stderr, "  [sw]   GEMM work through gemm(): %.3e flop; departed splits with a positive multiplier, summed over the steps: %lld; brought back: %lld; "
-                              "departures of splits in the step they entered: %lld\n", gemm_flops, (long long)st_dead_wanting, (long long)st_revived, (long long)st_dels_new);
-        if (log) for (const auto& kv : tsub) std::fprintf(stderr, "  [sw]   %-28s %8.3f s\n", kv.first.c_str(), kv.second);
-        return good;
-    }
+    };
 
     // runActiveConjugate (:366-557)
     void active_conjugate() {
@@ -1657,10 +1700,37 @@ struct Solver {
 
 }  // namespace fnnsw
 
+// The caller's statistics.  done == nullptr: the block method gave up (written before the call fails or the reference's route
+// starts) - what it counted, zeros elsewhere; else the call's normal end.
+struct Outcome { int route; int64_t npos; bool certified; double viol, t_solve_s; };
+static void fill_stats(fnn_sw_stats* stats, const fnnsw::Solver& S, const Outcome* done) {
+    if (!stats) return;
+    std::memset(stats, 0, sizeof(*stats));
+    const bool from_below = done && done->route == FNN_SW_ROUTE_FROM_BELOW;
+    stats->giveup_reason = S.giveup; stats->capacity = S.capacity; stats->free_set_peak = S.f_peak;
+    stats->outer_iterations = (!done || from_below) ? S.st_lh_steps : S.st_outer;
+    stats->entered = S.st_adds; stats->screened_out = S.st_screened; stats->departed = S.st_dels;
+    if (!done) return;
+    stats->cg_calls = S.st_cg;
+    stats->cg_iterations = S.st_it;
+    stats->reserved[0] = from_below ? 1 : 0;        // method: 1 = from below (block active-set, dense factor), 0 = the reference's (or the closed form)
+    stats->reserved[1] = S.st_lh_refactor;
+    stats->reserved[2] = S.st_solves;               // sub-problems solved (from below)
+    stats->t_solve_s = done->t_solve_s;
+    stats->nsplits = done->npos;                    // weights above the threshold (FastNN.java:455: 1e-6; the sparse call: its own)
+    stats->route = done->route;
+    stats->certified = done->certified ? 1 : 0;
+    stats->kkt_violation = done->viol;
+    stats->final_threshold_rel = from_below ? S.final_tol_rel : 0.0;
+    stats->n_set_aside = from_below ? S.n_set_aside : 0;
+    stats->t_alloc_s = S.t_alloc_s;
+}
+
 // weights_out != nullptr: all n (n - 1) / 2 weights; else the weights above `thr` as (index, weight) pairs in index order
 static int32_t split_weights_impl(const double* D, int32_t n, int64_t ldD, const int32_t* ordering, int32_t device, double* weights_out,
                                   double thr, int64_t* idx_out, double* w_out, int64_t cap_out, int64_t* count_out, fnn_sw_stats* stats) {
     using namespace fnnsw;
+    const Knobs kn = Knobs::from_env();  // every FNN_SW_* switch of this file, read once per call
     if (!D || !ordering || n < 2 || ldD < n || (!weights_out && (!idx_out || !w_out || !count_out || cap_out < 0)))
         return fnn::fail(FNN_EINVAL, "fnn_split_weights_f64: bad arguments");
     {
@@ -1717,7 +1787,7 @@ static int32_t split_weights_impl(const double* D, int32_t n, int64_t ldD, const
     int route = FNN_SW_ROUTE_CLOSED_FORM;
     hipLaunchKernelGGL(k_unconstrained, dim3((unsigned)((n + T - 1) / T), (unsigned)n), dim3(T), 0, S.s, S.d, S.x, n, S.ld);
     if (S.reduce_sum<RD_COUNT_NEG>(S.x, nullptr) != 0.0) {
-        const bool want_reference = std::getenv("FNN_SW_REFERENCE_METHOD") != nullptr;
+        const bool want_reference = kn.reference_method;
         // The block method's factor is sized for the common case (random or tree-like distances: 2.4 n ... 3.8 n positive splits) so
         // that small problems do not pay for a 100-GB allocation; distances whose optimum has more positive splits (nearly
         // circular metrics: measured 19.5 n at 1024 taxa with 1 % noise) outgrow it: try again with four times the capacity, up to
@@ -1726,8 +1796,11 @@ static int32_t split_weights_impl(const double* D, int32_t n, int64_t ldD, const
         if (!want_reference) {
             const int64_t Nall = (int64_t)n * (n - 1) / 2;
             for (int attempt = 0; attempt < 6; attempt++) {
-                from_below = S.block_active_set();
-                if (from_below || S.giveup != FNN_SW_GIVEUP_CAPACITY || S.capacity >= Nall || std::getenv("FNN_SW_CAP")) break;
+                {   // (its rocBLAS handle and the handle's workspace are gone before the free memory is read for another attempt)
+                    Solver::BlockMethod attempt_(S, kn);
+                    from_below = attempt_.run();
+                }
+                if (from_below || S.giveup != FNN_SW_GIVEUP_CAPACITY || S.capacity >= Nall || kn.cap_set) break;
                 const int64_t prev = S.capacity;
                 S.release_block_buffers();
                 S.cap_want = std::min<int64_t>(Nall, 4 * prev);
@@ -1747,20 +1820,15 @@ static int32_t split_weights_impl(const double* D, int32_t n, int64_t ldD, const
             if (!want_reference) {
                 // The block method gave up.  Say so, always: the route that follows is the reference's own - correct, but
                 // O(n^2) work per conjugate-gradient iteration and thousands of iterations on large problems.
-                int64_t max_n = 1024;  // (measured: a 1024-taxon nearly circular input takes 80 s on that route, 2048 taxa more than 5 min)
-                if (const char* e = std::getenv("FNN_SW_REFERENCE_MAX_N")) max_n = std::atoll(e);
-                const bool allow = std::getenv("FNN_SW_ALLOW_REFERENCE_ROUTE") != nullptr || n <= max_n;
+                // (the default of FNN_SW_REFERENCE_MAX_N, 1024, measured: a 1024-taxon nearly circular input takes 80 s on that route, 2048 taxa more than 5 min)
+                const bool allow = kn.allow_reference || n <= kn.reference_max_n;
                 std::fprintf(stderr, "fnn_split_weights_f64: the block active-set method gave up at n = %d (%s; capacity %lld splits, free set peaked at %lld): %s\n",
                              n, S.giveup_text, (long long)S.capacity, (long long)S.f_peak,
-                             std::getenv("FNN_SW_NO_REFERENCE_ROUTE") ? "FNN_SW_NO_REFERENCE_ROUTE is set"
+                             kn.no_reference ? "FNN_SW_NO_REFERENCE_ROUTE is set"
                              : allow ? "taking the reference's active-set / conjugate-gradient route"
                                      : "the reference's conjugate-gradient route is not taken automatically above FNN_SW_REFERENCE_MAX_N taxa");
-                if (stats) {
-                    std::memset(stats, 0, sizeof(*stats));
-                    stats->giveup_reason = S.giveup; stats->capacity = S.capacity; stats->free_set_peak = S.f_peak;
-                    stats->outer_iterations = S.st_lh_steps; stats->entered = S.st_adds; stats->screened_out = S.st_screened; stats->departed = S.st_dels;
-                }
-                if (std::getenv("FNN_SW_NO_REFERENCE_ROUTE") || !allow) {
+                fill_stats(stats, S, nullptr);
+                if (kn.no_reference || !allow) {
                     const bool cap = S.giveup == FNN_SW_GIVEUP_CAPACITY || S.giveup == FNN_SW_GIVEUP_DEPARTED || S.giveup == FNN_SW_GIVEUP_SETUP;
                     return fnn::fail(cap ? FNN_ECAPACITY : FNN_EHIP,
                                      std::string("fnn_split_weights_f64: the block active-set method gave up (") + S.giveup_text + "); the optimum of these distances has more "
@@ -1777,7 +1845,7 @@ static int32_t split_weights_impl(const double* D, int32_t n, int64_t ldD, const
             S.have_atwd = true;
         }
     }
-    if (std::getenv("FNN_SW_FAULT_PERTURB")) hipLaunchKernelGGL(k_fault_perturb, dim3(1), dim3(1), 0, S.s, S.x, n, S.ld);
+    if (kn.fault_perturb) hipLaunchKernelGGL(k_fault_perturb, dim3(1), dim3(1), 0, S.s, S.x, n, S.ld);
     hipLaunchKernelGGL(k_to_live, S.grid2, dim3(T), 0, S.s, S.x, S.live, n, S.ld);
     (void)hipEventRecord(ev.e1, S.s);
     // The solver's own Kuhn-Tucker check of what it returns: g = A^T (A x - d) from the implicit operators, which share
@@ -1833,28 +1901,8 @@ static int32_t split_weights_impl(const double* D, int32_t n, int64_t ldD, const
             for (int64_t q = 0; q < take; q++) { idx_out[q] = hi[(size_t)perm[(size_t)q]]; w_out[q] = hw[(size_t)perm[(size_t)q]]; }
         }
     }
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        const bool from_below = route == FNN_SW_ROUTE_FROM_BELOW;
-        stats->outer_iterations = from_below ? S.st_lh_steps : S.st_outer;
-        stats->cg_calls = S.st_cg;
-        stats->cg_iterations = S.st_it;
-        stats->reserved[0] = from_below ? 1 : 0;        // method: 1 = from below (block active-set, dense factor), 0 = the reference's (or the closed form)
-        stats->reserved[1] = S.st_lh_refactor;
-        stats->reserved[2] = S.st_solves;               // sub-problems solved (from below)
-        stats->t_solve_s = ms * 1e-3;
-        stats->nsplits = npos;                          // weights above the threshold (FastNN.java:455: 1e-6; the sparse call: its own)
-        stats->route = route;
-        stats->certified = certified ? 1 : 0;
-        stats->kkt_violation = viol;
-        stats->final_threshold_rel = from_below ? S.final_tol_rel : 0.0;
-        stats->n_set_aside = from_below ? S.n_set_aside : 0;
-        stats->capacity = S.capacity;
-        stats->free_set_peak = S.f_peak;
-        stats->giveup_reason = S.giveup;
-        stats->entered = S.st_adds; stats->screened_out = S.st_screened; stats->departed = S.st_dels;
-        stats->t_alloc_s = S.t_alloc_s;
-    }
+    const Outcome outcome{route, npos, certified, viol, ms * 1e-3};
+    fill_stats(stats, S, &outcome);
     if (route == FNN_SW_ROUTE_FROM_BELOW && !certified) {
         char buf[320];
         std::snprintf(buf, sizeof(buf), "fnn_split_weights_f64: the weights fail the Kuhn-Tucker check: violation %.3g of max|A^T d| (min x %.3g, gradient on positive weights %.3g, "
