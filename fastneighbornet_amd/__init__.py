@@ -64,6 +64,7 @@ def api() -> _capi.Api:
         _capi.bind_splits_batch(a)  # fnn_split_weights_batch_max_n, fnn_split_weights_batch_f64, fnn_split_weights_batch_device_f64
         _capi.bind_ragged(a)  # fnn_canonical_order_ragged[_device]_f64, fnn_split_weights_ragged[_device]_f64
         _capi.bind_dist(a)  # fnn_alignment_distances_batch[_device]_f64, fnn_bootstrap_counts
+        _capi.bind_dist_model(a)  # fnn_alignment_distances_model_batch[_device]_f64
         _capi.bind_support(a)  # fnn_split_support[_device]_f64, fnn_split_keys, fnn_split_support_max_n / _min_work
         _api = a
     return _api

@@ -253,6 +253,51 @@ def run_dist(a: Api, seq, n: int, L: int, lds: int, counts, batch: int, ldc: int
     return st
 
 
+class FnnDistModel(C.Structure):
+    _fields_ = [("model", C.c_int32), ("states", C.c_int32), ("on_saturation", C.c_int32), ("reserved", C.c_int32), ("cap", C.c_double)]
+
+
+class FnnDistModelStats(C.Structure):
+    _fields_ = [("base", FnnDistStats), ("n_recoded", C.c_int64), ("n_saturated_problems", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+    def as_dict(self):
+        return dict(self.base.as_dict(), n_recoded=self.n_recoded, n_saturated_problems=self.n_saturated_problems)
+
+
+DIST_JC69, DIST_K2P = 1, 2
+DIST_SAT_FAIL, DIST_SAT_CAP = 0, 1
+DIST_MODELS = {"p": DIST_P, "jc69": DIST_JC69, "k2p": DIST_K2P}
+DIST_POLICIES = {"fail": DIST_SAT_FAIL, "cap": DIST_SAT_CAP}
+_DIST_MODEL_ARGS = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(FnnDistModel), C.c_int32,
+                    C.c_void_p, C.c_int64, C.c_int64, C.POINTER(FnnDistModelStats)]
+
+
+def bind_dist_model(a: Api) -> Api:
+    """The entry points of the corrected alignment distances of include/fastnn.h (JC69, K2P) on `a`."""
+    a._fn("alignment_distances_model_batch_f64", C.c_int32, _DIST_MODEL_ARGS)
+    a._fn("alignment_distances_model_batch_device_f64", C.c_int32, _DIST_MODEL_ARGS)
+    return a
+
+
+def dist_model(model="p", states: int = 4, on_saturation="fail", cap=None) -> FnnDistModel:
+    """fnn_dist_model from names ("p", "jc69", "k2p"; "fail", "cap") or the header's numbers; cap=None is 0.0."""
+    m = FnnDistModel()
+    m.model = DIST_MODELS[model.lower()] if isinstance(model, str) else int(model)
+    m.states = int(states)
+    m.on_saturation = DIST_POLICIES[on_saturation.lower()] if isinstance(on_saturation, str) else int(on_saturation)
+    m.cap = 0.0 if cap is None else float(cap)
+    return m
+
+
+def run_dist_model(a: Api, seq, n: int, L: int, lds: int, counts, batch: int, ldc: int, out, ld: int, stride: int, m: FnnDistModel,
+                   device: int = 0, on_device: bool = False):
+    """`run_dist` through the model entries; m=None passes NULL.  Returns the stats (FnnDistModelStats)."""
+    st = FnnDistModelStats()
+    fn = a.alignment_distances_model_batch_device_f64 if on_device else a.alignment_distances_model_batch_f64
+    a.check(fn(seq, n, L, lds, counts, batch, ldc, C.byref(m) if m is not None else None, device, out, ld, stride, C.byref(st)))
+    return st
+
+
 def run_bootstrap_counts(a: Api, L: int, batch: int, seed: int) -> np.ndarray:
     counts = np.zeros((max(batch, 0), max(L, 0)), dtype=np.uint16)
     a.check(a.bootstrap_counts(L, batch, seed & 0xFFFFFFFFFFFFFFFF, counts.ctypes.data))

@@ -363,40 +363,55 @@ def _dist_inputs(seq, counts):
     return seq, counts
 
 
-def alignment_distances_batch(seq, counts, device: int = 0, out: str = "numpy"):
-    """p-distance matrices of the replicates `counts` (uint16 (B, L) site multiplicities) of the alignment `seq` (uint8 (n, L),
+def alignment_distances_batch(seq, counts, device: int = 0, out: str = "numpy", model: str = "p", states: int = 4,
+                              on_saturation: str = "fail", cap=None):
+    """Distance matrices of the replicates `counts` (uint16 (B, L) site multiplicities) of the alignment `seq` (uint8 (n, L),
     255 = missing: `encode_alignment`) over `fnn_alignment_distances_batch_f64`: exact integer counts on the int8 matrix
     cores and one IEEE division per entry.  out="numpy" returns a float64 array (B, n, n); out="torch" allocates a
     torch.float64 tensor (B, n, n) on the GPU and hands its address to the device entry, so that `canonical_order_batch` and
     `split_weights_batch` can read it in place.  Returns (matrices, stats dict).  Raises FnnError with code -1 naming the
-    lowest (b, i, j) when two taxa share no site in a replicate."""
+    lowest (b, i, j) when two taxa share no site in a replicate.
+    model: "p" (the default: mism / valid), "jc69" (Jukes-Cantor with `states` states, compared by equality) or "k2p" (Kimura
+    two-parameter: the bytes A C G T U in either case are the four states, 255 stays missing and every other byte is counted
+    in stats["n_recoded"] and treated as missing), over `fnn_alignment_distances_model_batch_f64`: the same exact counts, then a
+    fixed sequence of fp64 operations with the library's own log1p.  A saturated pair (the model's distance is infinite) fails
+    the call like an empty one with on_saturation="fail"; with "cap" it becomes `cap` (finite, > 0) and
+    stats["n_saturated_problems"] counts the replicates that had one."""
     from . import api
     a = api()
     seq, counts = _dist_inputs(seq, counts)
     (n, L), B = seq.shape, counts.shape[0]
+    if model == "p":
+        def run(ptr, **kw):
+            return _capi.run_dist(a, seq.ctypes.data, n, L, L, counts.ctypes.data, B, L, ptr, max(n, 1), max(n * n, 1), device=device, **kw)
+    else:
+        m = _capi.dist_model(model, states, on_saturation, cap)
+
+        def run(ptr, **kw):
+            return _capi.run_dist_model(a, seq.ctypes.data, n, L, L, counts.ctypes.data, B, L, ptr, max(n, 1), max(n * n, 1), m, device=device, **kw)
     if out == "torch":
         import torch
         dev = torch.device("cuda", device)
         D = torch.empty((B, n, n), dtype=torch.float64, device=dev)
         torch.cuda.synchronize(dev)
-        st = _capi.run_dist(a, seq.ctypes.data, n, L, L, counts.ctypes.data, B, L, D.data_ptr() if B and n else None, max(n, 1), max(n * n, 1),
-                            device=device, on_device=True)
+        st = run(D.data_ptr() if B and n else None, on_device=True)
     elif out == "numpy":
         D = np.empty((B, n, n), dtype=np.float64)
-        st = _capi.run_dist(a, seq.ctypes.data, n, L, L, counts.ctypes.data, B, L, D.ctypes.data, max(n, 1), max(n * n, 1), device=device)
+        st = run(D.ctypes.data)
     else:
         raise ValueError('out must be "numpy" or "torch"')
     return D, st.as_dict()
 
 
-def bootstrap(seq, B: int, seed: int, weights: bool = True, device: int = 0):
+def bootstrap(seq, B: int, seed: int, weights: bool = True, device: int = 0, model: str = "p", states: int = 4, on_saturation: str = "fail",
+              cap=None):
     """B bootstrap replicates of the alignment `seq` (uint8 (n, L)) end to end: `bootstrap_counts`, the distance matrices as a
     tensor on the GPU, `canonical_order_batch` of that tensor and (weights=True) `split_weights_batch` of it.  No matrix
     crosses to the host.  Returns (orders[B, n + 1], W[B, n(n-1)/2] or None, stats) with stats = {"distances": ..., "splits":
-    ... (weights=True)}."""
+    ... (weights=True)}.  model, states, on_saturation, cap: as `alignment_distances_batch` takes them."""
     seq = np.ascontiguousarray(seq, dtype=np.uint8)
     counts = bootstrap_counts(seq.shape[1], B, seed)
-    D, dst = alignment_distances_batch(seq, counts, device=device, out="torch")
+    D, dst = alignment_distances_batch(seq, counts, device=device, out="torch", model=model, states=states, on_saturation=on_saturation, cap=cap)
     orders = canonical_order_batch(D, device=device)
     stats = {"distances": dst}
     W = None
@@ -468,16 +483,18 @@ def key_taxa(key) -> list:
     return [64 * w + b + 1 for w, x in enumerate(np.asarray(key, dtype=np.uint64).tolist()) for b in range(64) if (x >> b) & 1]
 
 
-def bootstrap_support(seq, B: int, seed: int, threshold: float = 1e-6, device: int = 0):
+def bootstrap_support(seq, B: int, seed: int, threshold: float = 1e-6, device: int = 0, model: str = "p", states: int = 4,
+                      on_saturation: str = "fail", cap=None):
     """A bootstrap run with its result: the original alignment as problem 0 (every site once) in front of the B replicates of
     `bootstrap_counts(L, B, seed)`, through distances, orders and split weights as `bootstrap` runs them, then
     `split_support(..., lead=1)`.  Returns (order, weights, table, stats): the order and the weights of the original data, the
     table - its rows with first_b == 0 are the original network's splits above `threshold` in ascending k, `support` the share
-    of the B replicates that hold each - and stats = {"distances", "splits", "support"}."""
+    of the B replicates that hold each - and stats = {"distances", "splits", "support"}.  model, states, on_saturation, cap: as
+    `alignment_distances_batch` takes them."""
     seq = np.ascontiguousarray(seq, dtype=np.uint8)
     L = seq.shape[1]
     counts = np.concatenate([np.ones((1, L), dtype=np.uint16), bootstrap_counts(L, B, seed)])
-    D, dst = alignment_distances_batch(seq, counts, device=device, out="torch")
+    D, dst = alignment_distances_batch(seq, counts, device=device, out="torch", model=model, states=states, on_saturation=on_saturation, cap=cap)
     orders = canonical_order_batch(D, device=device)
     W, sst = split_weights_batch(D, orders, device=device)
     table, ust = split_support(orders, W, threshold=threshold, lead=1, device=device)

@@ -16,6 +16,10 @@
 // the planes to round_up(replicates of the chunk, 64) rows of lpad bytes, padding 0.  Padded pairs and replicates compute
 // values that are never stored, so the kernel has no tail branch in its loop and a 16-byte load never leaves its buffer.
 // Every (b, i, j) is stored by exactly one lane; no atomics, no LDS, no hand-over between workgroups.
+//
+// Corrected distances (k_dist_model): JC69 changes the epilogue only; K2P adds a third 0/1 operand,
+// "both present and a transition", made from the same two 16-byte loads, and a third accumulator set.  What a lane does
+// with the exact counts is fnn_dist_model.h.
 #ifndef FNN_DIST_H
 #define FNN_DIST_H
 
@@ -24,8 +28,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
+#include "fnn_dist_model.h"
 #include "fnn_small.h"  // batch_chunk (FNN_BATCH_CHUNK), round_up; fnn_engine.h: fail, now_s, the FNN_* codes
 
 namespace fnn {
@@ -56,6 +62,16 @@ struct DistArgs {
     int64_t ld, stride;
     int32_t* bad;            // bad[b] = 1: some pair of replicate b has valid == 0 (its entries are NaN)
 };
+// what k_dist_model needs beyond DistArgs
+struct DistModel {
+    int32_t states;          // JC69: k
+    double sat_value;        // stored for a saturated pair: the cap, or +inf when the call is going to fail
+    int32_t* sat;            // sat[b] = 1: some pair of replicate b is saturated (written like bad[])
+};
+// replicate tiles per wave of k_dist_model: K2P with three digit planes and `valid` counted holds 9 accumulator sets per
+// replicate tile; at DIST_RT tiles the compiler fills all 256 VGPRs and parks 15 more values in AGPRs inside the loop (no
+// scratch yet, and no margin), at 2 tiles it needs 184 + 72
+constexpr int32_t dist_model_rt(int32_t model, int32_t P, bool missing) { return model == FNN_DIST_K2P && P == 3 && missing ? 2 : DIST_RT; }
 
 // ---- fragment construction from bytes
 FNN_HD DistFrag dist_load16(const void* p) {
@@ -79,6 +95,17 @@ FNN_HD void dist_a_frags(const DistFrag& ri, const DistFrag& rj, DistFrag& mism,
         mism.w[q] = d;
     }
 }
+// the same with the K2P operand: ts = both present and the codes (A 0, C 1, G 2, T 3) differ by a transition, i.e. their
+// xor is 2 (A ^ G = C ^ T = 2).  A missing byte is 255: 255 ^ code is never 2, so without MISSING no mask is needed.
+template <bool MISSING>
+FNN_HD void dist_a_frags_ts(const DistFrag& ri, const DistFrag& rj, DistFrag& mism, DistFrag& valid, DistFrag& ts) {
+    dist_a_frags<MISSING>(ri, rj, mism, valid);
+    for (int q = 0; q < 4; q++) {
+        uint32_t s = ~dist_nonzero_bytes((ri.w[q] ^ rj.w[q]) ^ 0x02020202u) & 0x01010101u;
+        if (MISSING) s &= valid.w[q];
+        ts.w[q] = s;
+    }
+}
 // lane maps of the 16 x 16 x 64 int8 form (verified with exact integers: tests/dist_common.py, case "lane maps")
 FNN_HD int dist_lane_rc(int lane) { return lane & 15; }        // A: row (pair of the tile); B, C: column (replicate)
 FNN_HD int dist_lane_k(int lane) { return 16 * (lane >> 4); }  // A, B: first of the lane's 16 consecutive k (sites)
@@ -90,6 +117,13 @@ FNN_HD void dist_lane_a(const DistArgs& a, const DistTile& t, int lane, int64_t 
     const DistFrag ri = dist_load16(a.seq + (int64_t)t.i * a.lpad + off);
     const DistFrag rj = dist_load16(a.seq + (int64_t)(t.j0 + dist_lane_rc(lane)) * a.lpad + off);
     dist_a_frags<MISSING>(ri, rj, mism, valid);
+}
+template <bool MISSING>
+FNN_HD void dist_lane_a_ts(const DistArgs& a, const DistTile& t, int lane, int64_t s, DistFrag& mism, DistFrag& valid, DistFrag& ts) {
+    const int64_t off = s + dist_lane_k(lane);
+    const DistFrag ri = dist_load16(a.seq + (int64_t)t.i * a.lpad + off);
+    const DistFrag rj = dist_load16(a.seq + (int64_t)(t.j0 + dist_lane_rc(lane)) * a.lpad + off);
+    dist_a_frags_ts<MISSING>(ri, rj, mism, valid, ts);
 }
 // b0: the first replicate of the workgroup (a multiple of DIST_REPS), rt: the replicate tile, d: the digit
 FNN_HD DistFrag dist_lane_b(const DistArgs& a, int64_t b0, int rt, int d, int lane, int64_t s) {
@@ -159,6 +193,34 @@ FNN_HD void dist_lane_store(const DistArgs& a, const DistTile& t, int64_t b0, in
     }
 }
 
+// The same for a corrected distance (MODEL = FNN_DIST_JC69 or FNN_DIST_K2P; `ts` is read by K2P only): an empty pair is NaN
+// and flags bad[b] as above; a saturated pair is dm.sat_value and flags dm.sat[b]; no mismatch is +0.0.
+template <int MODEL, int P, bool MISSING>
+FNN_HD void dist_lane_store_model(const DistArgs& a, const DistModel& dm, const DistTile& t, int64_t b0, int lane, const DistAcc* mism,
+                                  const DistAcc* valid, const DistAcc* ts) {
+    const int64_t b = b0 + dist_lane_rc(lane);
+    if (b >= a.cnt || t.i >= a.n) return;
+    double* D = a.out + b * a.stride;
+    if (t.j0 == t.i + 1 && lane < 16) D[dist_store_index(t.i, t.i, a.ld)] = 0.0;
+    for (int r = 0; r < 4; r++) {
+        const int32_t j = t.j0 + dist_lane_row(lane, r);
+        if (j >= a.n) continue;
+        const int64_t m = dist_combine<P>(mism, r);
+        const int64_t v = MISSING ? dist_combine<P>(valid, r) : a.total[b];
+        double d;
+        if (v == 0) { a.bad[b] = 1; d = __builtin_nan(""); }
+        else if (m == 0) d = 0.0;
+        else {
+            const int64_t s = MODEL == FNN_DIST_K2P ? dist_combine<P>(ts, r) : 0;
+            const bool sat = MODEL == FNN_DIST_K2P ? dist_k2p_saturated(s, m - s, v) : dist_jc69_saturated(dm.states, m, v);
+            if (sat) { dm.sat[b] = 1; d = dm.sat_value; }
+            else d = MODEL == FNN_DIST_K2P ? dist_k2p(s, m - s, v) : dist_jc69(dm.states, m, v);
+        }
+        D[dist_store_index(t.i, j, a.ld)] = d;
+        D[dist_store_index(j, t.i, a.ld)] = d;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 // tiles of taxon i: j0 = i + 1 + 16 t while j0 < n, and at least one (it stores the diagonal entry); filled up to a
 // multiple of DIST_WAVES with {n, n}
@@ -204,16 +266,45 @@ inline int32_t dist_bootstrap_counts(const char* who, int64_t L, int64_t batch, 
 // fnn_alignment_distances_batch[_device]_f64 over a backend B (HIP: fnn_dist.hip; CPU driver: tests/emu):
 //   open(device); alloc; h2d / d2h; run(digits, missing, args, tile groups, replicate groups, &t_kernel_s); err()
 // The host variant writes D_out only when the whole call has succeeded.
+// A backend that has the corrected distances adds run_model(model, digits, missing, args, model args, tile groups,
+// replicates of the chunk, &t_kernel_s) and sizes its grid from dist_model_rt; one without it knows FNN_DIST_P only.
+template <class B, class = void>
+struct dist_runs_models : std::false_type {};
 template <class B>
-int32_t dist_batch(B& be, const char* who, const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts, int64_t batch,
-                   int64_t ldc, int32_t model, int32_t device, double* D_out, bool on_device, int64_t ld, int64_t stride, fnn_dist_stats* stats) {
+struct dist_runs_models<B, std::void_t<decltype(&B::run_model)>> : std::true_type {};
+
+inline int32_t dist_fail_saturated(const std::string& W, int64_t b, int64_t i, int64_t j) {
+    return fail(FNN_EINVAL, W + "saturated pair (the model's distance is infinite) at (b, i, j) = (" + std::to_string(b) + ", " + std::to_string(i) +
+                                ", " + std::to_string(j) + ")");
+}
+// K2P's codes: A a -> 0, C c -> 1, G g -> 2, T t U u -> 3, 255 stays, every other byte -> 255
+inline void dist_k2p_codes(uint8_t* lut) {
+    std::memset(lut, FNN_SITE_MISSING, 256);
+    const char* letters = "AaCcGgTtUu";
+    const uint8_t code[10] = {0, 0, 1, 1, 2, 2, 3, 3, 3, 3};
+    for (int k = 0; k < 10; k++) lut[(uint8_t)letters[k]] = code[k];
+}
+
+template <class B>
+int32_t dist_batch_model(B& be, const char* who, const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts, int64_t batch,
+                         int64_t ldc, const fnn_dist_model* mp, int32_t device, double* D_out, bool on_device, int64_t ld, int64_t stride,
+                         fnn_dist_model_stats* stats) {
     const double t0 = now_s();
     const std::string W = std::string(who) + ": ";
-    fnn_dist_stats st{};
+    fnn_dist_model_stats mst{};
+    fnn_dist_stats& st = mst.base;
     if (n <= 0 || L <= 0 || batch < 0) return fail(FNN_EINVAL, W + "needs n > 0, L > 0 and batch >= 0");
-    if (model != FNN_DIST_P) return fail(FNN_EINVAL, W + "unknown model");
+    if (!mp) return fail(FNN_EINVAL, W + "NULL model");
+    const int32_t model = mp->model;
+    const bool known = model == FNN_DIST_P || (dist_runs_models<B>::value && (model == FNN_DIST_JC69 || model == FNN_DIST_K2P));
+    if (!known) return fail(FNN_EINVAL, W + "unknown model");
+    const bool cap = mp->on_saturation == FNN_DIST_SAT_CAP;
+    if (mp->on_saturation != FNN_DIST_SAT_FAIL && !cap) return fail(FNN_EINVAL, W + "unknown saturation policy");
+    if (model == FNN_DIST_JC69 && (mp->states < 2 || mp->states > 255)) return fail(FNN_EINVAL, W + "JC69 needs 2 <= states <= 255");
+    if (model != FNN_DIST_P && cap && !(mp->cap > 0.0 && mp->cap <= 1.7976931348623157e308))
+        return fail(FNN_EINVAL, W + "the cap of saturated pairs must be finite and > 0");
     if (L > (((int64_t)1 << 31) - 1) / 127) return fail(FNN_EINVAL, W + "too many sites: 127 L must stay below 2^31 (the int32 digit accumulators)");
-    if (batch == 0) { if (stats) *stats = st; return FNN_OK; }
+    if (batch == 0) { if (stats) *stats = mst; return FNN_OK; }
     if (!seq || !counts || !D_out) return fail(FNN_EINVAL, W + "NULL argument");
     if (lds < L || ldc < L) return fail(FNN_EINVAL, W + "needs lds >= L and ldc >= L");
     if (ld < n || stride < (int64_t)n * ld) return fail(FNN_EINVAL, W + "needs ld >= n and stride >= n * ld");
@@ -224,7 +315,30 @@ int32_t dist_batch(B& be, const char* who, const uint8_t* seq, int32_t n, int64_
 
     // one look at the inputs: a missing byte, the largest count, every replicate's total
     bool missing = dist_force_missing();
-    for (int32_t i = 0; i < n && !missing; i++) missing = std::memchr(seq + (int64_t)i * lds, FNN_SITE_MISSING, (size_t)L) != nullptr;
+    uint8_t lut[256];
+    if (model == FNN_DIST_K2P) {  // what the recoding turns into 255 is missing too
+        dist_k2p_codes(lut);
+        for (int32_t i = 0; i < n; i++) {
+            const uint8_t* row = seq + (int64_t)i * lds;
+            for (int64_t s = 0; s < L; s++) {
+                if (lut[row[s]] != FNN_SITE_MISSING) continue;
+                missing = true;
+                if (row[s] != FNN_SITE_MISSING) mst.n_recoded++;
+            }
+        }
+    } else if (model == FNN_DIST_JC69) {
+        bool seen[256] = {};
+        for (int32_t i = 0; i < n; i++) {
+            const uint8_t* row = seq + (int64_t)i * lds;
+            for (int64_t s = 0; s < L; s++) seen[row[s]] = true;
+        }
+        int32_t distinct = 0;
+        for (int k = 0; k < FNN_SITE_MISSING; k++) distinct += seen[k] ? 1 : 0;
+        if (distinct > mp->states)
+            return fail(FNN_EINVAL, W + "the alignment holds " + std::to_string(distinct) + " distinct states, more than states = " + std::to_string(mp->states));
+        missing = missing || seen[FNN_SITE_MISSING];
+    } else
+        for (int32_t i = 0; i < n && !missing; i++) missing = std::memchr(seq + (int64_t)i * lds, FNN_SITE_MISSING, (size_t)L) != nullptr;
     st.has_missing = missing ? 1 : 0;
     std::vector<int64_t> total((size_t)batch, 0);
     uint16_t cmax = 0;
@@ -237,8 +351,10 @@ int32_t dist_batch(B& be, const char* who, const uint8_t* seq, int32_t n, int64_
     const int32_t P = cmax <= 127 ? 1 : (cmax <= 16383 ? 2 : 3);
     st.digit_passes = P;
     // valid is the total: an empty replicate has valid == 0 for every pair, (0, 1) the lowest (with missing bytes the
-    // kernel flags it, so that a lower replicate with one empty pair is named first)
-    if (n >= 2 && !missing)
+    // kernel flags it, so that a lower replicate with one empty pair is named first; so it does when a saturated pair fails
+    // the call, for the same reason)
+    const bool sat_fails = model != FNN_DIST_P && !cap;
+    if (n >= 2 && !missing && !sat_fails)
         for (int64_t b = 0; b < batch; b++)
             if (total[(size_t)b] == 0) return dist_fail_no_site(W, b, 0, 1);
 
@@ -254,18 +370,25 @@ int32_t dist_batch(B& be, const char* who, const uint8_t* seq, int32_t n, int64_
     int8_t* d_planes = (int8_t*)be.alloc(plane_bytes * (size_t)P);
     int64_t* d_total = (int64_t*)be.alloc(sizeof(int64_t) * (size_t)cpad);
     int32_t* d_bad = (int32_t*)be.alloc(sizeof(int32_t) * (size_t)cpad);
+    int32_t* d_sat = model != FNN_DIST_P ? (int32_t*)be.alloc(sizeof(int32_t) * (size_t)cpad) : nullptr;
     double* d_out = on_device ? nullptr : (double*)be.alloc(sizeof(double) * (size_t)nn * (size_t)chunk);
-    if (!d_seq || !d_tiles || !d_planes || !d_total || !d_bad || (!on_device && !d_out)) return fail(FNN_ENOMEM, W + "device allocation failed");
+    if (!d_seq || !d_tiles || !d_planes || !d_total || !d_bad || (model != FNN_DIST_P && !d_sat) || (!on_device && !d_out))
+        return fail(FNN_ENOMEM, W + "device allocation failed");
     {
         std::vector<uint8_t> img(seq_bytes, (uint8_t)FNN_SITE_MISSING);
-        for (int32_t i = 0; i < n; i++) std::memcpy(&img[(size_t)i * (size_t)lpad], seq + (int64_t)i * lds, (size_t)L);
+        for (int32_t i = 0; i < n; i++) {
+            uint8_t* row = &img[(size_t)i * (size_t)lpad];
+            std::memcpy(row, seq + (int64_t)i * lds, (size_t)L);
+            if (model == FNN_DIST_K2P)
+                for (int64_t s = 0; s < L; s++) row[s] = lut[row[s]];
+        }
         if (be.h2d(d_seq, img.data(), seq_bytes) != FNN_OK || be.h2d(d_tiles, tiles.data(), sizeof(DistTile) * tiles.size()) != FNN_OK)
             return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
     }
     st.t_upload_s += now_s() - tu0;
     std::vector<int8_t> planes(plane_bytes * (size_t)P);
     std::vector<int64_t> tot((size_t)cpad);
-    std::vector<int32_t> bad((size_t)cpad);
+    std::vector<int32_t> bad((size_t)cpad), sat(model != FNN_DIST_P ? (size_t)cpad : 0);
     std::vector<double> stage(on_device ? 0 : (size_t)nn * (size_t)batch), one;
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t cnt = batch - b0 < chunk ? batch - b0 : chunk;
@@ -283,7 +406,8 @@ int32_t dist_batch(B& be, const char* who, const uint8_t* seq, int32_t n, int64_
             }
         }
         if (be.h2d(d_planes, planes.data(), planes.size()) != FNN_OK || be.h2d(d_total, tot.data(), sizeof(int64_t) * (size_t)cpad) != FNN_OK ||
-            be.h2d(d_bad, bad.data(), sizeof(int32_t) * (size_t)cpad) != FNN_OK)
+            be.h2d(d_bad, bad.data(), sizeof(int32_t) * (size_t)cpad) != FNN_OK ||
+            (d_sat && be.h2d(d_sat, bad.data(), sizeof(int32_t) * (size_t)cpad) != FNN_OK))  // (zeros)
             return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
         st.t_upload_s += now_s() - tu;
         DistArgs a{};
@@ -292,19 +416,35 @@ int32_t dist_batch(B& be, const char* who, const uint8_t* seq, int32_t n, int64_
         if (on_device) { a.out = D_out + b0 * stride; a.ld = ld; a.stride = stride; }
         else { a.out = d_out; a.ld = n; a.stride = nn; }
         double tk = 0.0;
-        if (be.run(P, missing, a, (int64_t)(tiles.size() / DIST_WAVES), round_up(cnt, (int64_t)DIST_REPS) / DIST_REPS, &tk) != FNN_OK)
-            return fail(FNN_EHIP, W + "kernel failed (" + be.err() + ")");
+        int32_t rk;
+        if constexpr (dist_runs_models<B>::value) {
+            DistModel dm{};
+            dm.states = mp->states;
+            dm.sat_value = cap ? mp->cap : __builtin_huge_val();
+            dm.sat = d_sat;
+            rk = model != FNN_DIST_P ? be.run_model(model, P, missing, a, dm, (int64_t)(tiles.size() / DIST_WAVES), cnt, &tk)
+                                     : be.run(P, missing, a, (int64_t)(tiles.size() / DIST_WAVES), round_up(cnt, (int64_t)DIST_REPS) / DIST_REPS, &tk);
+        } else
+            rk = be.run(P, missing, a, (int64_t)(tiles.size() / DIST_WAVES), round_up(cnt, (int64_t)DIST_REPS) / DIST_REPS, &tk);
+        if (rk != FNN_OK) return fail(FNN_EHIP, W + "kernel failed (" + be.err() + ")");
         st.t_kernel_s += tk;
-        if (be.d2h(bad.data(), d_bad, sizeof(int32_t) * (size_t)cnt) != FNN_OK) return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
+        if (be.d2h(bad.data(), d_bad, sizeof(int32_t) * (size_t)cnt) != FNN_OK || (d_sat && be.d2h(sat.data(), d_sat, sizeof(int32_t) * (size_t)cnt) != FNN_OK))
+            return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
         for (int64_t b = 0; b < cnt; b++) {
-            if (!bad[(size_t)b]) continue;
-            // the lowest replicate with an empty pair: its matrix names the pair (NaN entries)
+            const bool saturated = d_sat && sat[(size_t)b];
+            if (saturated && cap) mst.n_saturated_problems++;
+            if (!bad[(size_t)b] && !(saturated && sat_fails)) continue;
+            // the lowest replicate with an empty pair (NaN entries) or, where that fails the call, a saturated one (+inf): its
+            // matrix names the pair
             const size_t span = (size_t)((int64_t)(n - 1) * a.ld + n);
             one.resize(span);
             if (be.d2h(one.data(), a.out + b * a.stride, sizeof(double) * span) != FNN_OK) return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
             for (int32_t i = 0; i < n; i++)
-                for (int32_t j = i + 1; j < n; j++)
-                    if (one[(size_t)dist_store_index(i, j, a.ld)] != one[(size_t)dist_store_index(i, j, a.ld)]) return dist_fail_no_site(W, b0 + b, i, j);
+                for (int32_t j = i + 1; j < n; j++) {
+                    const double x = one[(size_t)dist_store_index(i, j, a.ld)];
+                    if (x != x) return dist_fail_no_site(W, b0 + b, i, j);
+                    if (sat_fails && x == __builtin_huge_val()) return dist_fail_saturated(W, b0 + b, i, j);
+                }
             return fail(FNN_EHIP, W + "replicate " + std::to_string(b0 + b) + ": flagged without an empty pair");
         }
         if (!on_device && be.d2h(&stage[(size_t)b0 * (size_t)nn], d_out, sizeof(double) * (size_t)nn * (size_t)cnt) != FNN_OK)
@@ -315,8 +455,20 @@ int32_t dist_batch(B& be, const char* who, const uint8_t* seq, int32_t n, int64_
             for (int32_t r = 0; r < n; r++)
                 std::memcpy(D_out + b * stride + (int64_t)r * ld, &stage[(size_t)b * (size_t)nn + (size_t)r * (size_t)n], sizeof(double) * (size_t)n);
     st.t_total_s = now_s() - t0;
-    if (stats) *stats = st;
+    if (stats) *stats = mst;
     return FNN_OK;
+}
+
+// the p-distance entries: FNN_DIST_P or nothing
+template <class B>
+int32_t dist_batch(B& be, const char* who, const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts, int64_t batch,
+                   int64_t ldc, int32_t model, int32_t device, double* D_out, bool on_device, int64_t ld, int64_t stride, fnn_dist_stats* stats) {
+    if (n > 0 && L > 0 && batch >= 0 && model != FNN_DIST_P) return fail(FNN_EINVAL, std::string(who) + ": unknown model");
+    fnn_dist_model pm{};
+    fnn_dist_model_stats mst{};
+    const int32_t rc = dist_batch_model(be, who, seq, n, L, lds, counts, batch, ldc, &pm, device, D_out, on_device, ld, stride, &mst);
+    if (rc == FNN_OK && stats) *stats = mst.base;
+    return rc;
 }
 
 }  // namespace fnn

@@ -45,7 +45,72 @@ __global__ __launch_bounds__(DIST_THREADS) void k_dist(const DistArgs a, const u
     for (int rt = 0; rt < DIST_RT; rt++) dist_lane_store<P, MISSING>(a, t, b0 + DIST_TILE * rt, lane, am[rt], av[rt]);
 }
 
+// k_dist_model<MODEL, P, MISSING, RT>: the same walk for a corrected distance, RT replicate tiles per
+// wave (dist_model_rt; the grid's replicate groups hold 16 RT replicates).  JC69 differs from k_dist in the epilogue only; K2P
+// makes the transition operand from the same two loads and keeps a third accumulator set: 4 x P x (2 or 3) instructions
+// per 64 sites.
+template <int MODEL, int P, bool MISSING, int RT>
+__global__ __launch_bounds__(DIST_THREADS) void k_dist_model(const DistArgs a, const DistModel dm, const uint32_t tile_groups) {
+    constexpr bool K2P = MODEL == FNN_DIST_K2P;
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    const uint32_t rg = blockIdx.x / tile_groups, tg = blockIdx.x - rg * tile_groups;
+    const DistTile t = a.tiles[(size_t)tg * DIST_WAVES + (size_t)wave];
+    const int64_t b0 = (int64_t)rg * (DIST_TILE * RT);
+    DistAcc am[RT][P], av[RT][MISSING ? P : 1], at[RT][K2P ? P : 1];
+    for (int rt = 0; rt < RT; rt++)
+        for (int d = 0; d < P; d++) {
+            am[rt][d] = DistAcc{{0, 0, 0, 0}};
+            av[rt][MISSING ? d : 0] = DistAcc{{0, 0, 0, 0}};
+            at[rt][K2P ? d : 0] = DistAcc{{0, 0, 0, 0}};
+        }
+    for (int64_t s = 0; s < a.lpad; s += DIST_K) {
+        DistFrag fm, fv, ft;
+        if (K2P) dist_lane_a_ts<MISSING>(a, t, lane, s, fm, fv, ft);
+        else dist_lane_a<MISSING>(a, t, lane, s, fm, fv);
+#pragma unroll
+        for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+            for (int d = 0; d < P; d++) {
+                const DistFrag fb = dist_lane_b(a, b0, rt, d, lane, s);
+                am[rt][d] = dist_mma(fm, fb, am[rt][d]);
+                if (MISSING) av[rt][d] = dist_mma(fv, fb, av[rt][d]);
+                if (K2P) at[rt][d] = dist_mma(ft, fb, at[rt][d]);
+            }
+    }
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++) dist_lane_store_model<MODEL, P, MISSING>(a, dm, t, b0 + DIST_TILE * rt, lane, am[rt], av[rt], at[rt]);
+}
+
 struct DistHipBackend : HipBatchBase {
+    template <int MODEL, int P, bool MISSING>
+    int32_t launch_model(const DistArgs& a, const DistModel& dm, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+        constexpr int RT = dist_model_rt(MODEL, P, MISSING);
+        const int64_t rep_groups = round_up(cnt, (int64_t)(DIST_TILE * RT)) / (DIST_TILE * RT);
+        if (tile_groups * rep_groups >= ((int64_t)1 << 31)) { last = "too many workgroups for one launch"; return FNN_EHIP; }
+        return timed_launch(reinterpret_cast<const void*>(&k_dist_model<MODEL, P, MISSING, RT>), "k_dist_model", 0, [&] {
+            hipLaunchKernelGGL((k_dist_model<MODEL, P, MISSING, RT>), dim3((unsigned)(tile_groups * rep_groups)), dim3(DIST_THREADS), 0, stream, a, dm,
+                               (uint32_t)tile_groups);
+        }, t_kernel_s);
+    }
+    template <int MODEL>
+    int32_t run_model_of(int32_t P, bool missing, const DistArgs& a, const DistModel& dm, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+        switch (P * 2 + (missing ? 1 : 0)) {
+            case 2: return launch_model<MODEL, 1, false>(a, dm, tile_groups, cnt, t_kernel_s);
+            case 3: return launch_model<MODEL, 1, true>(a, dm, tile_groups, cnt, t_kernel_s);
+            case 4: return launch_model<MODEL, 2, false>(a, dm, tile_groups, cnt, t_kernel_s);
+            case 5: return launch_model<MODEL, 2, true>(a, dm, tile_groups, cnt, t_kernel_s);
+            case 6: return launch_model<MODEL, 3, false>(a, dm, tile_groups, cnt, t_kernel_s);
+            case 7: return launch_model<MODEL, 3, true>(a, dm, tile_groups, cnt, t_kernel_s);
+        }
+        last = "no kernel for " + std::to_string(P) + " digits";
+        return FNN_EHIP;
+    }
+    int32_t run_model(int32_t model, int32_t P, bool missing, const DistArgs& a, const DistModel& dm, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+        if (model == FNN_DIST_JC69) return run_model_of<FNN_DIST_JC69>(P, missing, a, dm, tile_groups, cnt, t_kernel_s);
+        if (model == FNN_DIST_K2P) return run_model_of<FNN_DIST_K2P>(P, missing, a, dm, tile_groups, cnt, t_kernel_s);
+        last = "no kernel for model " + std::to_string(model);
+        return FNN_EHIP;
+    }
     template <int P, bool MISSING>
     int32_t launch(const DistArgs& a, int64_t tile_groups, int64_t rep_groups, double* t_kernel_s) {
         return timed_launch(reinterpret_cast<const void*>(&k_dist<P, MISSING>), "k_dist", 0, [&] {
@@ -88,7 +153,27 @@ int32_t fnn_alignment_distances_batch_device_f64(const uint8_t* seq, int32_t n, 
     )
 }
 
-int32_t fnn_bootstrap_counts(int64_t L, int64_t batch, uint64_t seed, uint16_t* counts_out) {
+int32_t fnn_alignment_distances_model_batch_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts, int64_t batch,
+                                                int64_t ldc, const fnn_dist_model* m, int32_t device, double* D_out, int64_t ld, int64_t stride,
+                                                fnn_dist_model_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch_model(be, "fnn_alignment_distances_model_batch_f64", seq, n, L, lds, counts, batch, ldc, m, device, D_out, false, ld, stride,
+                                     stats);
+    )
+}
+
+int32_t fnn_alignment_distances_model_batch_device_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts, int64_t batch,
+                                                       int64_t ldc, const fnn_dist_model* m, int32_t device, double* d_D_out, int64_t ld, int64_t stride,
+                                                       fnn_dist_model_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch_model(be, "fnn_alignment_distances_model_batch_device_f64", seq, n, L, lds, counts, batch, ldc, m, device, d_D_out, true, ld,
+                                     stride, stats);
+    )
+}
+
+int32_t fnn_bootstrap_counts(int64_t L,int64_t batch, uint64_t seed, uint16_t* counts_out) {
     FNN_BATCH_TRY(return fnn::dist_bootstrap_counts("fnn_bootstrap_counts", L, batch, seed, counts_out);)
 }
 

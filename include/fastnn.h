@@ -490,7 +490,8 @@ int32_t fnn_split_weights_ragged_device_f64(const double* d_D, const int64_t* of
  * variants.  For replicate b and taxa i != j, as exact integers,
  *     valid = sum_s counts[b][s] * [seq[i][s] != 255 and seq[j][s] != 255]
  *     mism  = sum_s counts[b][s] * [both present and seq[i][s] != seq[j][s]]
- * and with model FNN_DIST_P (the only one so far; any other value is FNN_EINVAL) D_b[i][j] = D_b[j][i] =
+ * and with model FNN_DIST_P (the only one these two entries take; any other value is FNN_EINVAL here - the corrected
+ * distances have entries of their own below) D_b[i][j] = D_b[j][i] =
  * (double)mism / (double)valid, one correctly rounded division; D_b[i][i] = 0.  Replicate b is written at D_out + b * stride
  * with row stride ld (ld >= n, stride >= n * ld), padding untouched.
  * FNN_EINVAL: n <= 0, L <= 0, batch < 0, lds < L, ldc < L, ld < n, stride < n * ld, a NULL array, an unknown model,
@@ -518,6 +519,46 @@ int32_t fnn_alignment_distances_batch_f64(const uint8_t* seq, int32_t n, int64_t
 int32_t fnn_alignment_distances_batch_device_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds,
                                                  const uint16_t* counts, int64_t batch, int64_t ldc, int32_t model, int32_t device,
                                                  double* d_D_out, int64_t ld, int64_t stride, fnn_dist_stats* stats);
+/* ---- corrected distances: Jukes-Cantor and Kimura two-parameter ---------------------------
+ * The two entries above with a model description `m` in place of `model`; everything said there holds.  With
+ * m->model == FNN_DIST_P they write the same bytes as the entries above.  The counts stay exact integers; the correction
+ * is a fixed sequence of fp64 operations, one rounding each, nothing fused, with a logarithm log1p' of the library's own
+ * (fdlibm's algorithm in + - * / and bit operations only: the same bits on the device and on any host).
+ *   FNN_DIST_JC69, k = m->states, 2 <= k <= 255 (4 for DNA, 20 for protein).  States are compared by equality as for the
+ *     p-distance.  y = (double)(k mism) / (double)((k - 1) valid);  D = -(((double)(k - 1) / (double)k) * log1p'(-y)).
+ *     Saturated iff k mism >= (k - 1) valid (an integer test).  FNN_EINVAL, before any device use, when the alignment holds
+ *     more than k distinct bytes other than 255.
+ *   FNN_DIST_K2P (m->states is ignored).  The alignment is recoded while it is copied: A a -> 0, C c -> 1, G g -> 2,
+ *     T t U u -> 3, 255 stays, EVERY OTHER BYTE becomes 255 and is counted in n_recoded (and then has_missing = 1).  With
+ *     ts = sum_s counts[b][s] * [both present and the two codes differ by a transition (A <-> G, C <-> T)], tv = mism - ts:
+ *     y1 = (double)(2 ts + tv) / (double)valid;  y2 = (double)(2 tv) / (double)valid;
+ *     D = 0.5 * (-log1p'(-y1)) + 0.25 * (-log1p'(-y2)).  Saturated iff 2 ts + tv >= valid or 2 tv >= valid.
+ *   Both: mism == 0 gives +0.0, the diagonal is +0.0, the matrices are symmetric.
+ * Saturated pairs: with m->on_saturation == FNN_DIST_SAT_FAIL (0) the call fails with FNN_EINVAL; fnn_last_error() names the
+ * lowest (b, i, j) in lexicographic order that is EMPTY (valid == 0) or SATURATED and says which; the host output is
+ * untouched.  With FNN_DIST_SAT_CAP the entry becomes m->cap (finite, > 0) and n_saturated_problems counts the replicates
+ * that had such a pair; an empty pair still fails the call.
+ * FNN_EINVAL before any device use, beyond the list above: m == NULL, an unknown model or policy, states outside 2 ... 255
+ * for JC69, too many distinct states, cap not finite or <= 0 under FNN_DIST_SAT_CAP.  Set m->reserved to 0. */
+enum { FNN_DIST_JC69 = 1, FNN_DIST_K2P = 2 };
+enum { FNN_DIST_SAT_FAIL = 0, FNN_DIST_SAT_CAP = 1 };
+typedef struct fnn_dist_model {
+    int32_t model, states, on_saturation, reserved;
+    double  cap;
+} fnn_dist_model;
+typedef struct fnn_dist_model_stats {
+    fnn_dist_stats base;
+    int64_t n_recoded, n_saturated_problems;
+    int64_t reserved[2];
+} fnn_dist_model_stats;
+int32_t fnn_alignment_distances_model_batch_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds,
+                                                const uint16_t* counts, int64_t batch, int64_t ldc, const fnn_dist_model* m,
+                                                int32_t device, double* D_out, int64_t ld, int64_t stride,
+                                                fnn_dist_model_stats* stats /* may be NULL */);
+int32_t fnn_alignment_distances_model_batch_device_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds,
+                                                       const uint16_t* counts, int64_t batch, int64_t ldc,
+                                                       const fnn_dist_model* m, int32_t device, double* d_D_out, int64_t ld,
+                                                       int64_t stride, fnn_dist_model_stats* stats);
 /* Reproducible bootstrap multiplicities, host only (no device needed): replicate b draws k = 0 ... L - 1 and increments
  * site floor(x L / 2^64) (the high half of the 128-bit product), x = the (b L + k)-th output of SplitMix64 for `seed`
  * (z = seed + (b L + k + 1) * 0x9E3779B97F4A7C15, then the usual two multiply-xorshift rounds).  counts_out: batch x L,

@@ -10,8 +10,12 @@ B = 1024 bootstrap replicates of random 4-state alignments at about 10 % diverge
 Matrices and orders of (a) and (b) are compared, equal bitwise.  Prints one JSON line per shape: the kernel's time, the
 distance call's time, both routes and their ratio.  The condition: (a) faster than (b) at every shape.
 
+--model jc69 | k2p runs both routes with that corrected distance - (b) then adds the transition matmul
+and numpy's log1p, so its matrices agree to rounding, not bitwise: the largest relative difference is reported - and puts the
+kernel times of all three models of the same run side by side (t_kernel_p_ms, t_kernel_jc69_ms, t_kernel_k2p_ms).
+
     python tools/dist_perf.py [--batch 1024] [--sizes 32,64,140] [--sites 1000,10000] [--missing 0,0.02] [--out FILE]
-                              [--only-a]
+                              [--only-a] [--model p|jc69|k2p]
 
 --only-a runs route (a) alone (for a kernel trace of one shape); --out appends the JSON lines to FILE as well."""
 import argparse
@@ -37,16 +41,16 @@ def alignment(n, L, seed, missing):
     return seq
 
 
-def route_a(seq, counts):
+def route_a(seq, counts, model="p"):
     t0 = time.perf_counter()
-    T, st = fa.alignment_distances_batch(seq, counts, out="torch")
+    T, st = fa.alignment_distances_batch(seq, counts, out="torch", model=model)
     t1 = time.perf_counter()
     orders = fa.canonical_order_batch(T)
     t2 = time.perf_counter()
     return T, orders, st, t1 - t0, t2 - t0
 
 
-def numpy_matrices(seq, counts):
+def numpy_matrices(seq, counts, model="p"):
     n, B = seq.shape[0], counts.shape[0]
     iu, ju = np.triu_indices(n, 1)
     w = counts.astype(np.float64).T                                   # L x B
@@ -58,16 +62,27 @@ def numpy_matrices(seq, counts):
     else:
         mism = (si != sj).astype(np.float64) @ w
         valid = np.broadcast_to(w.sum(axis=0)[None, :], mism.shape)
-    d = (mism / valid).T                                              # B x pairs
+    if model == "jc69":
+        d = -(0.75 * np.log1p(-(4.0 * mism) / (3.0 * valid)))
+    elif model == "k2p":                                              # (ACGT: the bytes' own transitions are A <-> G and C <-> T)
+        code = np.zeros(256, dtype=np.uint8)
+        code[[65, 67, 71, 84]] = (0, 1, 2, 3)
+        pres = (si != 255) & (sj != 255)
+        ts = (pres & ((code[si] ^ code[sj]) == 2)).astype(np.float64) @ w
+        tv = mism - ts
+        d = 0.5 * -np.log1p(-(2.0 * ts + tv) / valid) + 0.25 * -np.log1p(-(2.0 * tv) / valid)
+    else:
+        d = mism / valid
+    d = d.T                                                           # B x pairs
     D = np.zeros((B, n, n))
     D[:, iu, ju] = d
     D[:, ju, iu] = d
     return D
 
 
-def route_b(seq, counts):
+def route_b(seq, counts, model="p"):
     t0 = time.perf_counter()
-    D = numpy_matrices(seq, counts)
+    D = numpy_matrices(seq, counts, model)
     t1 = time.perf_counter()
     orders = fa.canonical_order_batch(D)
     t2 = time.perf_counter()
@@ -82,13 +97,15 @@ def main():
     ap.add_argument("--missing", default="0,0.02")
     ap.add_argument("--out", default=None)
     ap.add_argument("--only-a", action="store_true")
+    ap.add_argument("--model", default="p", choices=["p", "jc69", "k2p"])
     args = ap.parse_args()
     B = args.batch
     # warm both routes: the runtime, the kernels' code objects, numpy's thread pool
     s0 = alignment(8, 256, 1, 0.0)
     c0 = fa.bootstrap_counts(256, 64, 1)
-    route_a(s0, c0)
-    route_b(s0, c0)
+    for m in sorted({"p", args.model} | ({"jc69", "k2p"} if args.model != "p" else set())):
+        route_a(s0, c0, m)
+    route_b(s0, c0, args.model)
     lines = []
     for miss in [float(x) for x in args.missing.split(",")]:
         for n in [int(x) for x in args.sizes.split(",")]:
@@ -97,24 +114,29 @@ def main():
                 counts = fa.bootstrap_counts(L, B, 7)
                 best = None
                 for _ in range(2):   # (the better of two runs of each route)
-                    T, oa, st, ta_call, ta = route_a(seq, counts)
+                    T, oa, st, ta_call, ta = route_a(seq, counts, args.model)
                     if best is None or ta < best[0]:
                         best = (ta, ta_call, st)
                     Ta = T.cpu().numpy()
                     del T
                 ta, ta_call, st = best
-                rec = {"n": n, "L": L, "B": B, "missing": miss, "digit_passes": st["digit_passes"], "has_missing": st["has_missing"],
+                rec = {"model": args.model, "n": n, "L": L, "B": B, "missing": miss, "digit_passes": st["digit_passes"], "has_missing": st["has_missing"],
                        "chunks": st["chunks"], "t_kernel_ms": st["t_kernel_s"] * 1e3, "t_upload_ms": st["t_upload_s"] * 1e3,
                        "t_call_ms": ta_call * 1e3, "t_route_a_ms": ta * 1e3, "out_bytes": B * n * n * 8}
+                if args.model != "p":   # the three kernels side by side: the better of two calls each
+                    for m in ("p", "jc69", "k2p"):
+                        rec[f"t_kernel_{m}_ms"] = min(fa.alignment_distances_batch(seq, counts, out="torch", model=m)[1]["t_kernel_s"] for _ in range(2)) * 1e3
                 if not args.only_a:
                     tb_best = None
                     for _ in range(2):
-                        Db, ob, tb_np, tb = route_b(seq, counts)
+                        Db, ob, tb_np, tb = route_b(seq, counts, args.model)
                         if tb_best is None or tb < tb_best[0]:
                             tb_best = (tb, tb_np)
                     rec.update({"t_numpy_ms": tb_best[1] * 1e3, "t_route_b_ms": tb_best[0] * 1e3, "ratio_b_over_a": tb_best[0] / ta,
                                 "matrices_bitwise_equal": bool((Ta.view(np.int64) == Db.view(np.int64)).all()),
                                 "orders_equal": bool((oa == ob).all())})
+                    if args.model != "p":
+                        rec["max_rel_diff"] = float(np.abs(Ta - Db).max() / np.abs(Db).max())
                 line = json.dumps(rec)
                 print(line, flush=True)
                 lines.append(line)
