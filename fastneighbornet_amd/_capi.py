@@ -304,6 +304,38 @@ def run_bootstrap_counts(a: Api, L: int, batch: int, seed: int) -> np.ndarray:
     return counts
 
 
+class FnnBootStats(C.Structure):
+    _fields_ = [("model", FnnDistModelStats), ("draw_route", C.c_int32), ("max_count", C.c_int32), ("t_draw_s", C.c_double),
+                ("reserved", C.c_int64 * 4)]
+
+    def as_dict(self):
+        return dict(self.model.as_dict(), draw_route=DRAW_ROUTES[self.draw_route], max_count=self.max_count, t_draw_s=self.t_draw_s)
+
+
+DRAW_DEVICE, DRAW_HOST = 0, 1
+DRAW_ROUTES = ("device", "host")
+_BOOT_ARGS = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.POINTER(FnnDistModel), C.c_int32,
+              C.c_void_p, C.c_int64, C.c_int64, C.POINTER(FnnBootStats)]
+
+
+def bind_boot(a: Api) -> Api:
+    """The bootstrap entry points of include/fastnn.h that draw their replicates themselves on `a`."""
+    a._fn("bootstrap_distances_batch_f64", C.c_int32, _BOOT_ARGS)
+    a._fn("bootstrap_distances_batch_device_f64", C.c_int32, _BOOT_ARGS)
+    a._fn("bootstrap_draw_max_sites", C.c_int32, [])
+    return a
+
+
+def run_boot(a: Api, seq, n: int, L: int, lds: int, batch: int, seed: int, lead: int, out, ld: int, stride: int, m: FnnDistModel,
+             device: int = 0, on_device: bool = False):
+    """One bootstrap-distance call on raw addresses (seq: host memory; out: host memory, or device memory with on_device);
+    m=None passes NULL.  Returns the stats (FnnBootStats)."""
+    st = FnnBootStats()
+    fn = a.bootstrap_distances_batch_device_f64 if on_device else a.bootstrap_distances_batch_f64
+    a.check(fn(seq, n, L, lds, batch, seed & 0xFFFFFFFFFFFFFFFF, lead, C.byref(m) if m is not None else None, device, out, ld, stride, C.byref(st)))
+    return st
+
+
 class FnnSupportStats(C.Structure):
     _fields_ = [("n_problems", C.c_int64), ("n_records", C.c_int64), ("n_splits", C.c_int64),
                 ("words", C.c_int32), ("route", C.c_int32), ("hash_retries", C.c_int32), ("chunks", C.c_int32),

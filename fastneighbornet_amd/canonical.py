@@ -403,15 +403,64 @@ def alignment_distances_batch(seq, counts, device: int = 0, out: str = "numpy", 
     return D, st.as_dict()
 
 
-def bootstrap(seq, B: int, seed: int, weights: bool = True, device: int = 0, model: str = "p", states: int = 4, on_saturation: str = "fail",
-              cap=None):
-    """B bootstrap replicates of the alignment `seq` (uint8 (n, L)) end to end: `bootstrap_counts`, the distance matrices as a
-    tensor on the GPU, `canonical_order_batch` of that tensor and (weights=True) `split_weights_batch` of it.  No matrix
-    crosses to the host.  Returns (orders[B, n + 1], W[B, n(n-1)/2] or None, stats) with stats = {"distances": ..., "splits":
-    ... (weights=True)}.  model, states, on_saturation, cap: as `alignment_distances_batch` takes them."""
+def bootstrap_distances(seq, B: int, seed: int, lead: int = 0, device: int = 0, out: str = "numpy", model: str = "p", states: int = 4,
+                        on_saturation: str = "fail", cap=None):
+    """Distance matrices of B bootstrap replicates of the alignment `seq` (uint8 (n, L)) over
+    `fnn_bootstrap_distances_batch_f64`: the replicates of `bootstrap_counts(L, B, seed)` without the counts - up to
+    `fnn_bootstrap_draw_max_sites()` sites a kernel draws them on the GPU where the distance kernel reads them, and the
+    alignment is all that is uploaded.  lead=1 puts the original data (every site once) in front as problem 0.  Returns
+    (matrices (B + lead, n, n), stats dict), bit for bit what `alignment_distances_batch` returns for those counts; out, model,
+    states, on_saturation, cap as there.  stats adds "draw_route" ("device" or "host"), "max_count" and "t_draw_s"."""
+    from . import api
+    a = api()
     seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    if seq.ndim != 2:
+        raise ValueError("seq must have shape (n, L)")
+    if lead not in (0, 1) or B < 0:
+        raise ValueError("lead must be 0 or 1 and B >= 0")
+    n, L = seq.shape
+    batch = int(B) + int(lead)
+    m = _capi.dist_model(model, states, on_saturation, cap)
+
+    def run(ptr, **kw):
+        return _capi.run_boot(a, seq.ctypes.data, n, L, L, batch, int(seed), int(lead), ptr, max(n, 1), max(n * n, 1), m, device=device, **kw)
+    if out == "torch":
+        import torch
+        dev = torch.device("cuda", device)
+        D = torch.empty((batch, n, n), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        st = run(D.data_ptr() if batch and n else None, on_device=True)
+    elif out == "numpy":
+        D = np.empty((batch, n, n), dtype=np.float64)
+        st = run(D.ctypes.data)
+    else:
+        raise ValueError('out must be "numpy" or "torch"')
+    return D, st.as_dict()
+
+
+def _bootstrap_matrices(seq, B, seed, lead, draw, device, **model):
+    """The replicates' matrices as a tensor on the GPU: draw="device" through `bootstrap_distances`, draw="host" through
+    `bootstrap_counts` and `alignment_distances_batch`."""
+    if draw == "device":
+        return bootstrap_distances(seq, B, seed, lead=lead, device=device, out="torch", **model)
+    if draw != "host":
+        raise ValueError('draw must be "device" or "host"')
     counts = bootstrap_counts(seq.shape[1], B, seed)
-    D, dst = alignment_distances_batch(seq, counts, device=device, out="torch", model=model, states=states, on_saturation=on_saturation, cap=cap)
+    if lead:
+        counts = np.concatenate([np.ones((1, seq.shape[1]), dtype=np.uint16), counts])
+    return alignment_distances_batch(seq, counts, device=device, out="torch", **model)
+
+
+def bootstrap(seq, B: int, seed: int, weights: bool = True, device: int = 0, model: str = "p", states: int = 4, on_saturation: str = "fail",
+              cap=None, draw: str = "device"):
+    """B bootstrap replicates of the alignment `seq` (uint8 (n, L)) end to end: the distance matrices of the replicates of
+    `bootstrap_counts(L, B, seed)` as a tensor on the GPU, `canonical_order_batch` of that tensor and (weights=True)
+    `split_weights_batch` of it.  No matrix crosses to the host.  Returns (orders[B, n + 1], W[B, n(n-1)/2] or None, stats) with
+    stats = {"distances": ..., "splits": ... (weights=True)}.  model, states, on_saturation, cap: as `alignment_distances_batch`
+    takes them.  draw="device" (the default) draws the replicates on the GPU (`bootstrap_distances`); draw="host" makes the
+    counts on the host and uploads them: the same matrices, bit for bit."""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    D, dst = _bootstrap_matrices(seq, B, seed, 0, draw, device, model=model, states=states, on_saturation=on_saturation, cap=cap)
     orders = canonical_order_batch(D, device=device)
     stats = {"distances": dst}
     W = None
@@ -484,17 +533,15 @@ def key_taxa(key) -> list:
 
 
 def bootstrap_support(seq, B: int, seed: int, threshold: float = 1e-6, device: int = 0, model: str = "p", states: int = 4,
-                      on_saturation: str = "fail", cap=None):
+                      on_saturation: str = "fail", cap=None, draw: str = "device"):
     """A bootstrap run with its result: the original alignment as problem 0 (every site once) in front of the B replicates of
     `bootstrap_counts(L, B, seed)`, through distances, orders and split weights as `bootstrap` runs them, then
     `split_support(..., lead=1)`.  Returns (order, weights, table, stats): the order and the weights of the original data, the
     table - its rows with first_b == 0 are the original network's splits above `threshold` in ascending k, `support` the share
     of the B replicates that hold each - and stats = {"distances", "splits", "support"}.  model, states, on_saturation, cap: as
-    `alignment_distances_batch` takes them."""
+    `alignment_distances_batch` takes them; draw: as `bootstrap` takes it."""
     seq = np.ascontiguousarray(seq, dtype=np.uint8)
-    L = seq.shape[1]
-    counts = np.concatenate([np.ones((1, L), dtype=np.uint16), bootstrap_counts(L, B, seed)])
-    D, dst = alignment_distances_batch(seq, counts, device=device, out="torch", model=model, states=states, on_saturation=on_saturation, cap=cap)
+    D, dst = _bootstrap_matrices(seq, B, seed, 1, draw, device, model=model, states=states, on_saturation=on_saturation, cap=cap)
     orders = canonical_order_batch(D, device=device)
     W, sst = split_weights_batch(D, orders, device=device)
     table, ust = split_support(orders, W, threshold=threshold, lead=1, device=device)

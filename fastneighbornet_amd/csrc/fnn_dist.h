@@ -20,6 +20,9 @@
 // Corrected distances (k_dist_model): JC69 changes the epilogue only; K2P adds a third 0/1 operand,
 // "both present and a transition", made from the same two 16-byte loads, and a third accumulator set.  What a lane does
 // with the exact counts is fnn_dist_model.h.
+//
+// Bootstrap replicates drawn on the device (k_draw): the planes of a bootstrap are made by a kernel
+// from the seed instead of on the host from counts; its per-lane steps are fnn_draw.h, the host side is the one below.
 #ifndef FNN_DIST_H
 #define FNN_DIST_H
 
@@ -221,6 +224,10 @@ FNN_HD void dist_lane_store_model(const DistArgs& a, const DistModel& dm, const 
     }
 }
 
+}  // namespace fnn
+#include "fnn_draw.h"  // the per-lane steps of k_draw: the planes of a bootstrap made where they are read
+namespace fnn {
+
 // ------------------------------------------------------------------------------------------------ host side
 // tiles of taxon i: j0 = i + 1 + 16 t while j0 < n, and at least one (it stores the diagonal entry); filled up to a
 // multiple of DIST_WAVES with {n, n}
@@ -237,6 +244,14 @@ inline bool dist_force_missing() {
     const char* e = std::getenv("FNN_DIST_FORCE_MISSING");
     return e && std::atoi(e) == 1;
 }
+// FNN_DIST_FORCE_DIGITS=2|3 (tests): at least that many digit planes are allocated, filled and multiplied; the high ones are
+// all zero wherever the counts do not need them, and the counts are exact integers: the same bytes come out
+inline int32_t dist_force_digits() {
+    const char* e = std::getenv("FNN_DIST_FORCE_DIGITS");
+    const int v = e ? std::atoi(e) : 0;
+    return v == 2 || v == 3 ? v : 1;
+}
+inline int32_t dist_digits_of(uint32_t cmax) { return cmax <= 127 ? 1 : (cmax <= 16383 ? 2 : 3); }
 inline int32_t dist_fail_no_site(const std::string& W, int64_t b, int64_t i, int64_t j) {
     return fail(FNN_EINVAL, W + "no site with both taxa present (valid == 0) at (b, i, j) = (" + std::to_string(b) + ", " + std::to_string(i) +
                                 ", " + std::to_string(j) + ")");
@@ -285,14 +300,34 @@ inline void dist_k2p_codes(uint8_t* lut) {
     for (int k = 0; k < 10; k++) lut[(uint8_t)letters[k]] = code[k];
 }
 
+// A backend that can draw a bootstrap's planes itself adds run_draw(draw args, rows, &t_draw_s): one workgroup per row.
+template <class B, class = void>
+struct dist_runs_draw : std::false_type {};
 template <class B>
-int32_t dist_batch_model(B& be, const char* who, const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts, int64_t batch,
-                         int64_t ldc, const fnn_dist_model* mp, int32_t device, double* D_out, bool on_device, int64_t ld, int64_t stride,
-                         fnn_dist_model_stats* stats) {
+struct dist_runs_draw<B, std::void_t<decltype(&B::run_draw)>> : std::true_type {};
+
+// Where the site multiplicities of a call come from: the caller's array, or a bootstrap of `seed` - problems 0 ... lead - 1
+// the original data (every site once), problem b >= lead replicate b - lead of fnn_bootstrap_counts(L, batch - lead, seed) -
+// drawn on the host into such an array or on the device straight into the planes.
+struct DistSource {
+    const uint16_t* counts = nullptr;
+    int64_t ldc = 0;
+    bool bootstrap = false;
+    int32_t draw_route = FNN_DRAW_HOST;  // of a bootstrap
+    uint64_t seed = 0;
+    int64_t lead = 0;
+};
+
+template <class B>
+int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n, int64_t L, int64_t lds, DistSource src, int64_t batch,
+                          const fnn_dist_model* mp, int32_t device, double* D_out, bool on_device, int64_t ld, int64_t stride, fnn_boot_stats* stats) {
     const double t0 = now_s();
     const std::string W = std::string(who) + ": ";
-    fnn_dist_model_stats mst{};
+    fnn_boot_stats bst{};
+    fnn_dist_model_stats& mst = bst.model;
     fnn_dist_stats& st = mst.base;
+    const bool draw = src.bootstrap && src.draw_route == FNN_DRAW_DEVICE;
+    bst.draw_route = draw ? FNN_DRAW_DEVICE : FNN_DRAW_HOST;
     if (n <= 0 || L <= 0 || batch < 0) return fail(FNN_EINVAL, W + "needs n > 0, L > 0 and batch >= 0");
     if (!mp) return fail(FNN_EINVAL, W + "NULL model");
     const int32_t model = mp->model;
@@ -304,10 +339,13 @@ int32_t dist_batch_model(B& be, const char* who, const uint8_t* seq, int32_t n, 
     if (model != FNN_DIST_P && cap && !(mp->cap > 0.0 && mp->cap <= 1.7976931348623157e308))
         return fail(FNN_EINVAL, W + "the cap of saturated pairs must be finite and > 0");
     if (L > (((int64_t)1 << 31) - 1) / 127) return fail(FNN_EINVAL, W + "too many sites: 127 L must stay below 2^31 (the int32 digit accumulators)");
-    if (batch == 0) { if (stats) *stats = mst; return FNN_OK; }
-    if (!seq || !counts || !D_out) return fail(FNN_EINVAL, W + "NULL argument");
-    if (lds < L || ldc < L) return fail(FNN_EINVAL, W + "needs lds >= L and ldc >= L");
+    if (batch == 0) { if (stats) *stats = bst; return FNN_OK; }
+    if (!seq || (!src.bootstrap && !src.counts) || !D_out) return fail(FNN_EINVAL, W + "NULL argument");
+    if (lds < L || (!src.bootstrap && src.ldc < L)) return fail(FNN_EINVAL, W + "needs lds >= L and ldc >= L");
     if (ld < n || stride < (int64_t)n * ld) return fail(FNN_EINVAL, W + "needs ld >= n and stride >= n * ld");
+    if (draw && !dist_runs_draw<B>::value) return fail(FNN_EINVAL, W + "this backend has no draw kernel");
+    if (draw && L > DRAW_MAX_SITES)
+        return fail(FNN_EINVAL, W + "the draw kernel takes at most " + std::to_string(DRAW_MAX_SITES) + " sites (FNN_DRAW_ROUTE=device)");
     st.n_problems = batch;
     st.n_pairs = (int64_t)n * (n - 1) / 2;
     st.n_sites = L;
@@ -340,22 +378,34 @@ int32_t dist_batch_model(B& be, const char* who, const uint8_t* seq, int32_t n, 
     } else
         for (int32_t i = 0; i < n && !missing; i++) missing = std::memchr(seq + (int64_t)i * lds, FNN_SITE_MISSING, (size_t)L) != nullptr;
     st.has_missing = missing ? 1 : 0;
-    std::vector<int64_t> total((size_t)batch, 0);
-    uint16_t cmax = 0;
-    for (int64_t b = 0; b < batch; b++) {
+    // a bootstrap drawn on the host: the counts this call would have been given
+    std::vector<uint16_t> drawn;
+    if (src.bootstrap && !draw) {
+        drawn.assign((size_t)batch * (size_t)L, (uint16_t)1);  // (the rows below `lead` stay all ones)
+        const int32_t rd = dist_bootstrap_counts(who, L, batch - src.lead, src.seed, drawn.data() + src.lead * L);
+        if (rd != FNN_OK) return rd;
+        src.counts = drawn.data();
+        src.ldc = L;
+    }
+    const uint16_t* counts = src.counts;
+    const int64_t ldc = src.ldc;
+    // (drawn on the device: every row's total is L > 0, and the largest count is the kernel's to report)
+    std::vector<int64_t> total(draw ? 0 : (size_t)batch, 0);
+    uint32_t cmax = 0;
+    for (int64_t b = 0; b < batch && !draw; b++) {
         const uint16_t* c = counts + b * ldc;
         int64_t t = 0;
         for (int64_t s = 0; s < L; s++) { t += c[s]; cmax = c[s] > cmax ? c[s] : cmax; }
         total[(size_t)b] = t;
     }
-    const int32_t P = cmax <= 127 ? 1 : (cmax <= 16383 ? 2 : 3);
-    st.digit_passes = P;
+    int32_t P = dist_digits_of(cmax);
+    if (dist_force_digits() > P) P = dist_force_digits();
     // valid is the total: an empty replicate has valid == 0 for every pair, (0, 1) the lowest (with missing bytes the
     // kernel flags it, so that a lower replicate with one empty pair is named first; so it does when a saturated pair fails
     // the call, for the same reason)
     const bool sat_fails = model != FNN_DIST_P && !cap;
     if (n >= 2 && !missing && !sat_fails)
-        for (int64_t b = 0; b < batch; b++)
+        for (int64_t b = 0; b < batch && !draw; b++)
             if (total[(size_t)b] == 0) return dist_fail_no_site(W, b, 0, 1);
 
     int32_t rc = be.open(device);
@@ -372,7 +422,8 @@ int32_t dist_batch_model(B& be, const char* who, const uint8_t* seq, int32_t n, 
     int32_t* d_bad = (int32_t*)be.alloc(sizeof(int32_t) * (size_t)cpad);
     int32_t* d_sat = model != FNN_DIST_P ? (int32_t*)be.alloc(sizeof(int32_t) * (size_t)cpad) : nullptr;
     double* d_out = on_device ? nullptr : (double*)be.alloc(sizeof(double) * (size_t)nn * (size_t)chunk);
-    if (!d_seq || !d_tiles || !d_planes || !d_total || !d_bad || (model != FNN_DIST_P && !d_sat) || (!on_device && !d_out))
+    uint32_t* d_max = draw ? (uint32_t*)be.alloc(sizeof(uint32_t)) : nullptr;
+    if (!d_seq || !d_tiles || !d_planes || !d_total || !d_bad || (model != FNN_DIST_P && !d_sat) || (!on_device && !d_out) || (draw && !d_max))
         return fail(FNN_ENOMEM, W + "device allocation failed");
     {
         std::vector<uint8_t> img(seq_bytes, (uint8_t)FNN_SITE_MISSING);
@@ -382,34 +433,59 @@ int32_t dist_batch_model(B& be, const char* who, const uint8_t* seq, int32_t n, 
             if (model == FNN_DIST_K2P)
                 for (int64_t s = 0; s < L; s++) row[s] = lut[row[s]];
         }
-        if (be.h2d(d_seq, img.data(), seq_bytes) != FNN_OK || be.h2d(d_tiles, tiles.data(), sizeof(DistTile) * tiles.size()) != FNN_OK)
+        const uint32_t zero = 0;
+        if (be.h2d(d_seq, img.data(), seq_bytes) != FNN_OK || be.h2d(d_tiles, tiles.data(), sizeof(DistTile) * tiles.size()) != FNN_OK ||
+            (draw && be.h2d(d_max, &zero, sizeof(zero)) != FNN_OK))
             return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
     }
     st.t_upload_s += now_s() - tu0;
-    std::vector<int8_t> planes(plane_bytes * (size_t)P);
-    std::vector<int64_t> tot((size_t)cpad);
+    std::vector<int8_t> planes(draw ? 0 : plane_bytes * (size_t)P);
+    std::vector<int64_t> tot(draw ? 0 : (size_t)cpad);
     std::vector<int32_t> bad((size_t)cpad), sat(model != FNN_DIST_P ? (size_t)cpad : 0);
     std::vector<double> stage(on_device ? 0 : (size_t)nn * (size_t)batch), one;
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t cnt = batch - b0 < chunk ? batch - b0 : chunk;
         st.chunks++;
-        const double tu = now_s();
-        std::memset(planes.data(), 0, planes.size());  // (padding: zero counts)
-        std::fill(tot.begin(), tot.end(), (int64_t)0);
-        std::fill(bad.begin(), bad.end(), 0);
-        for (int64_t b = 0; b < cnt; b++) {
-            const uint16_t* c = counts + (b0 + b) * ldc;
-            tot[(size_t)b] = total[(size_t)(b0 + b)];
-            for (int d = 0; d < P; d++) {
-                int8_t* row = &planes[(size_t)d * plane_bytes + (size_t)b * (size_t)lpad];
-                for (int64_t s = 0; s < L; s++) row[s] = dist_digit(c[s], d);
+        // the planes of this chunk, the rows' totals and their zeroed flags
+        if (draw) {
+            if constexpr (dist_runs_draw<B>::value) {
+                // The kernel writes P planes and reports the largest count of the call so far in one word, the only one of the
+                // counts that crosses the bus.  A count that needs more planes than were written (no honest bootstrap has
+                // one: P = 1 holds 127) repeats the chunk with as many as it needs; later chunks keep them.
+                for (;;) {
+                    DrawArgs da{};
+                    da.planes = d_planes; da.plane_stride = (int64_t)plane_bytes; da.lpad = lpad; da.L = L; da.digits = P;
+                    da.cnt = cnt; da.first = b0; da.lead = src.lead; da.seed = src.seed;
+                    da.total = d_total; da.bad = d_bad; da.sat = d_sat; da.max_count = d_max;
+                    double td = 0.0;
+                    if (be.run_draw(da, cpad, &td) != FNN_OK) return fail(FNN_EHIP, W + "kernel failed (" + be.err() + ")");
+                    bst.t_draw_s += td;
+                    if (be.d2h(&cmax, d_max, sizeof(cmax)) != FNN_OK) return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
+                    if (dist_digits_of(cmax) <= P) break;
+                    P = dist_digits_of(cmax);
+                    d_planes = (int8_t*)be.alloc(plane_bytes * (size_t)P);
+                    if (!d_planes) return fail(FNN_ENOMEM, W + "device allocation failed");
+                }
             }
+        } else {
+            const double tu = now_s();
+            std::memset(planes.data(), 0, planes.size());  // (padding: zero counts)
+            std::fill(tot.begin(), tot.end(), (int64_t)0);
+            std::fill(bad.begin(), bad.end(), 0);
+            for (int64_t b = 0; b < cnt; b++) {
+                const uint16_t* c = counts + (b0 + b) * ldc;
+                tot[(size_t)b] = total[(size_t)(b0 + b)];
+                for (int d = 0; d < P; d++) {
+                    int8_t* row = &planes[(size_t)d * plane_bytes + (size_t)b * (size_t)lpad];
+                    for (int64_t s = 0; s < L; s++) row[s] = dist_digit(c[s], d);
+                }
+            }
+            if (be.h2d(d_planes, planes.data(), planes.size()) != FNN_OK || be.h2d(d_total, tot.data(), sizeof(int64_t) * (size_t)cpad) != FNN_OK ||
+                be.h2d(d_bad, bad.data(), sizeof(int32_t) * (size_t)cpad) != FNN_OK ||
+                (d_sat && be.h2d(d_sat, bad.data(), sizeof(int32_t) * (size_t)cpad) != FNN_OK))  // (zeros)
+                return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
+            st.t_upload_s += now_s() - tu;
         }
-        if (be.h2d(d_planes, planes.data(), planes.size()) != FNN_OK || be.h2d(d_total, tot.data(), sizeof(int64_t) * (size_t)cpad) != FNN_OK ||
-            be.h2d(d_bad, bad.data(), sizeof(int32_t) * (size_t)cpad) != FNN_OK ||
-            (d_sat && be.h2d(d_sat, bad.data(), sizeof(int32_t) * (size_t)cpad) != FNN_OK))  // (zeros)
-            return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
-        st.t_upload_s += now_s() - tu;
         DistArgs a{};
         a.seq = d_seq; a.lpad = lpad; a.tiles = d_tiles; a.planes = d_planes; a.plane_stride = (int64_t)plane_bytes; a.total = d_total;
         a.n = n; a.cnt = cnt; a.bad = d_bad;
@@ -454,9 +530,47 @@ int32_t dist_batch_model(B& be, const char* who, const uint8_t* seq, int32_t n, 
         for (int64_t b = 0; b < batch; b++)
             for (int32_t r = 0; r < n; r++)
                 std::memcpy(D_out + b * stride + (int64_t)r * ld, &stage[(size_t)b * (size_t)nn + (size_t)r * (size_t)n], sizeof(double) * (size_t)n);
+    st.digit_passes = P;
+    bst.max_count = (int32_t)cmax;
     st.t_total_s = now_s() - t0;
-    if (stats) *stats = mst;
+    if (stats) *stats = bst;
     return FNN_OK;
+}
+
+// the counts entries: the caller's array
+template <class B>
+int32_t dist_batch_model(B& be, const char* who, const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts, int64_t batch,
+                         int64_t ldc, const fnn_dist_model* mp, int32_t device, double* D_out, bool on_device, int64_t ld, int64_t stride,
+                         fnn_dist_model_stats* stats) {
+    DistSource src;
+    src.counts = counts;
+    src.ldc = ldc;
+    fnn_boot_stats bst{};
+    const int32_t rc = dist_batch_source(be, who, seq, n, L, lds, src, batch, mp, device, D_out, on_device, ld, stride, &bst);
+    if (rc == FNN_OK && stats) *stats = bst.model;
+    return rc;
+}
+
+// FNN_DRAW_ROUTE=device|host (tests): where a bootstrap is drawn; anything else leaves the choice to the call
+inline int32_t dist_draw_route_switch() {
+    const char* e = std::getenv("FNN_DRAW_ROUTE");
+    if (e && std::strcmp(e, "device") == 0) return FNN_DRAW_DEVICE;
+    if (e && std::strcmp(e, "host") == 0) return FNN_DRAW_HOST;
+    return -1;
+}
+// fnn_bootstrap_distances_batch[_device]_f64: up to DRAW_MAX_SITES sites the replicates are drawn on the device, above that
+// on the host; the bytes are the same
+template <class B>
+int32_t dist_bootstrap_batch(B& be, const char* who, const uint8_t* seq, int32_t n, int64_t L, int64_t lds, int64_t batch, uint64_t seed, int64_t lead,
+                             const fnn_dist_model* mp, int32_t device, double* D_out, bool on_device, int64_t ld, int64_t stride, fnn_boot_stats* stats) {
+    if (lead < 0 || lead > 1 || lead > batch) return fail(FNN_EINVAL, std::string(who) + ": needs 0 <= lead <= 1 and lead <= batch");
+    DistSource src;
+    src.bootstrap = true;
+    src.seed = seed;
+    src.lead = lead;
+    const int32_t sw = dist_draw_route_switch();
+    src.draw_route = sw >= 0 ? sw : (L <= DRAW_MAX_SITES ? FNN_DRAW_DEVICE : FNN_DRAW_HOST);
+    return dist_batch_source(be, who, seq, n, L, lds, src, batch, mp, device, D_out, on_device, ld, stride, stats);
 }
 
 // the p-distance entries: FNN_DIST_P or nothing

@@ -5,6 +5,8 @@
 // and the workgroup's 64 replicates as 4 tiles of 16.  Per 64 sites a lane loads 16 bytes of row i and of its row j, makes
 // the 0/1 operand bytes in registers, loads 16 bytes of each digit plane of each of its 4 replicates and issues
 // 4 x P (x 2 with MISSING) v_mfma_i32_16x16x64_i8.  No LDS, no atomics, no hand-over; vector stores and plain C++ only.
+//
+// k_draw (fnn_draw.h) makes the digit planes of a bootstrap on the device, one workgroup per row.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -81,7 +83,37 @@ __global__ __launch_bounds__(DIST_THREADS) void k_dist_model(const DistArgs a, c
     for (int rt = 0; rt < RT; rt++) dist_lane_store_model<MODEL, P, MISSING>(a, dm, t, b0 + DIST_TILE * rt, lane, am[rt], av[rt], at[rt]);
 }
 
+// k_draw: one workgroup makes one row of the digit planes of a bootstrap (the steps are fnn_draw.h).
+// Dynamic LDS: the row's histogram, 2 * lpad bytes <= DRAW_LDS_BYTES.  grid: the chunk's padded rows.
+__global__ __launch_bounds__(DRAW_THREADS) void k_draw(const DrawArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t draw_hist[];
+    const int tid = (int)threadIdx.x;
+    const int64_t row = (int64_t)blockIdx.x;
+    uint32_t most = 0;
+    if (row < a.cnt) {  // (uniform over the workgroup)
+        draw_lane_zero(draw_hist, a.lpad, tid, DRAW_THREADS);
+        __syncthreads();
+        draw_lane_count(a, draw_hist, row, tid, DRAW_THREADS);
+        __syncthreads();
+        most = draw_lane_planes(a, draw_hist, row, tid, DRAW_THREADS);
+    } else
+        draw_lane_planes(a, nullptr, row, tid, DRAW_THREADS);
+    draw_lane_row_words(a, row, tid);
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)most, off);
+        most = o > most ? o : most;
+    }
+    if ((tid & 63) == 0 && most > 0) atomicMax(a.max_count, most);
+}
+
 struct DistHipBackend : HipBatchBase {
+    int32_t run_draw(const DrawArgs& a, int64_t rows, double* t_draw_s) {
+        const int32_t lds_bytes = draw_lds_bytes(a.lpad);
+        if (lds_bytes > DRAW_LDS_BYTES || rows >= ((int64_t)1 << 31)) { last = "too many sites or rows for the draw kernel"; return FNN_EHIP; }
+        return timed_launch(reinterpret_cast<const void*>(&k_draw), "k_draw", lds_bytes, [&] {
+            hipLaunchKernelGGL(k_draw, dim3((unsigned)rows), dim3(DRAW_THREADS), (size_t)lds_bytes, stream, a);
+        }, t_draw_s);
+    }
     template <int MODEL, int P, bool MISSING>
     int32_t launch_model(const DistArgs& a, const DistModel& dm, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
         constexpr int RT = dist_model_rt(MODEL, P, MISSING);
@@ -176,5 +208,25 @@ int32_t fnn_alignment_distances_model_batch_device_f64(const uint8_t* seq, int32
 int32_t fnn_bootstrap_counts(int64_t L,int64_t batch, uint64_t seed, uint16_t* counts_out) {
     FNN_BATCH_TRY(return fnn::dist_bootstrap_counts("fnn_bootstrap_counts", L, batch, seed, counts_out);)
 }
+
+int32_t fnn_bootstrap_distances_batch_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, int64_t batch, uint64_t seed, int64_t lead,
+                                          const fnn_dist_model* m, int32_t device, double* D_out, int64_t ld, int64_t stride, fnn_boot_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_bootstrap_batch(be, "fnn_bootstrap_distances_batch_f64", seq, n, L, lds, batch, seed, lead, m, device, D_out, false, ld, stride, stats);
+    )
+}
+
+int32_t fnn_bootstrap_distances_batch_device_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, int64_t batch, uint64_t seed, int64_t lead,
+                                                 const fnn_dist_model* m, int32_t device, double* d_D_out, int64_t ld, int64_t stride,
+                                                 fnn_boot_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_bootstrap_batch(be, "fnn_bootstrap_distances_batch_device_f64", seq, n, L, lds, batch, seed, lead, m, device, d_D_out, true, ld,
+                                         stride, stats);
+    )
+}
+
+int32_t fnn_bootstrap_draw_max_sites(void) { return fnn::DRAW_MAX_SITES; }
 
 }  // extern "C"

@@ -564,6 +564,36 @@ int32_t fnn_alignment_distances_model_batch_device_f64(const uint8_t* seq, int32
  * (z = seed + (b L + k + 1) * 0x9E3779B97F4A7C15, then the usual two multiply-xorshift rounds).  counts_out: batch x L,
  * dense.  A count above 65535 is FNN_EINVAL. */
 int32_t fnn_bootstrap_counts(int64_t L, int64_t batch, uint64_t seed, uint16_t* counts_out /* batch x L */);
+/* ---- bootstrap replicates drawn on the device ------------------------------------------------
+ * The model entries above for the counts of a bootstrap, without the counts: `batch` counts ALL problems of the call; the
+ * first `lead` of them (0 or 1) are the original data, every site counted once; problem b >= lead is replicate b - lead of
+ * fnn_bootstrap_counts(L, batch - lead, seed, ...).  D_out receives the same bytes as
+ * fnn_alignment_distances_model_batch[_device]_f64 writes on those counts (with lead == 1: an all-ones row in front), for
+ * every model and both saturation policies, and everything said there holds with b in this call's numbering: layout,
+ * chunks, host output written only on success, K2P's recoding, the lowest empty or saturated (b, i, j) named, the argument
+ * checks before any device use.  FNN_EINVAL beyond those: lead outside 0 ... 1 or above batch.
+ * Up to fnn_bootstrap_draw_max_sites() sites (32768: two bytes of a workgroup's 64 KiB of LDS per site) a kernel draws every
+ * replicate's row of the digit planes where the distance kernel reads it: the alignment is the only upload, and of the
+ * counts one word per chunk - the largest - comes back.  Longer alignments are drawn on the host (fnn_bootstrap_counts)
+ * and go the way of the counts entries.  FNN_DRAW_ROUTE=device|host overrides the choice (tests); `device` above the limit
+ * is FNN_EINVAL before any device use.  FNN_DIST_FORCE_DIGITS=2|3 makes any of the distance calls use at least that many
+ * digit planes (tests; the result does not change).
+ * stats: model = what the model entries report; draw_route; max_count = the largest multiplicity of the call; t_draw_s =
+ * the draw kernel's time, part of t_total_s and of no other field. */
+enum { FNN_DRAW_DEVICE = 0, FNN_DRAW_HOST = 1 };
+typedef struct fnn_boot_stats {
+    fnn_dist_model_stats model;
+    int32_t draw_route, max_count;
+    double  t_draw_s;
+    int64_t reserved[4];
+} fnn_boot_stats;
+int32_t fnn_bootstrap_distances_batch_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, int64_t batch, uint64_t seed,
+                                          int64_t lead, const fnn_dist_model* m, int32_t device,
+                                          double* D_out, int64_t ld, int64_t stride, fnn_boot_stats* stats /* may be NULL */);
+int32_t fnn_bootstrap_distances_batch_device_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, int64_t batch, uint64_t seed,
+                                                 int64_t lead, const fnn_dist_model* m, int32_t device,
+                                                 double* d_D_out, int64_t ld, int64_t stride, fnn_boot_stats* stats);
+int32_t fnn_bootstrap_draw_max_sites(void);
 
 /* ---- split support: how often each split occurs among many problems ---------
  * The last stage of a bootstrap run: the orderings and split weights of `batch` problems over ONE taxon set go in, one
