@@ -266,7 +266,9 @@ class FnnDistModelStats(C.Structure):
 
 DIST_JC69, DIST_K2P = 1, 2
 DIST_SAT_FAIL, DIST_SAT_CAP = 0, 1
-DIST_MODELS = {"p": DIST_P, "jc69": DIST_JC69, "k2p": DIST_K2P}
+DIST_F81, DIST_F84, DIST_TN93, DIST_LOGDET = 16, 17, 18, 19   # on the 4 x 4 table of state pairs
+# (Felsenstein 1984 is spelled out: "f84" stays a name these wrappers do not know)
+DIST_MODELS = {"p": DIST_P, "jc69": DIST_JC69, "k2p": DIST_K2P, "f81": DIST_F81, "felsenstein84": DIST_F84, "tn93": DIST_TN93, "logdet": DIST_LOGDET}
 DIST_POLICIES = {"fail": DIST_SAT_FAIL, "cap": DIST_SAT_CAP}
 _DIST_MODEL_ARGS = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(FnnDistModel), C.c_int32,
                     C.c_void_p, C.c_int64, C.c_int64, C.POINTER(FnnDistModelStats)]
@@ -280,7 +282,8 @@ def bind_dist_model(a: Api) -> Api:
 
 
 def dist_model(model="p", states: int = 4, on_saturation="fail", cap=None) -> FnnDistModel:
-    """fnn_dist_model from names ("p", "jc69", "k2p"; "fail", "cap") or the header's numbers; cap=None is 0.0."""
+    """fnn_dist_model from names ("p", "jc69", "k2p", "f81", "felsenstein84", "tn93", "logdet"; "fail", "cap") or the header's numbers;
+    cap=None is 0.0."""
     m = FnnDistModel()
     m.model = DIST_MODELS[model.lower()] if isinstance(model, str) else int(model)
     m.states = int(states)
@@ -295,6 +298,27 @@ def run_dist_model(a: Api, seq, n: int, L: int, lds: int, counts, batch: int, ld
     st = FnnDistModelStats()
     fn = a.alignment_distances_model_batch_device_f64 if on_device else a.alignment_distances_model_batch_f64
     a.check(fn(seq, n, L, lds, counts, batch, ldc, C.byref(m) if m is not None else None, device, out, ld, stride, C.byref(st)))
+    return st
+
+
+_PAIR_COUNTS_ARGS = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+                     C.POINTER(FnnDistModelStats)]
+
+
+def bind_pair_counts(a: Api) -> Api:
+    """The entry points of include/fastnn.h that hand out the 4 x 4 tables of state pairs on `a`."""
+    a._fn("alignment_pair_counts_batch_i64", C.c_int32, _PAIR_COUNTS_ARGS)
+    a._fn("alignment_pair_counts_batch_device_i64", C.c_int32, _PAIR_COUNTS_ARGS)
+    return a
+
+
+def run_pair_counts(a: Api, seq, n: int, L: int, lds: int, counts, batch: int, ldc: int, out, ld: int, stride: int, device: int = 0,
+                    on_device: bool = False):
+    """One pair-count call on raw addresses (out: int64, 16 per (i, j); host memory, or device memory with on_device).  Returns
+    the stats (FnnDistModelStats)."""
+    st = FnnDistModelStats()
+    fn = a.alignment_pair_counts_batch_device_i64 if on_device else a.alignment_pair_counts_batch_i64
+    a.check(fn(seq, n, L, lds, counts, batch, ldc, device, out, ld, stride, C.byref(st)))
     return st
 
 

@@ -376,7 +376,10 @@ def alignment_distances_batch(seq, counts, device: int = 0, out: str = "numpy", 
     in stats["n_recoded"] and treated as missing), over `fnn_alignment_distances_model_batch_f64`: the same exact counts, then a
     fixed sequence of fp64 operations with the library's own log1p.  A saturated pair (the model's distance is infinite) fails
     the call like an empty one with on_saturation="fail"; with "cap" it becomes `cap` (finite, > 0) and
-    stats["n_saturated_problems"] counts the replicates that had one."""
+    stats["n_saturated_problems"] counts the replicates that had one.
+    "f81", "felsenstein84" (F84), "tn93" and "logdet" work on the exact 4 x 4 table of state pairs of every pair (`pair_counts_batch`), recoded
+    as for "k2p", with the pair's own base frequencies; a pair that lacks a base the model divides by is degenerate and follows
+    on_saturation like a saturated one (include/fastnn.h has each model's sequence of operations)."""
     from . import api
     a = api()
     seq, counts = _dist_inputs(seq, counts)
@@ -401,6 +404,33 @@ def alignment_distances_batch(seq, counts, device: int = 0, out: str = "numpy", 
     else:
         raise ValueError('out must be "numpy" or "torch"')
     return D, st.as_dict()
+
+
+def pair_counts_batch(seq, counts, device: int = 0, out: str = "numpy"):
+    """The 4 x 4 tables of state pairs of the replicates `counts` of the alignment `seq` over
+    `fnn_alignment_pair_counts_batch_i64`: F[b, i, j, s, t] = the count-weighted number of sites at which taxon i shows state s
+    and taxon j state t (A 0, C 1, G 2, T 3; recoded as for model="k2p"), exact int64 from the int8 matrix cores; F[b, j, i] is
+    the transpose of F[b, i, j] and F[b, i, i] is zero.  out="numpy" returns an int64 array (B, n, n, 4, 4), out="torch" a
+    torch.int64 tensor on the GPU.  Returns (tables, stats dict).  An empty pair is a table of zeros; nothing fails the call."""
+    from . import api
+    a = api()
+    seq, counts = _dist_inputs(seq, counts)
+    (n, L), B = seq.shape, counts.shape[0]
+
+    def run(ptr, **kw):
+        return _capi.run_pair_counts(a, seq.ctypes.data, n, L, L, counts.ctypes.data, B, L, ptr, max(n, 1), max(16 * n * n, 1), device=device, **kw)
+    if out == "torch":
+        import torch
+        dev = torch.device("cuda", device)
+        F = torch.empty((B, n, n, 4, 4), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        st = run(F.data_ptr() if B and n else None, on_device=True)
+    elif out == "numpy":
+        F = np.empty((B, n, n, 4, 4), dtype=np.int64)
+        st = run(F.ctypes.data)
+    else:
+        raise ValueError('out must be "numpy" or "torch"')
+    return F, st.as_dict()
 
 
 def bootstrap_distances(seq, B: int, seed: int, lead: int = 0, device: int = 0, out: str = "numpy", model: str = "p", states: int = 4,

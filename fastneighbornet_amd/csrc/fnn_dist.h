@@ -23,6 +23,10 @@
 //
 // Bootstrap replicates drawn on the device (k_draw): the planes of a bootstrap are made by a kernel
 // from the seed instead of on the host from counts; its per-lane steps are fnn_draw.h, the host side is the one below.
+//
+// The 4 x 4 table of state pairs (k_dist_pairs): sixteen operands from the same two loads, F81, F84,
+// TN93 and LogDet on the exact table, or the table itself; its per-lane steps are fnn_dist_pairs.h, the host side is the one
+// below.
 #ifndef FNN_DIST_H
 #define FNN_DIST_H
 
@@ -226,6 +230,7 @@ FNN_HD void dist_lane_store_model(const DistArgs& a, const DistModel& dm, const 
 
 }  // namespace fnn
 #include "fnn_draw.h"  // the per-lane steps of k_draw: the planes of a bootstrap made where they are read
+#include "fnn_dist_pairs.h"  // the per-lane steps of k_dist_pairs: the 4 x 4 table of state pairs and its models
 namespace fnn {
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -288,6 +293,17 @@ struct dist_runs_models : std::false_type {};
 template <class B>
 struct dist_runs_models<B, std::void_t<decltype(&B::run_model)>> : std::true_type {};
 
+// A backend that has the 4 x 4 tables adds run_pairs(model or DIST_PAIR_COUNTS, digits, args, pair args, tile groups, replicates
+// of the chunk, &t_kernel_s) and sizes its grid from dist_pairs_rt; one without it refuses FNN_DIST_F81 ... FNN_DIST_LOGDET.
+template <class B, class = void>
+struct dist_runs_pairs : std::false_type {};
+template <class B>
+struct dist_runs_pairs<B, std::void_t<decltype(&B::run_pairs)>> : std::true_type {};
+
+inline int32_t dist_fail_degenerate(const std::string& W, int64_t b, int64_t i, int64_t j) {
+    return fail(FNN_EINVAL, W + "degenerate pair (a base that the model divides by does not occur in it) at (b, i, j) = (" + std::to_string(b) + ", " +
+                                std::to_string(i) + ", " + std::to_string(j) + ")");
+}
 inline int32_t dist_fail_saturated(const std::string& W, int64_t b, int64_t i, int64_t j) {
     return fail(FNN_EINVAL, W + "saturated pair (the model's distance is infinite) at (b, i, j) = (" + std::to_string(b) + ", " + std::to_string(i) +
                                 ", " + std::to_string(j) + ")");
@@ -316,6 +332,7 @@ struct DistSource {
     int32_t draw_route = FNN_DRAW_HOST;  // of a bootstrap
     uint64_t seed = 0;
     int64_t lead = 0;
+    bool pair_counts = false;            // the call wants the 4 x 4 tables (16 int64_t per pair in place of one double), no distance
 };
 
 template <class B>
@@ -330,9 +347,13 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
     bst.draw_route = draw ? FNN_DRAW_DEVICE : FNN_DRAW_HOST;
     if (n <= 0 || L <= 0 || batch < 0) return fail(FNN_EINVAL, W + "needs n > 0, L > 0 and batch >= 0");
     if (!mp) return fail(FNN_EINVAL, W + "NULL model");
-    const int32_t model = mp->model;
-    const bool known = model == FNN_DIST_P || (dist_runs_models<B>::value && (model == FNN_DIST_JC69 || model == FNN_DIST_K2P));
+    const bool tables = src.pair_counts;
+    const int32_t model = tables ? DIST_PAIR_COUNTS : mp->model;
+    const bool pairs = dist_runs_pairs<B>::value && (tables || dist_is_pair_model(model));
+    const bool known = model == FNN_DIST_P || (dist_runs_models<B>::value && (model == FNN_DIST_JC69 || model == FNN_DIST_K2P)) || pairs;
     if (!known) return fail(FNN_EINVAL, W + "unknown model");
+    const bool recoded = model == FNN_DIST_K2P || pairs;  // K2P's codes
+    const int64_t cell = tables ? DIST_PAIR_CELLS : 1;   // 8-byte words per (i, j) of the output
     const bool cap = mp->on_saturation == FNN_DIST_SAT_CAP;
     if (mp->on_saturation != FNN_DIST_SAT_FAIL && !cap) return fail(FNN_EINVAL, W + "unknown saturation policy");
     if (model == FNN_DIST_JC69 && (mp->states < 2 || mp->states > 255)) return fail(FNN_EINVAL, W + "JC69 needs 2 <= states <= 255");
@@ -342,7 +363,7 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
     if (batch == 0) { if (stats) *stats = bst; return FNN_OK; }
     if (!seq || (!src.bootstrap && !src.counts) || !D_out) return fail(FNN_EINVAL, W + "NULL argument");
     if (lds < L || (!src.bootstrap && src.ldc < L)) return fail(FNN_EINVAL, W + "needs lds >= L and ldc >= L");
-    if (ld < n || stride < (int64_t)n * ld) return fail(FNN_EINVAL, W + "needs ld >= n and stride >= n * ld");
+    if (ld < n || stride < (int64_t)n * ld * cell) return fail(FNN_EINVAL, W + (tables ? "needs ld >= n and stride >= 16 * n * ld" : "needs ld >= n and stride >= n * ld"));
     if (draw && !dist_runs_draw<B>::value) return fail(FNN_EINVAL, W + "this backend has no draw kernel");
     if (draw && L > DRAW_MAX_SITES)
         return fail(FNN_EINVAL, W + "the draw kernel takes at most " + std::to_string(DRAW_MAX_SITES) + " sites (FNN_DRAW_ROUTE=device)");
@@ -354,7 +375,7 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
     // one look at the inputs: a missing byte, the largest count, every replicate's total
     bool missing = dist_force_missing();
     uint8_t lut[256];
-    if (model == FNN_DIST_K2P) {  // what the recoding turns into 255 is missing too
+    if (recoded) {  // what the recoding turns into 255 is missing too
         dist_k2p_codes(lut);
         for (int32_t i = 0; i < n; i++) {
             const uint8_t* row = seq + (int64_t)i * lds;
@@ -403,8 +424,8 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
     // valid is the total: an empty replicate has valid == 0 for every pair, (0, 1) the lowest (with missing bytes the
     // kernel flags it, so that a lower replicate with one empty pair is named first; so it does when a saturated pair fails
     // the call, for the same reason)
-    const bool sat_fails = model != FNN_DIST_P && !cap;
-    if (n >= 2 && !missing && !sat_fails)
+    const bool sat_fails = model != FNN_DIST_P && !cap && !tables;
+    if (n >= 2 && !missing && !sat_fails && !tables)
         for (int64_t b = 0; b < batch && !draw; b++)
             if (total[(size_t)b] == 0) return dist_fail_no_site(W, b, 0, 1);
 
@@ -413,7 +434,7 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
     const double tu0 = now_s();
     const int64_t lpad = round_up(L, (int64_t)DIST_K), nn = (int64_t)n * n;
     const std::vector<DistTile> tiles = dist_tiles(n);
-    const int64_t chunk = batch_chunk(batch, 8 * nn + (int64_t)P * lpad, false), cpad = round_up(chunk, (int64_t)DIST_REPS);
+    const int64_t chunk = batch_chunk(batch, 8 * nn * cell + (int64_t)P * lpad, false), cpad = round_up(chunk, (int64_t)DIST_REPS);
     const size_t seq_bytes = (size_t)(n + DIST_PAD_ROWS) * (size_t)lpad, plane_bytes = (size_t)cpad * (size_t)lpad;
     uint8_t* d_seq = (uint8_t*)be.alloc(seq_bytes);
     DistTile* d_tiles = (DistTile*)be.alloc(sizeof(DistTile) * tiles.size());
@@ -421,7 +442,7 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
     int64_t* d_total = (int64_t*)be.alloc(sizeof(int64_t) * (size_t)cpad);
     int32_t* d_bad = (int32_t*)be.alloc(sizeof(int32_t) * (size_t)cpad);
     int32_t* d_sat = model != FNN_DIST_P ? (int32_t*)be.alloc(sizeof(int32_t) * (size_t)cpad) : nullptr;
-    double* d_out = on_device ? nullptr : (double*)be.alloc(sizeof(double) * (size_t)nn * (size_t)chunk);
+    double* d_out = on_device ? nullptr : (double*)be.alloc(sizeof(double) * (size_t)(nn * cell) * (size_t)chunk);
     uint32_t* d_max = draw ? (uint32_t*)be.alloc(sizeof(uint32_t)) : nullptr;
     if (!d_seq || !d_tiles || !d_planes || !d_total || !d_bad || (model != FNN_DIST_P && !d_sat) || (!on_device && !d_out) || (draw && !d_max))
         return fail(FNN_ENOMEM, W + "device allocation failed");
@@ -430,7 +451,7 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
         for (int32_t i = 0; i < n; i++) {
             uint8_t* row = &img[(size_t)i * (size_t)lpad];
             std::memcpy(row, seq + (int64_t)i * lds, (size_t)L);
-            if (model == FNN_DIST_K2P)
+            if (recoded)
                 for (int64_t s = 0; s < L; s++) row[s] = lut[row[s]];
         }
         const uint32_t zero = 0;
@@ -442,7 +463,7 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
     std::vector<int8_t> planes(draw ? 0 : plane_bytes * (size_t)P);
     std::vector<int64_t> tot(draw ? 0 : (size_t)cpad);
     std::vector<int32_t> bad((size_t)cpad), sat(model != FNN_DIST_P ? (size_t)cpad : 0);
-    std::vector<double> stage(on_device ? 0 : (size_t)nn * (size_t)batch), one;
+    std::vector<double> stage(on_device ? 0 : (size_t)(nn * cell) * (size_t)batch), one;
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t cnt = batch - b0 < chunk ? batch - b0 : chunk;
         st.chunks++;
@@ -490,17 +511,28 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
         a.seq = d_seq; a.lpad = lpad; a.tiles = d_tiles; a.planes = d_planes; a.plane_stride = (int64_t)plane_bytes; a.total = d_total;
         a.n = n; a.cnt = cnt; a.bad = d_bad;
         if (on_device) { a.out = D_out + b0 * stride; a.ld = ld; a.stride = stride; }
-        else { a.out = d_out; a.ld = n; a.stride = nn; }
+        else { a.out = d_out; a.ld = n; a.stride = nn * cell; }
         double tk = 0.0;
-        int32_t rk;
+        int32_t rk = FNN_OK;
+        if constexpr (dist_runs_pairs<B>::value) {
+            if (pairs) {  // a degenerate pair is told from a saturated one by the sign of the infinity it leaves
+                DistPairs dp{};
+                dp.sat_value = cap ? mp->cap : __builtin_huge_val();
+                dp.deg_value = cap ? mp->cap : -__builtin_huge_val();
+                dp.sat = d_sat;
+                rk = be.run_pairs(model, P, a, dp, (int64_t)(tiles.size() / DIST_WAVES), cnt, &tk);
+            }
+        }
         if constexpr (dist_runs_models<B>::value) {
-            DistModel dm{};
-            dm.states = mp->states;
-            dm.sat_value = cap ? mp->cap : __builtin_huge_val();
-            dm.sat = d_sat;
-            rk = model != FNN_DIST_P ? be.run_model(model, P, missing, a, dm, (int64_t)(tiles.size() / DIST_WAVES), cnt, &tk)
-                                     : be.run(P, missing, a, (int64_t)(tiles.size() / DIST_WAVES), round_up(cnt, (int64_t)DIST_REPS) / DIST_REPS, &tk);
-        } else
+            if (!pairs) {
+                DistModel dm{};
+                dm.states = mp->states;
+                dm.sat_value = cap ? mp->cap : __builtin_huge_val();
+                dm.sat = d_sat;
+                rk = model != FNN_DIST_P ? be.run_model(model, P, missing, a, dm, (int64_t)(tiles.size() / DIST_WAVES), cnt, &tk)
+                                         : be.run(P, missing, a, (int64_t)(tiles.size() / DIST_WAVES), round_up(cnt, (int64_t)DIST_REPS) / DIST_REPS, &tk);
+            }
+        } else if (!pairs)
             rk = be.run(P, missing, a, (int64_t)(tiles.size() / DIST_WAVES), round_up(cnt, (int64_t)DIST_REPS) / DIST_REPS, &tk);
         if (rk != FNN_OK) return fail(FNN_EHIP, W + "kernel failed (" + be.err() + ")");
         st.t_kernel_s += tk;
@@ -520,16 +552,18 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
                     const double x = one[(size_t)dist_store_index(i, j, a.ld)];
                     if (x != x) return dist_fail_no_site(W, b0 + b, i, j);
                     if (sat_fails && x == __builtin_huge_val()) return dist_fail_saturated(W, b0 + b, i, j);
+                    if (sat_fails && x == -__builtin_huge_val()) return dist_fail_degenerate(W, b0 + b, i, j);
                 }
             return fail(FNN_EHIP, W + "replicate " + std::to_string(b0 + b) + ": flagged without an empty pair");
         }
-        if (!on_device && be.d2h(&stage[(size_t)b0 * (size_t)nn], d_out, sizeof(double) * (size_t)nn * (size_t)cnt) != FNN_OK)
+        if (!on_device && be.d2h(&stage[(size_t)b0 * (size_t)(nn * cell)], d_out, sizeof(double) * (size_t)(nn * cell) * (size_t)cnt) != FNN_OK)
             return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
     }
     if (!on_device)
         for (int64_t b = 0; b < batch; b++)
             for (int32_t r = 0; r < n; r++)
-                std::memcpy(D_out + b * stride + (int64_t)r * ld, &stage[(size_t)b * (size_t)nn + (size_t)r * (size_t)n], sizeof(double) * (size_t)n);
+                std::memcpy(D_out + b * stride + (int64_t)r * ld * cell, &stage[(size_t)b * (size_t)(nn * cell) + (size_t)r * (size_t)(n * cell)],
+                            sizeof(double) * (size_t)(n * cell));
     st.digit_passes = P;
     bst.max_count = (int32_t)cmax;
     st.t_total_s = now_s() - t0;
@@ -571,6 +605,21 @@ int32_t dist_bootstrap_batch(B& be, const char* who, const uint8_t* seq, int32_t
     const int32_t sw = dist_draw_route_switch();
     src.draw_route = sw >= 0 ? sw : (L <= DRAW_MAX_SITES ? FNN_DRAW_DEVICE : FNN_DRAW_HOST);
     return dist_batch_source(be, who, seq, n, L, lds, src, batch, mp, device, D_out, on_device, ld, stride, stats);
+}
+
+// fnn_alignment_pair_counts_batch[_device]_i64: the tables in place of a distance (the 8-byte words of the output are int64_t)
+template <class B>
+int32_t dist_batch_pair_counts(B& be, const char* who, const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts, int64_t batch,
+                               int64_t ldc, int32_t device, int64_t* F_out, bool on_device, int64_t ld, int64_t stride, fnn_dist_model_stats* stats) {
+    DistSource src;
+    src.counts = counts;
+    src.ldc = ldc;
+    src.pair_counts = true;
+    fnn_dist_model pm{};
+    fnn_boot_stats bst{};
+    const int32_t rc = dist_batch_source(be, who, seq, n, L, lds, src, batch, &pm, device, reinterpret_cast<double*>(F_out), on_device, ld, stride, &bst);
+    if (rc == FNN_OK && stats) *stats = bst.model;
+    return rc;
 }
 
 // the p-distance entries: FNN_DIST_P or nothing

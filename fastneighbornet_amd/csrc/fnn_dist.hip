@@ -83,6 +83,38 @@ __global__ __launch_bounds__(DIST_THREADS) void k_dist_model(const DistArgs a, c
     for (int rt = 0; rt < RT; rt++) dist_lane_store_model<MODEL, P, MISSING>(a, dm, t, b0 + DIST_TILE * rt, lane, am[rt], av[rt], at[rt]);
 }
 
+// k_dist_pairs<MODEL, P, RT>: the same walk for the 4 x 4 table of state pairs (the steps are
+// fnn_dist_pairs.h), RT replicate tiles per wave (dist_pairs_rt).  Sixteen 0/1 operands from the two loads, each against every
+// digit plane: 16 x P x RT instructions per 64 sites.  MODEL: FNN_DIST_F81 ... FNN_DIST_LOGDET, or DIST_PAIR_COUNTS for the table.
+template <int MODEL, int P, int RT>
+__global__ __launch_bounds__(DIST_THREADS) void k_dist_pairs(const DistArgs a, const DistPairs dp, const uint32_t tile_groups) {
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    const uint32_t rg = blockIdx.x / tile_groups, tg = blockIdx.x - rg * tile_groups;
+    const DistTile t = a.tiles[(size_t)tg * DIST_WAVES + (size_t)wave];
+    const int64_t b0 = (int64_t)rg * (DIST_TILE * RT);
+    DistAcc acc[RT][DIST_PAIR_CELLS][P];
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+        for (int c = 0; c < DIST_PAIR_CELLS; c++)
+#pragma unroll
+            for (int d = 0; d < P; d++) acc[rt][c][d] = DistAcc{{0, 0, 0, 0}};
+    for (int64_t s = 0; s < a.lpad; s += DIST_K) {
+        DistFrag f[DIST_PAIR_CELLS];
+        dist_lane_a_pairs(a, t, lane, s, f);
+#pragma unroll
+        for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+            for (int d = 0; d < P; d++) {
+                const DistFrag fb = dist_lane_b(a, b0, rt, d, lane, s);
+#pragma unroll
+                for (int c = 0; c < DIST_PAIR_CELLS; c++) acc[rt][c][d] = dist_mma(f[c], fb, acc[rt][c][d]);
+            }
+    }
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++) dist_lane_store_pairs<MODEL, P>(a, dp, t, b0 + DIST_TILE * rt, lane, acc[rt]);
+}
+
 // k_draw: one workgroup makes one row of the digit planes of a bootstrap (the steps are fnn_draw.h).
 // Dynamic LDS: the row's histogram, 2 * lpad bytes <= DRAW_LDS_BYTES.  grid: the chunk's padded rows.
 __global__ __launch_bounds__(DRAW_THREADS) void k_draw(const DrawArgs a) {
@@ -140,6 +172,37 @@ struct DistHipBackend : HipBatchBase {
     int32_t run_model(int32_t model, int32_t P, bool missing, const DistArgs& a, const DistModel& dm, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
         if (model == FNN_DIST_JC69) return run_model_of<FNN_DIST_JC69>(P, missing, a, dm, tile_groups, cnt, t_kernel_s);
         if (model == FNN_DIST_K2P) return run_model_of<FNN_DIST_K2P>(P, missing, a, dm, tile_groups, cnt, t_kernel_s);
+        last = "no kernel for model " + std::to_string(model);
+        return FNN_EHIP;
+    }
+    template <int MODEL, int P>
+    int32_t launch_pairs(const DistArgs& a, const DistPairs& dp, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+        constexpr int RT = dist_pairs_rt(P);
+        const int64_t rep_groups = round_up(cnt, (int64_t)(DIST_TILE * RT)) / (DIST_TILE * RT);
+        if (tile_groups * rep_groups >= ((int64_t)1 << 31)) { last = "too many workgroups for one launch"; return FNN_EHIP; }
+        return timed_launch(reinterpret_cast<const void*>(&k_dist_pairs<MODEL, P, RT>), "k_dist_pairs", 0, [&] {
+            hipLaunchKernelGGL((k_dist_pairs<MODEL, P, RT>), dim3((unsigned)(tile_groups * rep_groups)), dim3(DIST_THREADS), 0, stream, a, dp,
+                               (uint32_t)tile_groups);
+        }, t_kernel_s);
+    }
+    template <int MODEL>
+    int32_t run_pairs_of(int32_t P, const DistArgs& a, const DistPairs& dp, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+        switch (P) {
+            case 1: return launch_pairs<MODEL, 1>(a, dp, tile_groups, cnt, t_kernel_s);
+            case 2: return launch_pairs<MODEL, 2>(a, dp, tile_groups, cnt, t_kernel_s);
+            case 3: return launch_pairs<MODEL, 3>(a, dp, tile_groups, cnt, t_kernel_s);
+        }
+        last = "no kernel for " + std::to_string(P) + " digits";
+        return FNN_EHIP;
+    }
+    int32_t run_pairs(int32_t model, int32_t P, const DistArgs& a, const DistPairs& dp, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+        switch (model) {
+            case FNN_DIST_F81: return run_pairs_of<FNN_DIST_F81>(P, a, dp, tile_groups, cnt, t_kernel_s);
+            case FNN_DIST_F84: return run_pairs_of<FNN_DIST_F84>(P, a, dp, tile_groups, cnt, t_kernel_s);
+            case FNN_DIST_TN93: return run_pairs_of<FNN_DIST_TN93>(P, a, dp, tile_groups, cnt, t_kernel_s);
+            case FNN_DIST_LOGDET: return run_pairs_of<FNN_DIST_LOGDET>(P, a, dp, tile_groups, cnt, t_kernel_s);
+            case DIST_PAIR_COUNTS: return run_pairs_of<DIST_PAIR_COUNTS>(P, a, dp, tile_groups, cnt, t_kernel_s);
+        }
         last = "no kernel for model " + std::to_string(model);
         return FNN_EHIP;
     }
@@ -202,6 +265,24 @@ int32_t fnn_alignment_distances_model_batch_device_f64(const uint8_t* seq, int32
         fnn::DistHipBackend be;
         return fnn::dist_batch_model(be, "fnn_alignment_distances_model_batch_device_f64", seq, n, L, lds, counts, batch, ldc, m, device, d_D_out, true, ld,
                                      stride, stats);
+    )
+}
+
+int32_t fnn_alignment_pair_counts_batch_i64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts, int64_t batch, int64_t ldc,
+                                            int32_t device, int64_t* F_out, int64_t ld, int64_t stride, fnn_dist_model_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch_pair_counts(be, "fnn_alignment_pair_counts_batch_i64", seq, n, L, lds, counts, batch, ldc, device, F_out, false, ld, stride, stats);
+    )
+}
+
+int32_t fnn_alignment_pair_counts_batch_device_i64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts, int64_t batch,
+                                                   int64_t ldc, int32_t device, int64_t* d_F_out, int64_t ld, int64_t stride,
+                                                   fnn_dist_model_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch_pair_counts(be, "fnn_alignment_pair_counts_batch_device_i64", seq, n, L, lds, counts, batch, ldc, device, d_F_out, true, ld,
+                                           stride, stats);
     )
 }
 

@@ -1,6 +1,8 @@
 // fnn_dist_model.h -- corrected alignment distances: what one lane does with the exact integer counts
 // of one (b, i, j) under FNN_DIST_JC69 and FNN_DIST_K2P.  Shared by k_dist_model (fnn_dist.hip) and the CPU driver
 // (tests/emu/fnn_dist_model_emu.cpp); tests/dist_model_common.py restates every line with Python floats.
+// Below those: dist_log and FNN_DIST_F81 ... FNN_DIST_LOGDET on the exact 4 x 4 table of state pairs,
+// shared by k_dist_pairs and tests/emu/fnn_dist_pairs_emu.cpp and restated in tests/dist_pairs_common.py.
 //
 // Every fp64 step below is ONE written operation with one rounding (-ffp-contract=off on host and device): + - * / and
 // conversions of integers below 2^53 only.  No fma, no libm, no ocml: the bits are the same in all three places.
@@ -110,6 +112,171 @@ FNN_HD double dist_k2p(int64_t ts, int64_t tv, int64_t v) {
     const double a = 0.5 * (-dist_log1p(-y1));
     const double b = 0.25 * (-dist_log1p(-y2));
     return a + b;
+}
+
+// log(x) for finite x > 0 after the published fdlibm algorithm (e_log.c): x = 2^k (1 + f) with sqrt(2)/2 < 1 + f < sqrt(2)
+// from the exponent bits (a subnormal x is multiplied by 2^54 first), log(1 + f) = f - s (f - R) or f - (f^2/2 - s (f^2/2 + R))
+// with s = f / (2 + f) and R the same degree-7 polynomial, here split into its even and odd halves as the source has it, and
+// k ln 2 added in two parts.  x <= 0, NaN and +inf are the caller's to keep away; they give NaN here.
+FNN_HD double dist_log(double x) {
+    const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10, two54 = 1.80143985094819840000e+16;
+    const double Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01, Lg3 = 2.857142874366239149e-01,
+                 Lg4 = 2.222219843214978396e-01, Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
+                 Lg7 = 1.479819860511658591e-01;
+    if (!(x > 0.0)) return dist_from_bits(0x7ff8000000000000ull);
+    int32_t hx = (int32_t)(uint32_t)(dist_bits(x) >> 32);
+    if (hx >= 0x7ff00000) return dist_from_bits(0x7ff8000000000000ull);
+    int32_t k = 0;
+    if (hx < 0x00100000) {                                // subnormal
+        k = -54;
+        x = x * two54;
+        hx = (int32_t)(uint32_t)(dist_bits(x) >> 32);
+    }
+    k += (hx >> 20) - 1023;
+    hx &= 0x000fffff;
+    const int32_t i = (hx + 0x95f64) & 0x100000;          // the mantissa is at or above sqrt(2): x / 2^(k + 1)
+    x = dist_from_bits(((uint64_t)(uint32_t)(hx | (i ^ 0x3ff00000)) << 32) | (dist_bits(x) & 0xffffffffull));
+    k += i >> 20;
+    const double f = x - 1.0;
+    const double dk = (double)k;
+    if ((0x000fffff & (2 + hx)) < 3) {                    // |f| < 2^-20
+        if (f == 0.0) {
+            if (k == 0) return 0.0;
+            return dk * ln2_hi + dk * ln2_lo;
+        }
+        const double R = f * f * (0.5 - 0.33333333333333333 * f);
+        if (k == 0) return f - R;
+        return dk * ln2_hi - ((R - dk * ln2_lo) - f);
+    }
+    const double s = f / (2.0 + f);
+    const double z = s * s;
+    const double w = z * z;
+    const double t1 = w * (Lg2 + w * (Lg4 + w * Lg6));
+    const double t2 = z * (Lg1 + w * (Lg3 + w * (Lg5 + w * Lg7)));
+    const double R = t2 + t1;
+    if (((hx - 0x6147a) | (0x6b851 - hx)) > 0) {
+        const double hfsq = 0.5 * f * f;
+        if (k == 0) return f - (hfsq - s * (hfsq + R));
+        return dk * ln2_hi - ((hfsq - (s * (hfsq + R) + dk * ln2_lo)) - f);
+    }
+    if (k == 0) return f - s * (f - R);
+    return dk * ln2_hi - ((s * (f - R) - dk * ln2_lo) - f);
+}
+
+// ---- models on the 4 x 4 table of state pairs: F[4 s + t] = the count-weighted number of sites at which
+// the lower-numbered taxon shows code s and the other code t (A 0, C 1, G 2, T 3); every entry, and 2 v, stays below 2^53.
+//   v = sum F;  r_s = sum_t F[s][t];  c_t = sum_s F[s][t];  n_s = r_s + c_s;  mism = v - trace F          (integers)
+//   ts1 = F[A][G] + F[G][A];  ts2 = F[C][T] + F[T][C];  tv = mism - ts1 - ts2                              (integers)
+//   g_s = (double)n_s / (double)(2 v)   - the pair's own base frequencies -;  gR = gA + gG;  gY = gC + gT
+// The callers have seen v > 0 and mism > 0.  dist_pairs_kind says what a pair is: DEGENERATE by integer tests alone (F84,
+// TN93: some n_s == 0; LogDet: some r_s == 0 or c_s == 0; F81: never, mism > 0 leaves two n_s > 0 and so E > 0), SATURATED
+// when an argument y of a logarithm ln(1 - y) is not below 1.0 (`!(y < 1.0)` on the computed double) or LogDet's computed
+// determinant is not above 0.0.  The value is computed by the sequences below, one rounding per written operation:
+//   F81     sq = ((gA gA + gC gC) + gG gG) + gT gT;  E = 1 - sq;  p = (double)mism / (double)v;  y = p / E;
+//           D = -(E * log1p'(-y))
+//   F84     ct = gC gT;  ag = gA gG;  A = ct / gY + ag / gR;  B = ct + ag;  C = gR gY;  A2 = 2 A;
+//           P = (double)(ts1 + ts2) / (double)v;  Q = (double)tv / (double)v;
+//           y1 = P / A2 + ((A - B) Q) / (A2 C);  y2 = Q / (2 C);
+//           D = -(A2 * log1p'(-y1)) + (2 ((A - B) - C)) * log1p'(-y2)
+//   TN93    k1 = (2 gA gG) / gR  [(2 gA) gG];  k2 = (2 gT gC) / gY  [(2 gT) gC];
+//           k3 = 2 ((gR gY - ((gA gG) gY) / gR) - ((gT gC) gR) / gY);
+//           P1 = (double)ts1 / (double)v;  P2 = (double)ts2 / (double)v;  Q = (double)tv / (double)v;
+//           y1 = P1 / k1 + Q / (2 gR);  y2 = P2 / k2 + Q / (2 gY);  y3 = Q / (2 (gR gY));
+//           D = (-(k1 * log1p'(-y1)) - k2 * log1p'(-y2)) - k3 * log1p'(-y3)
+//   LogDet  m[s][t] = (double)F[s][t] / (double)v;  det = the cofactor expansion along row 0,
+//           det = ((m00 C0 - m01 C1) + m02 C2) - m03 C3,  Ck = det3 of rows 1 ... 3 without column k,
+//           det3(a b c / d e f / g h i) = (a (e i - f h) - b (d i - f g)) + c (d h - e g);
+//           ls = sum over s = A, C, G, T in turn, from 0.0, of (log'(r_s / v) + log'(c_s / v));
+//           D = -(0.25 * (log'(det) - 0.5 * ls))
+enum { DIST_KIND_OK = 0, DIST_KIND_DEGENERATE = 1, DIST_KIND_SATURATED = 2 };
+
+struct DistTable {
+    int64_t F[16];
+    int64_t v, mism, ts1, ts2, tv, r[4], c[4];
+};
+FNN_HD void dist_table_sums(DistTable& t) {
+#pragma unroll
+    for (int s = 0; s < 4; s++) t.r[s] = ((t.F[4 * s] + t.F[4 * s + 1]) + t.F[4 * s + 2]) + t.F[4 * s + 3];
+#pragma unroll
+    for (int s = 0; s < 4; s++) t.c[s] = ((t.F[s] + t.F[4 + s]) + t.F[8 + s]) + t.F[12 + s];
+    t.v = ((t.r[0] + t.r[1]) + t.r[2]) + t.r[3];
+    t.mism = t.v - (((t.F[0] + t.F[5]) + t.F[10]) + t.F[15]);
+    t.ts1 = t.F[2] + t.F[8];
+    t.ts2 = t.F[7] + t.F[13];
+    t.tv = t.mism - t.ts1 - t.ts2;
+}
+FNN_HD double dist_pair_freq(const DistTable& t, int s) { return (double)(t.r[s] + t.c[s]) / (double)(2 * t.v); }
+FNN_HD bool dist_pair_lacks_a_base(const DistTable& t) {
+    return t.r[0] + t.c[0] == 0 || t.r[1] + t.c[1] == 0 || t.r[2] + t.c[2] == 0 || t.r[3] + t.c[3] == 0;
+}
+
+FNN_HD int32_t dist_f81(const DistTable& t, double& D) {
+    const double gA = dist_pair_freq(t, 0), gC = dist_pair_freq(t, 1), gG = dist_pair_freq(t, 2), gT = dist_pair_freq(t, 3);
+    const double sq = ((gA * gA + gC * gC) + gG * gG) + gT * gT;
+    const double E = 1.0 - sq;
+    const double p = (double)t.mism / (double)t.v;
+    const double y = p / E;
+    if (!(y < 1.0)) return DIST_KIND_SATURATED;
+    D = -(E * dist_log1p(-y));
+    return DIST_KIND_OK;
+}
+FNN_HD int32_t dist_f84(const DistTable& t, double& D) {
+    if (dist_pair_lacks_a_base(t)) return DIST_KIND_DEGENERATE;
+    const double gA = dist_pair_freq(t, 0), gC = dist_pair_freq(t, 1), gG = dist_pair_freq(t, 2), gT = dist_pair_freq(t, 3);
+    const double gR = gA + gG, gY = gC + gT;
+    const double ct = gC * gT, ag = gA * gG;
+    const double A = ct / gY + ag / gR;
+    const double B = ct + ag;
+    const double Cc = gR * gY;
+    const double A2 = 2.0 * A;
+    const double P = (double)(t.ts1 + t.ts2) / (double)t.v;
+    const double Q = (double)t.tv / (double)t.v;
+    const double y1 = P / A2 + ((A - B) * Q) / (A2 * Cc);
+    const double y2 = Q / (2.0 * Cc);
+    if (!(y1 < 1.0) || !(y2 < 1.0)) return DIST_KIND_SATURATED;
+    D = -(A2 * dist_log1p(-y1)) + (2.0 * ((A - B) - Cc)) * dist_log1p(-y2);
+    return DIST_KIND_OK;
+}
+FNN_HD int32_t dist_tn93(const DistTable& t, double& D) {
+    if (dist_pair_lacks_a_base(t)) return DIST_KIND_DEGENERATE;
+    const double gA = dist_pair_freq(t, 0), gC = dist_pair_freq(t, 1), gG = dist_pair_freq(t, 2), gT = dist_pair_freq(t, 3);
+    const double gR = gA + gG, gY = gC + gT;
+    const double k1 = ((2.0 * gA) * gG) / gR;
+    const double k2 = ((2.0 * gT) * gC) / gY;
+    const double k3 = 2.0 * ((gR * gY - ((gA * gG) * gY) / gR) - ((gT * gC) * gR) / gY);
+    const double P1 = (double)t.ts1 / (double)t.v;
+    const double P2 = (double)t.ts2 / (double)t.v;
+    const double Q = (double)t.tv / (double)t.v;
+    const double y1 = P1 / k1 + Q / (2.0 * gR);
+    const double y2 = P2 / k2 + Q / (2.0 * gY);
+    const double y3 = Q / (2.0 * (gR * gY));
+    if (!(y1 < 1.0) || !(y2 < 1.0) || !(y3 < 1.0)) return DIST_KIND_SATURATED;
+    D = (-(k1 * dist_log1p(-y1)) - k2 * dist_log1p(-y2)) - k3 * dist_log1p(-y3);
+    return DIST_KIND_OK;
+}
+FNN_HD double dist_det3(double a, double b, double c, double d, double e, double f, double g, double h, double i) {
+    return (a * (e * i - f * h) - b * (d * i - f * g)) + c * (d * h - e * g);
+}
+FNN_HD int32_t dist_logdet(const DistTable& t, double& D) {
+    bool lacks = false;
+#pragma unroll
+    for (int s = 0; s < 4; s++) lacks = lacks || t.r[s] == 0 || t.c[s] == 0;
+    if (lacks) return DIST_KIND_DEGENERATE;
+    const double v = (double)t.v;
+    double m[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) m[k] = (double)t.F[k] / v;
+    const double C0 = dist_det3(m[5], m[6], m[7], m[9], m[10], m[11], m[13], m[14], m[15]);
+    const double C1 = dist_det3(m[4], m[6], m[7], m[8], m[10], m[11], m[12], m[14], m[15]);
+    const double C2 = dist_det3(m[4], m[5], m[7], m[8], m[9], m[11], m[12], m[13], m[15]);
+    const double C3 = dist_det3(m[4], m[5], m[6], m[8], m[9], m[10], m[12], m[13], m[14]);
+    const double det = ((m[0] * C0 - m[1] * C1) + m[2] * C2) - m[3] * C3;
+    if (!(det > 0.0)) return DIST_KIND_SATURATED;
+    double ls = 0.0;
+#pragma unroll
+    for (int s = 0; s < 4; s++) ls = ls + (dist_log((double)t.r[s] / v) + dist_log((double)t.c[s] / v));
+    D = -(0.25 * (dist_log(det) - 0.5 * ls));
+    return DIST_KIND_OK;
 }
 
 }  // namespace fnn

@@ -559,6 +559,51 @@ int32_t fnn_alignment_distances_model_batch_device_f64(const uint8_t* seq, int32
                                                        const uint16_t* counts, int64_t batch, int64_t ldc,
                                                        const fnn_dist_model* m, int32_t device, double* d_D_out, int64_t ld,
                                                        int64_t stride, fnn_dist_model_stats* stats);
+/* ---- the 4 x 4 table of state pairs: F81, F84, TN93, LogDet and the table itself -----------------
+ * Four more values of m->model, numbered from 16 (the family of models on the table; 3 ... 15 stay unknown), for all entries that take a fnn_dist_model (the two above and the bootstrap entries below;
+ * m->states is ignored, m->reserved stays 0).  The alignment is recoded exactly as for K2P (n_recoded, has_missing).  For
+ * i < j, with code_i the code of the LOWER-numbered taxon, as exact integers
+ *     F[s][t] = sum_site counts[b][site] * [code_i == s and code_j == t]      (s, t in A 0, C 1, G 2, T 3)
+ *     v = sum F;  r_s = sum_t F[s][t];  c_t = sum_s F[s][t];  n_s = r_s + c_s;  mism = v - trace F
+ *     ts1 = F[A][G] + F[G][A];  ts2 = F[C][T] + F[T][C];  tv = mism - ts1 - ts2
+ * and, in fp64 with one rounding per written operation (nothing fused), the PAIR's base frequencies
+ *     g_s = (double)n_s / (double)(2 v);  gR = gA + gG;  gY = gC + gT
+ * (frequencies given by the caller or taken over the whole alignment are not offered).  log1p' and log' are the library's
+ * own (fdlibm's algorithms in + - * / and bit operations: the same bits on the device and on any host).
+ *   FNN_DIST_F81     sq = ((gA gA + gC gC) + gG gG) + gT gT;  E = 1 - sq;  p = (double)mism / (double)v;  y = p / E;
+ *                    D = -(E * log1p'(-y))
+ *   FNN_DIST_F84     ct = gC gT;  ag = gA gG;  A = ct / gY + ag / gR;  B = ct + ag;  C = gR gY;  A2 = 2 A;
+ *                    P = (double)(ts1 + ts2) / (double)v;  Q = (double)tv / (double)v;
+ *                    y1 = P / A2 + ((A - B) Q) / (A2 C);  y2 = Q / (2 C);
+ *                    D = -(A2 * log1p'(-y1)) + (2 ((A - B) - C)) * log1p'(-y2)
+ *   FNN_DIST_TN93    k1 = ((2 gA) gG) / gR;  k2 = ((2 gT) gC) / gY;
+ *                    k3 = 2 ((gR gY - ((gA gG) gY) / gR) - ((gT gC) gR) / gY);
+ *                    P1 = (double)ts1 / (double)v;  P2 = (double)ts2 / (double)v;  Q = (double)tv / (double)v;
+ *                    y1 = P1 / k1 + Q / (2 gR);  y2 = P2 / k2 + Q / (2 gY);  y3 = Q / (2 (gR gY));
+ *                    D = (-(k1 * log1p'(-y1)) - k2 * log1p'(-y2)) - k3 * log1p'(-y3)
+ *   FNN_DIST_LOGDET  m[s][t] = (double)F[s][t] / (double)v;  det = ((m00 C0 - m01 C1) + m02 C2) - m03 C3, Ck the 3 x 3
+ *                    determinant of rows 1 ... 3 without column k, (a (e i - f h) - b (d i - f g)) + c (d h - e g) for
+ *                    the rows a b c / d e f / g h i;  ls = the sum over s = A, C, G, T in turn, from 0.0, of
+ *                    (log'((double)r_s / (double)v) + log'((double)c_s / (double)v));
+ *                    D = -(0.25 * (log'(det) - 0.5 * ls)).  The determinant is not exact; it is the same everywhere.
+ * Per pair, in this order: v == 0 is EMPTY (NaN; the call fails under both policies, as above); mism == 0 gives +0.0;
+ * DEGENERATE by integer tests - F84, TN93: some n_s == 0; LogDet: some r_s == 0 or c_s == 0; F81: never -; SATURATED when some
+ * y is not below 1.0 (!(y < 1.0) on the computed double) or LogDet's computed determinant is not above 0.  Degenerate and
+ * saturated pairs follow m->on_saturation alike: FNN_DIST_SAT_FAIL fails the call and fnn_last_error() names the lowest
+ * (b, i, j) that is empty, degenerate or saturated and says which; FNN_DIST_SAT_CAP stores m->cap and counts the replicate in
+ * n_saturated_problems.  D[i][j] and D[j][i] are one value, computed on the table of i < j. */
+enum { FNN_DIST_F81 = 16, FNN_DIST_F84 = 17, FNN_DIST_TN93 = 18, FNN_DIST_LOGDET = 19 };  /* 16 ...: the models of the table; 3 ... 15 are unknown */
+/* The tables themselves, as integers: entry (b, i, j, s, t) at F_out + b * stride + (i * ld + j) * 16 + 4 * s + t for ALL i != j
+ * (the block at (j, i) is the transposed table: there code_i is the row again), 16 zeros at i == j.  ld >= n and
+ * stride >= 16 * n * ld; everything else - the recoding, layout of the inputs, chunks, host output written only on success,
+ * the device variant's in-place output, the argument checks before any device use - is as for the entries above.  No
+ * table fails the call: an empty pair is 16 zeros. */
+int32_t fnn_alignment_pair_counts_batch_i64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const uint16_t* counts,
+                                            int64_t batch, int64_t ldc, int32_t device, int64_t* F_out, int64_t ld,
+                                            int64_t stride, fnn_dist_model_stats* stats /* may be NULL */);
+int32_t fnn_alignment_pair_counts_batch_device_i64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds,
+                                                   const uint16_t* counts, int64_t batch, int64_t ldc, int32_t device,
+                                                   int64_t* d_F_out, int64_t ld, int64_t stride, fnn_dist_model_stats* stats);
 /* Reproducible bootstrap multiplicities, host only (no device needed): replicate b draws k = 0 ... L - 1 and increments
  * site floor(x L / 2^64) (the high half of the 128-bit product), x = the (b L + k)-th output of SplitMix64 for `seed`
  * (z = seed + (b L + k + 1) * 0x9E3779B97F4A7C15, then the usual two multiply-xorshift rounds).  counts_out: batch x L,

@@ -14,8 +14,12 @@ distance call's time, both routes and their ratio.  The condition: (a) faster th
 and numpy's log1p, so its matrices agree to rounding, not bitwise: the largest relative difference is reported - and puts the
 kernel times of all three models of the same run side by side (t_kernel_p_ms, t_kernel_jc69_ms, t_kernel_k2p_ms).
 
+--model f81 | felsenstein84 | tn93 | logdet does the same on the 4 x 4 tables of state pairs - (b) then is numpy's
+sixteen float64 matmuls, one per cell, plus numpy's logarithms - and puts the kernel's time beside the p and K2P kernels' of the
+same run (t_kernel_p_ms, t_kernel_k2p_ms, t_kernel_<model>_ms).
+
     python tools/dist_perf.py [--batch 1024] [--sizes 32,64,140] [--sites 1000,10000] [--missing 0,0.02] [--out FILE]
-                              [--only-a] [--model p|jc69|k2p]
+                              [--only-a] [--model p|jc69|k2p|f81|felsenstein84|tn93|logdet]
 
 --only-a runs route (a) alone (for a kernel trace of one shape); --out appends the JSON lines to FILE as well."""
 import argparse
@@ -50,11 +54,51 @@ def route_a(seq, counts, model="p"):
     return T, orders, st, t1 - t0, t2 - t0
 
 
+PAIR_MODELS = ("f81", "felsenstein84", "tn93", "logdet")
+
+
+def numpy_pair_model(si, sj, w, model):
+    """pairs x B distances from the sixteen cells of every pair's table, each one float64 matmul (exact: integers below 2^53)."""
+    code = np.full(256, 255, dtype=np.uint8)
+    code[[65, 67, 71, 84]] = (0, 1, 2, 3)
+    ci, cj = code[si], code[sj]
+    F = [[((ci == s) & (cj == t)).astype(np.float64) @ w for t in range(4)] for s in range(4)]
+    r = [F[s][0] + F[s][1] + F[s][2] + F[s][3] for s in range(4)]
+    c = [F[0][t] + F[1][t] + F[2][t] + F[3][t] for t in range(4)]
+    v = r[0] + r[1] + r[2] + r[3]
+    if model == "logdet":
+        M = np.stack([np.stack([F[s][t] / v for t in range(4)], axis=-1) for s in range(4)], axis=-2)   # pairs x B x 4 x 4
+        ls = sum(np.log(r[s] / v) + np.log(c[s] / v) for s in range(4))
+        return -0.25 * (np.log(np.linalg.det(M)) - 0.5 * ls)
+    g = [(r[s] + c[s]) / (2.0 * v) for s in range(4)]
+    mism = v - (F[0][0] + F[1][1] + F[2][2] + F[3][3])
+    if model == "f81":
+        E = 1.0 - (g[0] * g[0] + g[1] * g[1] + g[2] * g[2] + g[3] * g[3])
+        return -E * np.log1p(-(mism / v) / E)
+    P1, P2 = (F[0][2] + F[2][0]) / v, (F[1][3] + F[3][1]) / v
+    Q = mism / v - P1 - P2
+    gR, gY = g[0] + g[2], g[1] + g[3]
+    if model == "felsenstein84":
+        A = g[1] * g[3] / gY + g[0] * g[2] / gR
+        Bq = g[1] * g[3] + g[0] * g[2]
+        Cq = gR * gY
+        return -2.0 * A * np.log1p(-(P1 + P2) / (2.0 * A) - (A - Bq) * Q / (2.0 * A * Cq)) + 2.0 * (A - Bq - Cq) * np.log1p(-Q / (2.0 * Cq))
+    k1, k2 = 2.0 * g[0] * g[2] / gR, 2.0 * g[3] * g[1] / gY
+    k3 = 2.0 * (gR * gY - g[0] * g[2] * gY / gR - g[3] * g[1] * gR / gY)
+    return -k1 * np.log1p(-P1 / k1 - Q / (2.0 * gR)) - k2 * np.log1p(-P2 / k2 - Q / (2.0 * gY)) - k3 * np.log1p(-Q / (2.0 * gR * gY))
+
+
 def numpy_matrices(seq, counts, model="p"):
     n, B = seq.shape[0], counts.shape[0]
     iu, ju = np.triu_indices(n, 1)
     w = counts.astype(np.float64).T                                   # L x B
     si, sj = seq[iu], seq[ju]
+    if model in PAIR_MODELS:
+        d = numpy_pair_model(si, sj, w, model).T
+        D = np.zeros((B, n, n))
+        D[:, iu, ju] = d
+        D[:, ju, iu] = d
+        return D
     if (seq == 255).any():
         both = (si != 255) & (sj != 255)
         valid = both.astype(np.float64) @ w                           # pairs x B, exact: integers below 2^53
@@ -97,13 +141,14 @@ def main():
     ap.add_argument("--missing", default="0,0.02")
     ap.add_argument("--out", default=None)
     ap.add_argument("--only-a", action="store_true")
-    ap.add_argument("--model", default="p", choices=["p", "jc69", "k2p"])
+    ap.add_argument("--model", default="p", choices=["p", "jc69", "k2p"] + list(PAIR_MODELS))
     args = ap.parse_args()
     B = args.batch
     # warm both routes: the runtime, the kernels' code objects, numpy's thread pool
     s0 = alignment(8, 256, 1, 0.0)
     c0 = fa.bootstrap_counts(256, 64, 1)
-    for m in sorted({"p", args.model} | ({"jc69", "k2p"} if args.model != "p" else set())):
+    beside = () if args.model == "p" else ("p", "k2p", args.model) if args.model in PAIR_MODELS else ("p", "jc69", "k2p")
+    for m in sorted({"p", args.model} | set(beside)):
         route_a(s0, c0, m)
     route_b(s0, c0, args.model)
     lines = []
@@ -123,8 +168,8 @@ def main():
                 rec = {"model": args.model, "n": n, "L": L, "B": B, "missing": miss, "digit_passes": st["digit_passes"], "has_missing": st["has_missing"],
                        "chunks": st["chunks"], "t_kernel_ms": st["t_kernel_s"] * 1e3, "t_upload_ms": st["t_upload_s"] * 1e3,
                        "t_call_ms": ta_call * 1e3, "t_route_a_ms": ta * 1e3, "out_bytes": B * n * n * 8}
-                if args.model != "p":   # the three kernels side by side: the better of two calls each
-                    for m in ("p", "jc69", "k2p"):
+                if args.model != "p":   # the kernels side by side: the better of two calls each
+                    for m in beside:
                         rec[f"t_kernel_{m}_ms"] = min(fa.alignment_distances_batch(seq, counts, out="torch", model=m)[1]["t_kernel_s"] for _ in range(2)) * 1e3
                 if not args.only_a:
                     tb_best = None
