@@ -257,6 +257,11 @@ class FnnDistModel(C.Structure):
     _fields_ = [("model", C.c_int32), ("states", C.c_int32), ("on_saturation", C.c_int32), ("reserved", C.c_int32), ("cap", C.c_double)]
 
 
+class FnnDistModelRates(C.Structure):
+    """fnn_dist_model_rates: `base.reserved` = DIST_RATES_GAMMA and the entries are handed the address of `base`."""
+    _fields_ = [("base", FnnDistModel), ("shape", C.c_double), ("reserved", C.c_double * 3)]
+
+
 class FnnDistModelStats(C.Structure):
     _fields_ = [("base", FnnDistStats), ("n_recoded", C.c_int64), ("n_saturated_problems", C.c_int64), ("reserved", C.c_int64 * 2)]
 
@@ -270,6 +275,7 @@ DIST_F81, DIST_F84, DIST_TN93, DIST_LOGDET = 16, 17, 18, 19   # on the 4 x 4 tab
 # (Felsenstein 1984 is spelled out: "f84" stays a name these wrappers do not know)
 DIST_MODELS = {"p": DIST_P, "jc69": DIST_JC69, "k2p": DIST_K2P, "f81": DIST_F81, "felsenstein84": DIST_F84, "tn93": DIST_TN93, "logdet": DIST_LOGDET}
 DIST_POLICIES = {"fail": DIST_SAT_FAIL, "cap": DIST_SAT_CAP}
+DIST_RATES_EQUAL, DIST_RATES_GAMMA = 0, 1
 _DIST_MODEL_ARGS = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(FnnDistModel), C.c_int32,
                     C.c_void_p, C.c_int64, C.c_int64, C.POINTER(FnnDistModelStats)]
 
@@ -281,9 +287,16 @@ def bind_dist_model(a: Api) -> Api:
     return a
 
 
-def dist_model(model="p", states: int = 4, on_saturation="fail", cap=None) -> FnnDistModel:
+def dist_model(model="p", states: int = 4, on_saturation="fail", cap=None, gamma_shape=None):
     """fnn_dist_model from names ("p", "jc69", "k2p", "f81", "felsenstein84", "tn93", "logdet"; "fail", "cap") or the header's numbers;
-    cap=None is 0.0."""
+    cap=None is 0.0.  gamma_shape=None: equal rates, a FnnDistModel; a number: a FnnDistModelRates with that shape (the call
+    refuses what is not finite and > 0)."""
+    if gamma_shape is not None:
+        mr = FnnDistModelRates()
+        mr.base = dist_model(model, states, on_saturation, cap)
+        mr.base.reserved = DIST_RATES_GAMMA
+        mr.shape = float(gamma_shape)
+        return mr
     m = FnnDistModel()
     m.model = DIST_MODELS[model.lower()] if isinstance(model, str) else int(model)
     m.states = int(states)
@@ -292,12 +305,19 @@ def dist_model(model="p", states: int = 4, on_saturation="fail", cap=None) -> Fn
     return m
 
 
+def dist_model_ref(m):
+    """What the entries take for `m`: the address of a FnnDistModel, of the first member of a FnnDistModelRates, or NULL."""
+    if m is None:
+        return None
+    return C.byref(m.base) if isinstance(m, FnnDistModelRates) else C.byref(m)
+
+
 def run_dist_model(a: Api, seq, n: int, L: int, lds: int, counts, batch: int, ldc: int, out, ld: int, stride: int, m: FnnDistModel,
                    device: int = 0, on_device: bool = False):
     """`run_dist` through the model entries; m=None passes NULL.  Returns the stats (FnnDistModelStats)."""
     st = FnnDistModelStats()
     fn = a.alignment_distances_model_batch_device_f64 if on_device else a.alignment_distances_model_batch_f64
-    a.check(fn(seq, n, L, lds, counts, batch, ldc, C.byref(m) if m is not None else None, device, out, ld, stride, C.byref(st)))
+    a.check(fn(seq, n, L, lds, counts, batch, ldc, dist_model_ref(m), device, out, ld, stride, C.byref(st)))
     return st
 
 
@@ -356,7 +376,7 @@ def run_boot(a: Api, seq, n: int, L: int, lds: int, batch: int, seed: int, lead:
     m=None passes NULL.  Returns the stats (FnnBootStats)."""
     st = FnnBootStats()
     fn = a.bootstrap_distances_batch_device_f64 if on_device else a.bootstrap_distances_batch_f64
-    a.check(fn(seq, n, L, lds, batch, seed & 0xFFFFFFFFFFFFFFFF, lead, C.byref(m) if m is not None else None, device, out, ld, stride, C.byref(st)))
+    a.check(fn(seq, n, L, lds, batch, seed & 0xFFFFFFFFFFFFFFFF, lead, dist_model_ref(m), device, out, ld, stride, C.byref(st)))
     return st
 
 

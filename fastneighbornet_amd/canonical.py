@@ -364,7 +364,7 @@ def _dist_inputs(seq, counts):
 
 
 def alignment_distances_batch(seq, counts, device: int = 0, out: str = "numpy", model: str = "p", states: int = 4,
-                              on_saturation: str = "fail", cap=None):
+                              on_saturation: str = "fail", cap=None, gamma_shape=None):
     """Distance matrices of the replicates `counts` (uint16 (B, L) site multiplicities) of the alignment `seq` (uint8 (n, L),
     255 = missing: `encode_alignment`) over `fnn_alignment_distances_batch_f64`: exact integer counts on the int8 matrix
     cores and one IEEE division per entry.  out="numpy" returns a float64 array (B, n, n); out="torch" allocates a
@@ -379,16 +379,19 @@ def alignment_distances_batch(seq, counts, device: int = 0, out: str = "numpy", 
     stats["n_saturated_problems"] counts the replicates that had one.
     "f81", "felsenstein84" (F84), "tn93" and "logdet" work on the exact 4 x 4 table of state pairs of every pair (`pair_counts_batch`), recoded
     as for "k2p", with the pair's own base frequencies; a pair that lacks a base the model divides by is degenerate and follows
-    on_saturation like a saturated one (include/fastnn.h has each model's sequence of operations)."""
+    on_saturation like a saturated one (include/fastnn.h has each model's sequence of operations).
+    gamma_shape: None (equal rates across sites) or the shape alpha > 0 of gamma-distributed rates for "jc69", "k2p", "f81",
+    "felsenstein84" and "tn93": alpha * expm1(-log1p(-y) / alpha), with the library's own expm1, in place of every -ln(1 - y);
+    "p" and "logdet" have no gamma form and refuse it.  A pair whose expm1 overflows (a very small alpha) is saturated."""
     from . import api
     a = api()
     seq, counts = _dist_inputs(seq, counts)
     (n, L), B = seq.shape, counts.shape[0]
-    if model == "p":
+    if model == "p" and gamma_shape is None:
         def run(ptr, **kw):
             return _capi.run_dist(a, seq.ctypes.data, n, L, L, counts.ctypes.data, B, L, ptr, max(n, 1), max(n * n, 1), device=device, **kw)
     else:
-        m = _capi.dist_model(model, states, on_saturation, cap)
+        m = _capi.dist_model(model, states, on_saturation, cap, gamma_shape)
 
         def run(ptr, **kw):
             return _capi.run_dist_model(a, seq.ctypes.data, n, L, L, counts.ctypes.data, B, L, ptr, max(n, 1), max(n * n, 1), m, device=device, **kw)
@@ -434,13 +437,13 @@ def pair_counts_batch(seq, counts, device: int = 0, out: str = "numpy"):
 
 
 def bootstrap_distances(seq, B: int, seed: int, lead: int = 0, device: int = 0, out: str = "numpy", model: str = "p", states: int = 4,
-                        on_saturation: str = "fail", cap=None):
+                        on_saturation: str = "fail", cap=None, gamma_shape=None):
     """Distance matrices of B bootstrap replicates of the alignment `seq` (uint8 (n, L)) over
     `fnn_bootstrap_distances_batch_f64`: the replicates of `bootstrap_counts(L, B, seed)` without the counts - up to
     `fnn_bootstrap_draw_max_sites()` sites a kernel draws them on the GPU where the distance kernel reads them, and the
     alignment is all that is uploaded.  lead=1 puts the original data (every site once) in front as problem 0.  Returns
     (matrices (B + lead, n, n), stats dict), bit for bit what `alignment_distances_batch` returns for those counts; out, model,
-    states, on_saturation, cap as there.  stats adds "draw_route" ("device" or "host"), "max_count" and "t_draw_s"."""
+    states, on_saturation, cap, gamma_shape as there.  stats adds "draw_route" ("device" or "host"), "max_count" and "t_draw_s"."""
     from . import api
     a = api()
     seq = np.ascontiguousarray(seq, dtype=np.uint8)
@@ -450,7 +453,7 @@ def bootstrap_distances(seq, B: int, seed: int, lead: int = 0, device: int = 0, 
         raise ValueError("lead must be 0 or 1 and B >= 0")
     n, L = seq.shape
     batch = int(B) + int(lead)
-    m = _capi.dist_model(model, states, on_saturation, cap)
+    m = _capi.dist_model(model, states, on_saturation, cap, gamma_shape)
 
     def run(ptr, **kw):
         return _capi.run_boot(a, seq.ctypes.data, n, L, L, batch, int(seed), int(lead), ptr, max(n, 1), max(n * n, 1), m, device=device, **kw)
@@ -482,15 +485,16 @@ def _bootstrap_matrices(seq, B, seed, lead, draw, device, **model):
 
 
 def bootstrap(seq, B: int, seed: int, weights: bool = True, device: int = 0, model: str = "p", states: int = 4, on_saturation: str = "fail",
-              cap=None, draw: str = "device"):
+              cap=None, draw: str = "device", gamma_shape=None):
     """B bootstrap replicates of the alignment `seq` (uint8 (n, L)) end to end: the distance matrices of the replicates of
     `bootstrap_counts(L, B, seed)` as a tensor on the GPU, `canonical_order_batch` of that tensor and (weights=True)
     `split_weights_batch` of it.  No matrix crosses to the host.  Returns (orders[B, n + 1], W[B, n(n-1)/2] or None, stats) with
-    stats = {"distances": ..., "splits": ... (weights=True)}.  model, states, on_saturation, cap: as `alignment_distances_batch`
-    takes them.  draw="device" (the default) draws the replicates on the GPU (`bootstrap_distances`); draw="host" makes the
+    stats = {"distances": ..., "splits": ... (weights=True)}.  model, states, on_saturation, cap, gamma_shape: as
+    `alignment_distances_batch` takes them.  draw="device" (the default) draws the replicates on the GPU (`bootstrap_distances`); draw="host" makes the
     counts on the host and uploads them: the same matrices, bit for bit."""
     seq = np.ascontiguousarray(seq, dtype=np.uint8)
-    D, dst = _bootstrap_matrices(seq, B, seed, 0, draw, device, model=model, states=states, on_saturation=on_saturation, cap=cap)
+    D, dst = _bootstrap_matrices(seq, B, seed, 0, draw, device, model=model, states=states, on_saturation=on_saturation, cap=cap,
+                                 gamma_shape=gamma_shape)
     orders = canonical_order_batch(D, device=device)
     stats = {"distances": dst}
     W = None
@@ -563,15 +567,16 @@ def key_taxa(key) -> list:
 
 
 def bootstrap_support(seq, B: int, seed: int, threshold: float = 1e-6, device: int = 0, model: str = "p", states: int = 4,
-                      on_saturation: str = "fail", cap=None, draw: str = "device"):
+                      on_saturation: str = "fail", cap=None, draw: str = "device", gamma_shape=None):
     """A bootstrap run with its result: the original alignment as problem 0 (every site once) in front of the B replicates of
     `bootstrap_counts(L, B, seed)`, through distances, orders and split weights as `bootstrap` runs them, then
     `split_support(..., lead=1)`.  Returns (order, weights, table, stats): the order and the weights of the original data, the
     table - its rows with first_b == 0 are the original network's splits above `threshold` in ascending k, `support` the share
-    of the B replicates that hold each - and stats = {"distances", "splits", "support"}.  model, states, on_saturation, cap: as
+    of the B replicates that hold each - and stats = {"distances", "splits", "support"}.  model, states, on_saturation, cap, gamma_shape: as
     `alignment_distances_batch` takes them; draw: as `bootstrap` takes it."""
     seq = np.ascontiguousarray(seq, dtype=np.uint8)
-    D, dst = _bootstrap_matrices(seq, B, seed, 1, draw, device, model=model, states=states, on_saturation=on_saturation, cap=cap)
+    D, dst = _bootstrap_matrices(seq, B, seed, 1, draw, device, model=model, states=states, on_saturation=on_saturation, cap=cap,
+                                 gamma_shape=gamma_shape)
     orders = canonical_order_batch(D, device=device)
     W, sst = split_weights_batch(D, orders, device=device)
     table, ust = split_support(orders, W, threshold=threshold, lead=1, device=device)

@@ -27,6 +27,9 @@
 // The 4 x 4 table of state pairs (k_dist_pairs): sixteen operands from the same two loads, F81, F84,
 // TN93 and LogDet on the exact table, or the table itself; its per-lane steps are fnn_dist_pairs.h, the host side is the one
 // below.
+//
+// Gamma-distributed rates: a shape in DistModel / DistPairs, read by the two model epilogues and filled by
+// the host side from a fnn_dist_model_rates; 0.0 is equal rates.  What a lane does with it is fnn_dist_model.h (dist_rate_log).
 #ifndef FNN_DIST_H
 #define FNN_DIST_H
 
@@ -74,6 +77,7 @@ struct DistModel {
     int32_t states;          // JC69: k
     double sat_value;        // stored for a saturated pair: the cap, or +inf when the call is going to fail
     int32_t* sat;            // sat[b] = 1: some pair of replicate b is saturated (written like bad[])
+    double shape;            // 0.0: equal rates; alpha > 0: gamma-distributed rates
 };
 // replicate tiles per wave of k_dist_model: K2P with three digit planes and `valid` counted holds 9 accumulator sets per
 // replicate tile; at DIST_RT tiles the compiler fills all 256 VGPRs and parks 15 more values in AGPRs inside the loop (no
@@ -201,7 +205,8 @@ FNN_HD void dist_lane_store(const DistArgs& a, const DistTile& t, int64_t b0, in
 }
 
 // The same for a corrected distance (MODEL = FNN_DIST_JC69 or FNN_DIST_K2P; `ts` is read by K2P only): an empty pair is NaN
-// and flags bad[b] as above; a saturated pair is dm.sat_value and flags dm.sat[b]; no mismatch is +0.0.
+// and flags bad[b] as above; a saturated pair is dm.sat_value and flags dm.sat[b]; no mismatch is +0.0.  With dm.shape > 0 a
+// pair whose expm1' overflows is saturated too (fnn_dist_model.h, dist_rate_log).
 template <int MODEL, int P, bool MISSING>
 FNN_HD void dist_lane_store_model(const DistArgs& a, const DistModel& dm, const DistTile& t, int64_t b0, int lane, const DistAcc* mism,
                                   const DistAcc* valid, const DistAcc* ts) {
@@ -221,7 +226,11 @@ FNN_HD void dist_lane_store_model(const DistArgs& a, const DistModel& dm, const 
             const int64_t s = MODEL == FNN_DIST_K2P ? dist_combine<P>(ts, r) : 0;
             const bool sat = MODEL == FNN_DIST_K2P ? dist_k2p_saturated(s, m - s, v) : dist_jc69_saturated(dm.states, m, v);
             if (sat) { dm.sat[b] = 1; d = dm.sat_value; }
-            else d = MODEL == FNN_DIST_K2P ? dist_k2p(s, m - s, v) : dist_jc69(dm.states, m, v);
+            else {
+                bool over = false;
+                d = MODEL == FNN_DIST_K2P ? dist_k2p(s, m - s, v, dm.shape, over) : dist_jc69(dm.states, m, v, dm.shape, over);
+                if (over) { dm.sat[b] = 1; d = dm.sat_value; }
+            }
         }
         D[dist_store_index(t.i, j, a.ld)] = d;
         D[dist_store_index(j, t.i, a.ld)] = d;
@@ -356,6 +365,20 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
     const int64_t cell = tables ? DIST_PAIR_CELLS : 1;   // 8-byte words per (i, j) of the output
     const bool cap = mp->on_saturation == FNN_DIST_SAT_CAP;
     if (mp->on_saturation != FNN_DIST_SAT_FAIL && !cap) return fail(FNN_EINVAL, W + "unknown saturation policy");
+    // rates across sites: mp->reserved; with FNN_DIST_RATES_GAMMA mp is the first member of a fnn_dist_model_rates
+    double shape = 0.0;
+    if (!tables) {
+        if (mp->reserved != FNN_DIST_RATES_EQUAL && mp->reserved != FNN_DIST_RATES_GAMMA)
+            return fail(FNN_EINVAL, W + "unknown rates (the field `reserved` of fnn_dist_model: 0 equal, 1 gamma)");
+        if (mp->reserved == FNN_DIST_RATES_GAMMA) {
+            const fnn_dist_model_rates* mr = reinterpret_cast<const fnn_dist_model_rates*>(mp);
+            if (model == FNN_DIST_P || model == FNN_DIST_LOGDET) return fail(FNN_EINVAL, W + "rates: this model has no gamma form (FNN_DIST_P, FNN_DIST_LOGDET)");
+            if (!(mr->shape > 0.0 && mr->shape <= 1.7976931348623157e308)) return fail(FNN_EINVAL, W + "the shape of the gamma rates must be finite and > 0");
+            if (mr->reserved[0] != 0.0 || mr->reserved[1] != 0.0 || mr->reserved[2] != 0.0)
+                return fail(FNN_EINVAL, W + "the field `reserved` of fnn_dist_model_rates must be zero");
+            shape = mr->shape;
+        }
+    }
     if (model == FNN_DIST_JC69 && (mp->states < 2 || mp->states > 255)) return fail(FNN_EINVAL, W + "JC69 needs 2 <= states <= 255");
     if (model != FNN_DIST_P && cap && !(mp->cap > 0.0 && mp->cap <= 1.7976931348623157e308))
         return fail(FNN_EINVAL, W + "the cap of saturated pairs must be finite and > 0");
@@ -520,6 +543,7 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
                 dp.sat_value = cap ? mp->cap : __builtin_huge_val();
                 dp.deg_value = cap ? mp->cap : -__builtin_huge_val();
                 dp.sat = d_sat;
+                dp.shape = shape;
                 rk = be.run_pairs(model, P, a, dp, (int64_t)(tiles.size() / DIST_WAVES), cnt, &tk);
             }
         }
@@ -529,6 +553,7 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
                 dm.states = mp->states;
                 dm.sat_value = cap ? mp->cap : __builtin_huge_val();
                 dm.sat = d_sat;
+                dm.shape = shape;
                 rk = model != FNN_DIST_P ? be.run_model(model, P, missing, a, dm, (int64_t)(tiles.size() / DIST_WAVES), cnt, &tk)
                                          : be.run(P, missing, a, (int64_t)(tiles.size() / DIST_WAVES), round_up(cnt, (int64_t)DIST_REPS) / DIST_REPS, &tk);
             }

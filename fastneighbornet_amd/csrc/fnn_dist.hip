@@ -50,10 +50,13 @@ __global__ __launch_bounds__(DIST_THREADS) void k_dist(const DistArgs a, const u
 // k_dist_model<MODEL, P, MISSING, RT>: the same walk for a corrected distance, RT replicate tiles per
 // wave (dist_model_rt; the grid's replicate groups hold 16 RT replicates).  JC69 differs from k_dist in the epilogue only; K2P
 // makes the transition operand from the same two loads and keeps a third accumulator set: 4 x P x (2 or 3) instructions
-// per 64 sites.
-template <int MODEL, int P, bool MISSING, int RT>
-__global__ __launch_bounds__(DIST_THREADS) void k_dist_model(const DistArgs a, const DistModel dm, const uint32_t tile_groups) {
+// per 64 sites.  GAMMA: the epilogue reads the shape of gamma-distributed rates; without it the shape is the
+// constant 0.0 there and the correction folds away: the equal-rates variants are the kernels they were.
+template <int MODEL, int P, bool MISSING, int RT, bool GAMMA>
+__global__ __launch_bounds__(DIST_THREADS) void k_dist_model(const DistArgs a, const DistModel dm_in, const uint32_t tile_groups) {
     constexpr bool K2P = MODEL == FNN_DIST_K2P;
+    DistModel dm = dm_in;
+    if (!GAMMA) dm.shape = 0.0;
     const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
     const uint32_t rg = blockIdx.x / tile_groups, tg = blockIdx.x - rg * tile_groups;
     const DistTile t = a.tiles[(size_t)tg * DIST_WAVES + (size_t)wave];
@@ -86,8 +89,11 @@ __global__ __launch_bounds__(DIST_THREADS) void k_dist_model(const DistArgs a, c
 // k_dist_pairs<MODEL, P, RT>: the same walk for the 4 x 4 table of state pairs (the steps are
 // fnn_dist_pairs.h), RT replicate tiles per wave (dist_pairs_rt).  Sixteen 0/1 operands from the two loads, each against every
 // digit plane: 16 x P x RT instructions per 64 sites.  MODEL: FNN_DIST_F81 ... FNN_DIST_LOGDET, or DIST_PAIR_COUNTS for the table.
-template <int MODEL, int P, int RT>
-__global__ __launch_bounds__(DIST_THREADS) void k_dist_pairs(const DistArgs a, const DistPairs dp, const uint32_t tile_groups) {
+// GAMMA: as k_dist_model's (F81, F84 and TN93 only).
+template <int MODEL, int P, int RT, bool GAMMA>
+__global__ __launch_bounds__(DIST_THREADS) void k_dist_pairs(const DistArgs a, const DistPairs dp_in, const uint32_t tile_groups) {
+    DistPairs dp = dp_in;
+    if (!GAMMA) dp.shape = 0.0;
     const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
     const uint32_t rg = blockIdx.x / tile_groups, tg = blockIdx.x - rg * tile_groups;
     const DistTile t = a.tiles[(size_t)tg * DIST_WAVES + (size_t)wave];
@@ -146,15 +152,20 @@ struct DistHipBackend : HipBatchBase {
             hipLaunchKernelGGL(k_draw, dim3((unsigned)rows), dim3(DRAW_THREADS), (size_t)lds_bytes, stream, a);
         }, t_draw_s);
     }
-    template <int MODEL, int P, bool MISSING>
-    int32_t launch_model(const DistArgs& a, const DistModel& dm, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+    template <int MODEL, int P, bool MISSING, bool GAMMA>
+    int32_t launch_model_rates(const DistArgs& a, const DistModel& dm, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
         constexpr int RT = dist_model_rt(MODEL, P, MISSING);
         const int64_t rep_groups = round_up(cnt, (int64_t)(DIST_TILE * RT)) / (DIST_TILE * RT);
         if (tile_groups * rep_groups >= ((int64_t)1 << 31)) { last = "too many workgroups for one launch"; return FNN_EHIP; }
-        return timed_launch(reinterpret_cast<const void*>(&k_dist_model<MODEL, P, MISSING, RT>), "k_dist_model", 0, [&] {
-            hipLaunchKernelGGL((k_dist_model<MODEL, P, MISSING, RT>), dim3((unsigned)(tile_groups * rep_groups)), dim3(DIST_THREADS), 0, stream, a, dm,
-                               (uint32_t)tile_groups);
+        return timed_launch(reinterpret_cast<const void*>(&k_dist_model<MODEL, P, MISSING, RT, GAMMA>), "k_dist_model", 0, [&] {
+            hipLaunchKernelGGL((k_dist_model<MODEL, P, MISSING, RT, GAMMA>), dim3((unsigned)(tile_groups * rep_groups)), dim3(DIST_THREADS), 0, stream, a,
+                               dm, (uint32_t)tile_groups);
         }, t_kernel_s);
+    }
+    template <int MODEL, int P, bool MISSING>
+    int32_t launch_model(const DistArgs& a, const DistModel& dm, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+        return dm.shape != 0.0 ? launch_model_rates<MODEL, P, MISSING, true>(a, dm, tile_groups, cnt, t_kernel_s)
+                               : launch_model_rates<MODEL, P, MISSING, false>(a, dm, tile_groups, cnt, t_kernel_s);
     }
     template <int MODEL>
     int32_t run_model_of(int32_t P, bool missing, const DistArgs& a, const DistModel& dm, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
@@ -175,15 +186,22 @@ struct DistHipBackend : HipBatchBase {
         last = "no kernel for model " + std::to_string(model);
         return FNN_EHIP;
     }
-    template <int MODEL, int P>
-    int32_t launch_pairs(const DistArgs& a, const DistPairs& dp, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+    template <int MODEL, int P, bool GAMMA>
+    int32_t launch_pairs_rates(const DistArgs& a, const DistPairs& dp, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
         constexpr int RT = dist_pairs_rt(P);
         const int64_t rep_groups = round_up(cnt, (int64_t)(DIST_TILE * RT)) / (DIST_TILE * RT);
         if (tile_groups * rep_groups >= ((int64_t)1 << 31)) { last = "too many workgroups for one launch"; return FNN_EHIP; }
-        return timed_launch(reinterpret_cast<const void*>(&k_dist_pairs<MODEL, P, RT>), "k_dist_pairs", 0, [&] {
-            hipLaunchKernelGGL((k_dist_pairs<MODEL, P, RT>), dim3((unsigned)(tile_groups * rep_groups)), dim3(DIST_THREADS), 0, stream, a, dp,
+        return timed_launch(reinterpret_cast<const void*>(&k_dist_pairs<MODEL, P, RT, GAMMA>), "k_dist_pairs", 0, [&] {
+            hipLaunchKernelGGL((k_dist_pairs<MODEL, P, RT, GAMMA>), dim3((unsigned)(tile_groups * rep_groups)), dim3(DIST_THREADS), 0, stream, a, dp,
                                (uint32_t)tile_groups);
         }, t_kernel_s);
+    }
+    template <int MODEL, int P>
+    int32_t launch_pairs(const DistArgs& a, const DistPairs& dp, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+        if constexpr (MODEL == FNN_DIST_F81 || MODEL == FNN_DIST_F84 || MODEL == FNN_DIST_TN93) {  // (the models with a gamma form)
+            if (dp.shape != 0.0) return launch_pairs_rates<MODEL, P, true>(a, dp, tile_groups, cnt, t_kernel_s);
+        }
+        return launch_pairs_rates<MODEL, P, false>(a, dp, tile_groups, cnt, t_kernel_s);
     }
     template <int MODEL>
     int32_t run_pairs_of(int32_t P, const DistArgs& a, const DistPairs& dp, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {

@@ -3,6 +3,8 @@
 // (tests/emu/fnn_dist_model_emu.cpp); tests/dist_model_common.py restates every line with Python floats.
 // Below those: dist_log and FNN_DIST_F81 ... FNN_DIST_LOGDET on the exact 4 x 4 table of state pairs,
 // shared by k_dist_pairs and tests/emu/fnn_dist_pairs_emu.cpp and restated in tests/dist_pairs_common.py.
+// Between them: dist_expm1 and dist_rate_log, gamma-distributed rates for the five logarithmic models,
+// restated in tests/dist_gamma_common.py.
 //
 // Every fp64 step below is ONE written operation with one rounding (-ffp-contract=off on host and device): + - * / and
 // conversions of integers below 2^53 only.  No fma, no libm, no ocml: the bits are the same in all three places.
@@ -96,22 +98,117 @@ FNN_HD double dist_log1p(double x) {
     return dk * ln2_hi - ((hfsq - (s * (hfsq + R) + (dk * ln2_lo + c))) - f);
 }
 
+// e^x - 1 after the published fdlibm algorithm (s_expm1.c): x = k ln 2 + r with |r| <= 0.5 ln 2 (k = +-1 taken directly for
+// 0.5 ln 2 < |x| < 1.5 ln 2, else k = (int)(x / ln 2 +- 0.5)) and c the rounding error of r; expm1(r) = r - (r e - hxs) with
+// hxs = r^2 / 2, R1 = 1 + hxs (Q1 + ... + hxs Q5), t = 3 - R1 r / 2 and e = hxs ((R1 - t) / (6 - r t)); then one of six
+// reconstructions of 2^k (1 + expm1(r)) - 1, the scaling by 2^k an addition to the exponent bits.  NaN gives NaN, +inf and
+// every x above 709.78... give +inf, -inf and every x below -56 ln 2 give -1, |x| < 2^-54 gives x.
+FNN_HD double dist_expm1(double x) {
+    const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10, invln2 = 1.44269504088896338700e+00;
+    const double o_threshold = 7.09782712893383973096e+02;
+    const double Q1 = -3.33333333333331316428e-02, Q2 = 1.58730158725481460165e-03, Q3 = -7.93650757867487942473e-05,
+                 Q4 = 4.00821782732936239552e-06, Q5 = -2.01099218183624371326e-07;
+    const uint64_t bx = dist_bits(x);
+    const bool neg = (bx >> 63) != 0;
+    const uint32_t hx = (uint32_t)(bx >> 32) & 0x7fffffffu;   // exponent and the top 20 mantissa bits of |x|
+    if (hx >= 0x4043687au) {                              // |x| >= 56 ln 2
+        if (hx >= 0x40862e42u) {                          // |x| >= 709.78...
+            if (hx >= 0x7ff00000u) {
+                if (((hx & 0x000fffffu) | (uint32_t)bx) != 0) return x + x;   // NaN
+                return neg ? -1.0 : x;
+            }
+            if (x > o_threshold) return dist_from_bits(0x7ff0000000000000ull);
+        }
+        if (neg) return -1.0;
+    }
+    int32_t k = 0;
+    double c = 0.0;
+    if (hx > 0x3fd62e42u) {                               // |x| > 0.5 ln 2
+        double hi, lo;
+        if (hx < 0x3ff0a2b2u) {                           // |x| < 1.5 ln 2
+            if (!neg) { hi = x - ln2_hi; lo = ln2_lo; k = 1; }
+            else { hi = x + ln2_hi; lo = -ln2_lo; k = -1; }
+        } else {
+            k = (int32_t)(invln2 * x + (neg ? -0.5 : 0.5));
+            const double t = (double)k;
+            hi = x - t * ln2_hi;
+            lo = t * ln2_lo;
+        }
+        x = hi - lo;
+        c = (hi - x) - lo;
+    } else if (hx < 0x3c900000u)                          // |x| < 2^-54 (and -0.0 stays -0.0)
+        return x;
+    const double hfx = 0.5 * x;
+    const double hxs = x * hfx;
+    const double r1 = 1.0 + hxs * (Q1 + hxs * (Q2 + hxs * (Q3 + hxs * (Q4 + hxs * Q5))));
+    double t = 3.0 - r1 * hfx;
+    double e = hxs * ((r1 - t) / (6.0 - x * t));
+    if (k == 0) return x - (x * e - hxs);
+    e = x * (e - c) - c;
+    e = e - hxs;
+    if (k == -1) return 0.5 * (x - e) - 0.5;
+    if (k == 1) {
+        if (x < -0.25) return -2.0 * (e - (x + 0.5));
+        return 1.0 + 2.0 * (x - e);
+    }
+    const uint64_t scale = (uint64_t)(int64_t)k << 52;    // k added to the exponent bits
+    double y;
+    if (k <= -2 || k > 56) {                              // 2^k (1 + expm1(r)) - 1, the 1 inside below an ulp or dominant
+        y = 1.0 - (e - x);
+        if (k == 1024) y = (y * 2.0) * dist_from_bits(0x7fe0000000000000ull);   // (2^1023: the exponent bits would run over)
+        else y = dist_from_bits(dist_bits(y) + scale);
+        return y - 1.0;
+    }
+    if (k < 20) {
+        t = dist_from_bits((uint64_t)(0x3ff00000u - (0x00200000u >> k)) << 32);   // 1 - 2^-k
+        y = t - (e - x);
+        return dist_from_bits(dist_bits(y) + scale);
+    }
+    t = dist_from_bits((uint64_t)(uint32_t)(0x3ff - k) << 52);                    // 2^-k
+    y = x - (e + t);
+    y = y + 1.0;
+    return dist_from_bits(dist_bits(y) + scale);
+}
+
+// ---- rates across sites.  What stands where the equal-rates sequences have log1p'(-y): with shape == 0.0
+// (equal rates) that logarithm; with shape = alpha > 0 (gamma-distributed rates) -g, where
+//   l = log1p'(-y);  t = (-l) / alpha;  e = expm1'(t);  g = alpha * e          (g = alpha ((1 - y)^(-1/alpha) - 1))
+// `over` is set when e is not finite (!(e < inf): a small alpha has pushed t over expm1's overflow threshold); the pair is
+// saturated then.  shape is uniform over the wave (a kernel argument).
+FNN_HD double dist_rate_log(double y, double shape, bool& over) {
+    const double l = dist_log1p(-y);
+    if (shape == 0.0) return l;
+    const double t = (-l) / shape;
+    const double e = dist_expm1(t);
+    if (!(e < dist_from_bits(0x7ff0000000000000ull))) over = true;
+    const double g = shape * e;
+    return -g;
+}
+
 // ---- Jukes-Cantor with k states: m mismatches among v common sites (0 < m, 0 < v; k m and (k - 1) v stay below 2^53)
 FNN_HD bool dist_jc69_saturated(int64_t k, int64_t m, int64_t v) { return k * m >= (k - 1) * v; }
-FNN_HD double dist_jc69(int64_t k, int64_t m, int64_t v) {
+FNN_HD double dist_jc69(int64_t k, int64_t m, int64_t v, double shape, bool& over) {
     const double y = (double)(k * m) / (double)((k - 1) * v);
     const double e = (double)(k - 1) / (double)k;
-    return -(e * dist_log1p(-y));
+    return -(e * dist_rate_log(y, shape, over));
+}
+FNN_HD double dist_jc69(int64_t k, int64_t m, int64_t v) {
+    bool over = false;
+    return dist_jc69(k, m, v, 0.0, over);
 }
 
 // ---- Kimura two-parameter: ts transitions and tv transversions among v common sites (0 < ts + tv, 0 < v)
 FNN_HD bool dist_k2p_saturated(int64_t ts, int64_t tv, int64_t v) { return 2 * ts + tv >= v || 2 * tv >= v; }
-FNN_HD double dist_k2p(int64_t ts, int64_t tv, int64_t v) {
+FNN_HD double dist_k2p(int64_t ts, int64_t tv, int64_t v, double shape, bool& over) {
     const double y1 = (double)(2 * ts + tv) / (double)v;
     const double y2 = (double)(2 * tv) / (double)v;
-    const double a = 0.5 * (-dist_log1p(-y1));
-    const double b = 0.25 * (-dist_log1p(-y2));
+    const double a = 0.5 * (-dist_rate_log(y1, shape, over));
+    const double b = 0.25 * (-dist_rate_log(y2, shape, over));
     return a + b;
+}
+FNN_HD double dist_k2p(int64_t ts, int64_t tv, int64_t v) {
+    bool over = false;
+    return dist_k2p(ts, tv, v, 0.0, over);
 }
 
 // log(x) for finite x > 0 after the published fdlibm algorithm (e_log.c): x = 2^k (1 + f) with sqrt(2)/2 < 1 + f < sqrt(2)
@@ -210,17 +307,18 @@ FNN_HD bool dist_pair_lacks_a_base(const DistTable& t) {
     return t.r[0] + t.c[0] == 0 || t.r[1] + t.c[1] == 0 || t.r[2] + t.c[2] == 0 || t.r[3] + t.c[3] == 0;
 }
 
-FNN_HD int32_t dist_f81(const DistTable& t, double& D) {
+FNN_HD int32_t dist_f81(const DistTable& t, double& D, double shape = 0.0) {
     const double gA = dist_pair_freq(t, 0), gC = dist_pair_freq(t, 1), gG = dist_pair_freq(t, 2), gT = dist_pair_freq(t, 3);
     const double sq = ((gA * gA + gC * gC) + gG * gG) + gT * gT;
     const double E = 1.0 - sq;
     const double p = (double)t.mism / (double)t.v;
     const double y = p / E;
     if (!(y < 1.0)) return DIST_KIND_SATURATED;
-    D = -(E * dist_log1p(-y));
-    return DIST_KIND_OK;
+    bool over = false;
+    D = -(E * dist_rate_log(y, shape, over));
+    return over ? DIST_KIND_SATURATED : DIST_KIND_OK;
 }
-FNN_HD int32_t dist_f84(const DistTable& t, double& D) {
+FNN_HD int32_t dist_f84(const DistTable& t, double& D, double shape = 0.0) {
     if (dist_pair_lacks_a_base(t)) return DIST_KIND_DEGENERATE;
     const double gA = dist_pair_freq(t, 0), gC = dist_pair_freq(t, 1), gG = dist_pair_freq(t, 2), gT = dist_pair_freq(t, 3);
     const double gR = gA + gG, gY = gC + gT;
@@ -234,10 +332,11 @@ FNN_HD int32_t dist_f84(const DistTable& t, double& D) {
     const double y1 = P / A2 + ((A - B) * Q) / (A2 * Cc);
     const double y2 = Q / (2.0 * Cc);
     if (!(y1 < 1.0) || !(y2 < 1.0)) return DIST_KIND_SATURATED;
-    D = -(A2 * dist_log1p(-y1)) + (2.0 * ((A - B) - Cc)) * dist_log1p(-y2);
-    return DIST_KIND_OK;
+    bool over = false;
+    D = -(A2 * dist_rate_log(y1, shape, over)) + (2.0 * ((A - B) - Cc)) * dist_rate_log(y2, shape, over);
+    return over ? DIST_KIND_SATURATED : DIST_KIND_OK;
 }
-FNN_HD int32_t dist_tn93(const DistTable& t, double& D) {
+FNN_HD int32_t dist_tn93(const DistTable& t, double& D, double shape = 0.0) {
     if (dist_pair_lacks_a_base(t)) return DIST_KIND_DEGENERATE;
     const double gA = dist_pair_freq(t, 0), gC = dist_pair_freq(t, 1), gG = dist_pair_freq(t, 2), gT = dist_pair_freq(t, 3);
     const double gR = gA + gG, gY = gC + gT;
@@ -251,8 +350,9 @@ FNN_HD int32_t dist_tn93(const DistTable& t, double& D) {
     const double y2 = P2 / k2 + Q / (2.0 * gY);
     const double y3 = Q / (2.0 * (gR * gY));
     if (!(y1 < 1.0) || !(y2 < 1.0) || !(y3 < 1.0)) return DIST_KIND_SATURATED;
-    D = (-(k1 * dist_log1p(-y1)) - k2 * dist_log1p(-y2)) - k3 * dist_log1p(-y3);
-    return DIST_KIND_OK;
+    bool over = false;
+    D = (-(k1 * dist_rate_log(y1, shape, over)) - k2 * dist_rate_log(y2, shape, over)) - k3 * dist_rate_log(y3, shape, over);
+    return over ? DIST_KIND_SATURATED : DIST_KIND_OK;
 }
 FNN_HD double dist_det3(double a, double b, double c, double d, double e, double f, double g, double h, double i) {
     return (a * (e * i - f * h) - b * (d * i - f * g)) + c * (d * h - e * g);

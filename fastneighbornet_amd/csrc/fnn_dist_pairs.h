@@ -19,6 +19,7 @@ struct DistPairs {
     double sat_value;        // stored for a saturated pair: the cap, or +inf when the call is going to fail
     double deg_value;        // stored for a degenerate pair: the cap, or -inf when the call is going to fail
     int32_t* sat;            // sat[b] = 1: some pair of replicate b is saturated or degenerate (written like bad[])
+    double shape;            // 0.0: equal rates; alpha > 0: gamma-distributed rates (F81, F84, TN93)
 };
 // replicate tiles per wave: 64 P RT accumulator registers beside the sixteen operand fragments (DESIGN.md section 18 has the
 // register table)
@@ -96,8 +97,8 @@ FNN_HD void dist_lane_store_pairs(const DistArgs& a, const DistPairs& dp, const 
         double d = 0.0;
         if (tb.v == 0) { a.bad[b] = 1; d = __builtin_nan(""); }
         else if (tb.mism != 0) {
-            const int32_t kind = MODEL == FNN_DIST_F81 ? dist_f81(tb, d) : MODEL == FNN_DIST_F84 ? dist_f84(tb, d)
-                               : MODEL == FNN_DIST_TN93 ? dist_tn93(tb, d) : dist_logdet(tb, d);
+            const int32_t kind = MODEL == FNN_DIST_F81 ? dist_f81(tb, d, dp.shape) : MODEL == FNN_DIST_F84 ? dist_f84(tb, d, dp.shape)
+                               : MODEL == FNN_DIST_TN93 ? dist_tn93(tb, d, dp.shape) : dist_logdet(tb, d);
             if (kind == DIST_KIND_DEGENERATE) { dp.sat[b] = 1; d = dp.deg_value; }
             else if (kind == DIST_KIND_SATURATED) { dp.sat[b] = 1; d = dp.sat_value; }
         }

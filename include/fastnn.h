@@ -539,7 +539,8 @@ int32_t fnn_alignment_distances_batch_device_f64(const uint8_t* seq, int32_t n, 
  * untouched.  With FNN_DIST_SAT_CAP the entry becomes m->cap (finite, > 0) and n_saturated_problems counts the replicates
  * that had such a pair; an empty pair still fails the call.
  * FNN_EINVAL before any device use, beyond the list above: m == NULL, an unknown model or policy, states outside 2 ... 255
- * for JC69, too many distinct states, cap not finite or <= 0 under FNN_DIST_SAT_CAP.  Set m->reserved to 0. */
+ * for JC69, too many distinct states, cap not finite or <= 0 under FNN_DIST_SAT_CAP.  m->reserved is 0 (equal rates) or selects gamma-distributed
+ * rates (further below). */
 enum { FNN_DIST_JC69 = 1, FNN_DIST_K2P = 2 };
 enum { FNN_DIST_SAT_FAIL = 0, FNN_DIST_SAT_CAP = 1 };
 typedef struct fnn_dist_model {
@@ -561,7 +562,7 @@ int32_t fnn_alignment_distances_model_batch_device_f64(const uint8_t* seq, int32
                                                        int64_t stride, fnn_dist_model_stats* stats);
 /* ---- the 4 x 4 table of state pairs: F81, F84, TN93, LogDet and the table itself -----------------
  * Four more values of m->model, numbered from 16 (the family of models on the table; 3 ... 15 stay unknown), for all entries that take a fnn_dist_model (the two above and the bootstrap entries below;
- * m->states is ignored, m->reserved stays 0).  The alignment is recoded exactly as for K2P (n_recoded, has_missing).  For
+ * m->states is ignored, m->reserved is the rates, below).  The alignment is recoded exactly as for K2P (n_recoded, has_missing).  For
  * i < j, with code_i the code of the LOWER-numbered taxon, as exact integers
  *     F[s][t] = sum_site counts[b][site] * [code_i == s and code_j == t]      (s, t in A 0, C 1, G 2, T 3)
  *     v = sum F;  r_s = sum_t F[s][t];  c_t = sum_s F[s][t];  n_s = r_s + c_s;  mism = v - trace F
@@ -593,6 +594,33 @@ int32_t fnn_alignment_distances_model_batch_device_f64(const uint8_t* seq, int32
  * (b, i, j) that is empty, degenerate or saturated and says which; FNN_DIST_SAT_CAP stores m->cap and counts the replicate in
  * n_saturated_problems.  D[i][j] and D[j][i] are one value, computed on the table of i < j. */
 enum { FNN_DIST_F81 = 16, FNN_DIST_F84 = 17, FNN_DIST_TN93 = 18, FNN_DIST_LOGDET = 19 };  /* 16 ...: the models of the table; 3 ... 15 are unknown */
+/* ---- gamma-distributed rates across sites -----------------------------------------------------
+ * The sequences above assume one rate for all sites.  m->reserved says otherwise: FNN_DIST_RATES_EQUAL (0, everything above)
+ * or FNN_DIST_RATES_GAMMA (1): then `m` MUST POINT AT THE FIRST MEMBER OF A fnn_dist_model_rates, whose `shape` is the
+ * shape parameter alpha > 0 of the gamma distribution (mean 1) and whose reserved[3] are 0.  All entries that take a
+ * fnn_dist_model take it, the bootstrap entries on both draw routes.  For alpha > 0, with expm1' the library's own e^x - 1
+ * (fdlibm's algorithm in + - * / and bit operations, like log1p'),
+ *     g(y):  l = log1p'(-y);  t = (-l) / alpha;  e = expm1'(t);  g = alpha * e          (= alpha ((1 - y)^(-1/alpha) - 1))
+ * stands in place of -ln(1 - y): in the five sequences every log1p'(-y) becomes -g(y), everything else - the coefficients, the
+ * order of the sums, the signs, one rounding per written operation - stays:
+ *   FNN_DIST_JC69    D = -(((double)(k - 1) / (double)k) * (-g(y)))
+ *   FNN_DIST_K2P     D = 0.5 * (-(-g(y1))) + 0.25 * (-(-g(y2)))
+ *   FNN_DIST_F81     D = -(E * (-g(y)))
+ *   FNN_DIST_F84     D = -(A2 * (-g(y1))) + (2 ((A - B) - C)) * (-g(y2))
+ *   FNN_DIST_TN93    D = (-(k1 * (-g(y1))) - k2 * (-g(y2))) - k3 * (-g(y3))
+ * with y, y1, y2, y3 and the coefficients as above (the gamma distances of Jin and Nei and of Tamura and Nei).  The order of
+ * the per-pair tests is unchanged - empty, mism == 0 gives +0.0, degenerate, saturated - and a pair is ALSO SATURATED when
+ * some e is not finite (!(e < inf)): a small alpha has pushed t over expm1's overflow threshold 709.78...  Such a pair
+ * follows m->on_saturation like the others.
+ * FNN_EINVAL before any device use, with the field named: m->reserved other than 0 or 1; shape not finite or <= 0; a non-zero
+ * entry of reserved[3]; FNN_DIST_RATES_GAMMA with FNN_DIST_P or FNN_DIST_LOGDET (neither has a gamma form).  With
+ * FNN_DIST_RATES_EQUAL every entry writes the bytes described above and reads sizeof(fnn_dist_model) bytes of `m` only. */
+enum { FNN_DIST_RATES_EQUAL = 0, FNN_DIST_RATES_GAMMA = 1 };
+typedef struct fnn_dist_model_rates {
+    fnn_dist_model base;   /* base.reserved = FNN_DIST_RATES_GAMMA; pass &base */
+    double  shape;
+    double  reserved[3];
+} fnn_dist_model_rates;
 /* The tables themselves, as integers: entry (b, i, j, s, t) at F_out + b * stride + (i * ld + j) * 16 + 4 * s + t for ALL i != j
  * (the block at (j, i) is the transposed table: there code_i is the row again), 16 zeros at i == j.  ld >= n and
  * stride >= 16 * n * ld; everything else - the recoding, layout of the inputs, chunks, host output written only on success,

@@ -18,8 +18,14 @@ kernel times of all three models of the same run side by side (t_kernel_p_ms, t_
 sixteen float64 matmuls, one per cell, plus numpy's logarithms - and puts the kernel's time beside the p and K2P kernels' of the
 same run (t_kernel_p_ms, t_kernel_k2p_ms, t_kernel_<model>_ms).
 
+--gamma SHAPE (with --model jc69 | k2p | f81 | felsenstein84 | tn93) runs route (a) with gamma-distributed
+rates of that shape.  Route (b) then is what a user had to do before the shape existed: `pair_counts_batch` to the host (16 int64
+per pair and replicate), the gamma formula with numpy's log1p and expm1 on 16 threads, `canonical_order_batch` on the host
+matrices.  The gamma kernel's time stands beside the equal-rates kernel's of the same run (t_kernel_<model>_ms,
+t_kernel_<model>_gamma_ms).
+
     python tools/dist_perf.py [--batch 1024] [--sizes 32,64,140] [--sites 1000,10000] [--missing 0,0.02] [--out FILE]
-                              [--only-a] [--model p|jc69|k2p|f81|felsenstein84|tn93|logdet]
+                              [--only-a] [--model p|jc69|k2p|f81|felsenstein84|tn93|logdet] [--gamma SHAPE]
 
 --only-a runs route (a) alone (for a kernel trace of one shape); --out appends the JSON lines to FILE as well."""
 import argparse
@@ -45,9 +51,9 @@ def alignment(n, L, seed, missing):
     return seq
 
 
-def route_a(seq, counts, model="p"):
+def route_a(seq, counts, model="p", gamma=None):
     t0 = time.perf_counter()
-    T, st = fa.alignment_distances_batch(seq, counts, out="torch", model=model)
+    T, st = fa.alignment_distances_batch(seq, counts, out="torch", model=model, gamma_shape=gamma)
     t1 = time.perf_counter()
     orders = fa.canonical_order_batch(T)
     t2 = time.perf_counter()
@@ -124,6 +130,67 @@ def numpy_matrices(seq, counts, model="p"):
     return D
 
 
+GAMMA_THREADS = 16
+
+
+def numpy_gamma_from_tables(F, model, alpha):
+    """(b, n, n) distances of a slice of replicates from its int64 tables (b, n, n, 4, 4) with numpy's log1p and expm1."""
+    F = F.astype(np.float64)
+    n = F.shape[1]
+
+    def g(y):
+        with np.errstate(invalid="ignore", divide="ignore"):              # (the diagonal's zero tables; overwritten below)
+            return alpha * np.expm1(-np.log1p(-y) / alpha)
+    r, c = F.sum(axis=4), F.sum(axis=3)
+    v = r.sum(axis=3)
+    v = np.where(v == 0.0, 1.0, v)                                    # (the diagonal: zero tables)
+    mism = v - np.trace(F, axis1=3, axis2=4)
+    fr = (r + c) / (2.0 * v[..., None])
+    fr = np.where(fr == 0.0, 0.25, fr)
+    gA, gC, gG, gT = fr[..., 0], fr[..., 1], fr[..., 2], fr[..., 3]
+    P1, P2 = (F[..., 0, 2] + F[..., 2, 0]) / v, (F[..., 1, 3] + F[..., 3, 1]) / v
+    Q = mism / v - P1 - P2
+    gR, gY = gA + gG, gC + gT
+    if model == "jc69":
+        D = 0.75 * g(4.0 * mism / (3.0 * v))
+    elif model == "k2p":
+        D = 0.5 * g(2.0 * (P1 + P2) + Q) + 0.25 * g(2.0 * Q)
+    elif model == "f81":
+        E = 1.0 - (gA * gA + gC * gC + gG * gG + gT * gT)
+        D = E * g((mism / v) / E)
+    elif model == "felsenstein84":
+        A = gC * gT / gY + gA * gG / gR
+        Bq = gC * gT + gA * gG
+        Cq = gR * gY
+        D = 2.0 * A * g((P1 + P2) / (2.0 * A) + (A - Bq) * Q / (2.0 * A * Cq)) - 2.0 * (A - Bq - Cq) * g(Q / (2.0 * Cq))
+    else:
+        k1, k2 = 2.0 * gA * gG / gR, 2.0 * gT * gC / gY
+        k3 = 2.0 * (gR * gY - gA * gG * gY / gR - gT * gC * gR / gY)
+        D = k1 * g(P1 / k1 + Q / (2.0 * gR)) + k2 * g(P2 / k2 + Q / (2.0 * gY)) + k3 * g(Q / (2.0 * gR * gY))
+    D[:, np.arange(n), np.arange(n)] = 0.0
+    return D
+
+
+def route_b_gamma(seq, counts, model, alpha):
+    """The parent's offer: the tables to the host, numpy's gamma formula on GAMMA_THREADS threads, the orders of the host matrices."""
+    from concurrent.futures import ThreadPoolExecutor
+    t0 = time.perf_counter()
+    F, _ = fa.pair_counts_batch(seq, counts)
+    t1 = time.perf_counter()
+    B = F.shape[0]
+    D = np.empty(F.shape[:3], dtype=np.float64)
+    cuts = np.linspace(0, B, GAMMA_THREADS + 1).astype(int)
+
+    def part(k):
+        D[cuts[k]:cuts[k + 1]] = numpy_gamma_from_tables(F[cuts[k]:cuts[k + 1]], model, alpha)
+    with ThreadPoolExecutor(GAMMA_THREADS) as ex:
+        list(ex.map(part, range(GAMMA_THREADS)))
+    t2 = time.perf_counter()
+    orders = fa.canonical_order_batch(D)
+    t3 = time.perf_counter()
+    return D, orders, t1 - t0, t2 - t0, t3 - t0
+
+
 def route_b(seq, counts, model="p"):
     t0 = time.perf_counter()
     D = numpy_matrices(seq, counts, model)
@@ -142,7 +209,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--only-a", action="store_true")
     ap.add_argument("--model", default="p", choices=["p", "jc69", "k2p"] + list(PAIR_MODELS))
+    ap.add_argument("--gamma", type=float, default=None)
     args = ap.parse_args()
+    if args.gamma is not None and args.model in ("p", "logdet"):
+        ap.error("--gamma needs a model with a gamma form")
     B = args.batch
     # warm both routes: the runtime, the kernels' code objects, numpy's thread pool
     s0 = alignment(8, 256, 1, 0.0)
@@ -150,7 +220,11 @@ def main():
     beside = () if args.model == "p" else ("p", "k2p", args.model) if args.model in PAIR_MODELS else ("p", "jc69", "k2p")
     for m in sorted({"p", args.model} | set(beside)):
         route_a(s0, c0, m)
-    route_b(s0, c0, args.model)
+    if args.gamma is not None:
+        route_a(s0, c0, args.model, args.gamma)
+        route_b_gamma(s0, c0, args.model, args.gamma)
+    else:
+        route_b(s0, c0, args.model)
     lines = []
     for miss in [float(x) for x in args.missing.split(",")]:
         for n in [int(x) for x in args.sizes.split(",")]:
@@ -159,7 +233,7 @@ def main():
                 counts = fa.bootstrap_counts(L, B, 7)
                 best = None
                 for _ in range(2):   # (the better of two runs of each route)
-                    T, oa, st, ta_call, ta = route_a(seq, counts, args.model)
+                    T, oa, st, ta_call, ta = route_a(seq, counts, args.model, args.gamma)
                     if best is None or ta < best[0]:
                         best = (ta, ta_call, st)
                     Ta = T.cpu().numpy()
@@ -171,7 +245,24 @@ def main():
                 if args.model != "p":   # the kernels side by side: the better of two calls each
                     for m in beside:
                         rec[f"t_kernel_{m}_ms"] = min(fa.alignment_distances_batch(seq, counts, out="torch", model=m)[1]["t_kernel_s"] for _ in range(2)) * 1e3
-                if not args.only_a:
+                if args.gamma is not None:   # the gamma kernel beside the equal-rates one: alternating, the better of three calls each
+                    tk = {None: [], args.gamma: []}
+                    for _ in range(3):
+                        for sh in (None, args.gamma):
+                            tk[sh].append(fa.alignment_distances_batch(seq, counts, out="torch", model=args.model, gamma_shape=sh)[1]["t_kernel_s"])
+                    rec.update({"gamma": args.gamma, f"t_kernel_{args.model}_ms": min(tk[None]) * 1e3,
+                                f"t_kernel_{args.model}_gamma_ms": min(tk[args.gamma]) * 1e3, "n_pairs_times_B": n * (n - 1) // 2 * B})
+                    if not args.only_a:
+                        tb_best = None
+                        for _ in range(2):
+                            Db, ob, tb_tables, tb_np, tb = route_b_gamma(seq, counts, args.model, args.gamma)
+                            if tb_best is None or tb < tb_best[0]:
+                                tb_best = (tb, tb_tables, tb_np)
+                        rec.update({"t_tables_to_host_ms": tb_best[1] * 1e3, "t_tables_and_numpy_ms": tb_best[2] * 1e3, "t_route_b_ms": tb_best[0] * 1e3,
+                                    "ratio_b_over_a": tb_best[0] / ta, "tables_bytes": 16 * 8 * B * n * n,
+                                    "matrices_bitwise_equal": bool((Ta.view(np.int64) == Db.view(np.int64)).all()),
+                                    "orders_equal": bool((oa == ob).all()), "max_rel_diff": float(np.abs(Ta - Db).max() / np.abs(Db).max())})
+                elif not args.only_a:
                     tb_best = None
                     for _ in range(2):
                         Db, ob, tb_np, tb = route_b(seq, counts, args.model)
