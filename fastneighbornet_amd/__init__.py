@@ -67,6 +67,7 @@ def api() -> _capi.Api:
         _capi.bind_dist_model(a)  # fnn_alignment_distances_model_batch[_device]_f64
         _capi.bind_pair_counts(a)  # fnn_alignment_pair_counts_batch[_device]_i64
         _capi.bind_boot(a)  # fnn_bootstrap_distances_batch[_device]_f64, fnn_bootstrap_draw_max_sites
+        _capi.bind_ranges(a)  # fnn_alignment_distances_ranges[_device]_f64, fnn_alignment_pair_counts_ranges[_device]_i64
         _capi.bind_support(a)  # fnn_split_support[_device]_f64, fnn_split_keys, fnn_split_support_max_n / _min_work
         _api = a
     return _api
@@ -75,4 +76,5 @@ def api() -> _capi.Api:
 from .canonical import (NeighborNetCanonical, NeighborNetLocal, canonical_order, canonical_order_batch, canonical_order_ragged,  # noqa: E402,F401
                         split_weights, split_weights_batch, split_weights_ragged, split_weights_sparse,
                         encode_alignment, bootstrap_counts, alignment_distances_batch, pair_counts_batch, bootstrap_distances, bootstrap,
-                        split_support, split_keys, key_taxa, bootstrap_support)
+                        split_support, split_keys, key_taxa, bootstrap_support,
+                        window_ranges, range_distances, pair_counts_ranges, range_networks, sliding_windows)

@@ -380,6 +380,47 @@ def run_boot(a: Api, seq, n: int, L: int, lds: int, batch: int, seed: int, lead:
     return st
 
 
+class FnnRangeStats(C.Structure):
+    _fields_ = [("model", FnnDistModelStats), ("n_site_blocks", C.c_int64), ("n_site_blocks_dense", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+    def as_dict(self):
+        return dict(self.model.as_dict(), n_site_blocks=self.n_site_blocks, n_site_blocks_dense=self.n_site_blocks_dense)
+
+
+_RANGES_ARGS = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(FnnDistModel), C.c_int32, C.c_void_p,
+                C.c_int64, C.c_int64, C.POINTER(FnnRangeStats)]
+_PAIR_COUNTS_RANGES_ARGS = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                            C.c_int64, C.POINTER(FnnRangeStats)]
+
+
+def bind_ranges(a: Api) -> Api:
+    """The entry points of include/fastnn.h whose problems are site ranges of one alignment on `a`."""
+    a._fn("alignment_distances_ranges_f64", C.c_int32, _RANGES_ARGS)
+    a._fn("alignment_distances_ranges_device_f64", C.c_int32, _RANGES_ARGS)
+    a._fn("alignment_pair_counts_ranges_i64", C.c_int32, _PAIR_COUNTS_RANGES_ARGS)
+    a._fn("alignment_pair_counts_ranges_device_i64", C.c_int32, _PAIR_COUNTS_RANGES_ARGS)
+    return a
+
+
+def run_ranges(a: Api, seq, n: int, L: int, lds: int, starts, ends, batch: int, out, ld: int, stride: int, m: FnnDistModel, device: int = 0,
+               on_device: bool = False):
+    """One range-distance call on raw addresses (seq, starts, ends: host memory, the bounds int64; out: host memory, or device
+    memory with on_device); m=None passes NULL.  Returns the stats (FnnRangeStats)."""
+    st = FnnRangeStats()
+    fn = a.alignment_distances_ranges_device_f64 if on_device else a.alignment_distances_ranges_f64
+    a.check(fn(seq, n, L, lds, starts, ends, batch, dist_model_ref(m), device, out, ld, stride, C.byref(st)))
+    return st
+
+
+def run_pair_counts_ranges(a: Api, seq, n: int, L: int, lds: int, starts, ends, batch: int, out, ld: int, stride: int, device: int = 0,
+                           on_device: bool = False):
+    """One pair-count call over ranges on raw addresses (out: int64, 16 per (i, j)).  Returns the stats (FnnRangeStats)."""
+    st = FnnRangeStats()
+    fn = a.alignment_pair_counts_ranges_device_i64 if on_device else a.alignment_pair_counts_ranges_i64
+    a.check(fn(seq, n, L, lds, starts, ends, batch, device, out, ld, stride, C.byref(st)))
+    return st
+
+
 class FnnSupportStats(C.Structure):
     _fields_ = [("n_problems", C.c_int64), ("n_records", C.c_int64), ("n_splits", C.c_int64),
                 ("words", C.c_int32), ("route", C.c_int32), ("hash_retries", C.c_int32), ("chunks", C.c_int32),

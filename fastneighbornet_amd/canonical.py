@@ -503,6 +503,111 @@ def bootstrap(seq, B: int, seed: int, weights: bool = True, device: int = 0, mod
     return orders, W, stats
 
 
+# ---- site ranges: per-gene matrices and sliding windows without a counts matrix
+
+def window_ranges(L: int, width: int, step: int = 1):
+    """(starts, ends), int64: the windows [k step, k step + width) that lie fully inside [0, L), in order."""
+    L, width, step = int(L), int(width), int(step)
+    if width < 1 or width > L or step < 1:
+        raise ValueError("window_ranges needs 1 <= width <= L and step >= 1")
+    starts = np.arange(0, L - width + 1, step, dtype=np.int64)
+    return starts, starts + width
+
+
+def _range_inputs(seq, starts, ends):
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    starts = np.ascontiguousarray(starts, dtype=np.int64)
+    ends = np.ascontiguousarray(ends, dtype=np.int64)
+    if seq.ndim != 2 or starts.ndim != 1 or ends.shape != starts.shape:
+        raise ValueError("seq must have shape (n, L), starts and ends one shape (B,)")
+    return seq, starts, ends
+
+
+def range_distances(seq, starts, ends, device: int = 0, out: str = "numpy", model: str = "p", states: int = 4, on_saturation: str = "fail",
+                    cap=None, gamma_shape=None):
+    """Distance matrices of the alignment `seq` (uint8 (n, L)) restricted to the site ranges [starts[b], ends[b]) - genes of a
+    concatenated alignment, windows of a scan (`window_ranges`) - over `fnn_alignment_distances_ranges_f64`: bit for bit what
+    `alignment_distances_batch` returns on the 0/1 counts of the ranges, without those counts: the kernel makes its operand
+    from the bounds and walks the ranges' sites only.  Ranges may overlap, nest, repeat and come in any order (ranges that lie
+    close together are cheapest next to each other); an empty range fails like a replicate without sites.  out, model, states,
+    on_saturation, cap, gamma_shape as there.  Returns (matrices (B, n, n), stats dict); stats adds "n_site_blocks" (64-site
+    blocks walked, per tile of 16 consecutive ranges) and "n_site_blocks_dense" (what the counts route would walk)."""
+    from . import api
+    a = api()
+    seq, starts, ends = _range_inputs(seq, starts, ends)
+    (n, L), B = seq.shape, starts.shape[0]
+    m = _capi.dist_model(model, states, on_saturation, cap, gamma_shape)
+
+    def run(ptr, **kw):
+        return _capi.run_ranges(a, seq.ctypes.data, n, L, L, starts.ctypes.data, ends.ctypes.data, B, ptr, max(n, 1), max(n * n, 1), m, device=device, **kw)
+    if out == "torch":
+        import torch
+        dev = torch.device("cuda", device)
+        D = torch.empty((B, n, n), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        st = run(D.data_ptr() if B and n else None, on_device=True)
+    elif out == "numpy":
+        D = np.empty((B, n, n), dtype=np.float64)
+        st = run(D.ctypes.data)
+    else:
+        raise ValueError('out must be "numpy" or "torch"')
+    return D, st.as_dict()
+
+
+def pair_counts_ranges(seq, starts, ends, device: int = 0, out: str = "numpy"):
+    """The 4 x 4 tables of state pairs of the site ranges [starts[b], ends[b]) of the alignment `seq` over
+    `fnn_alignment_pair_counts_ranges_i64`: what `pair_counts_batch` returns on the 0/1 counts of the ranges.  Returns (tables
+    (B, n, n, 4, 4) int64, stats dict as `range_distances` reports it)."""
+    from . import api
+    a = api()
+    seq, starts, ends = _range_inputs(seq, starts, ends)
+    (n, L), B = seq.shape, starts.shape[0]
+
+    def run(ptr, **kw):
+        return _capi.run_pair_counts_ranges(a, seq.ctypes.data, n, L, L, starts.ctypes.data, ends.ctypes.data, B, ptr, max(n, 1), max(16 * n * n, 1),
+                                            device=device, **kw)
+    if out == "torch":
+        import torch
+        dev = torch.device("cuda", device)
+        F = torch.empty((B, n, n, 4, 4), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        st = run(F.data_ptr() if B and n else None, on_device=True)
+    elif out == "numpy":
+        F = np.empty((B, n, n, 4, 4), dtype=np.int64)
+        st = run(F.ctypes.data)
+    else:
+        raise ValueError('out must be "numpy" or "torch"')
+    return F, st.as_dict()
+
+
+def range_networks(seq, starts, ends, weights: bool = True, device: int = 0, model: str = "p", states: int = 4, on_saturation: str = "fail",
+                   cap=None, gamma_shape=None):
+    """One Neighbor-Net per site range end to end, as `bootstrap` runs its replicates: `range_distances` as a tensor on the GPU,
+    `canonical_order_batch` of that tensor and (weights=True) `split_weights_batch` of it.  No matrix crosses to the host.
+    Returns (orders[B, n + 1], W[B, n(n-1)/2] or None, stats) with stats = {"distances": ..., "splits": ... (weights=True)}."""
+    D, dst = range_distances(seq, starts, ends, device=device, out="torch", model=model, states=states, on_saturation=on_saturation, cap=cap,
+                             gamma_shape=gamma_shape)
+    orders = canonical_order_batch(D, device=device)
+    stats = {"distances": dst}
+    W = None
+    if weights:
+        W, stats["splits"] = split_weights_batch(D, orders, device=device)
+    return orders, W, stats
+
+
+def sliding_windows(seq, width: int, step: int = 1, weights: bool = True, device: int = 0, model: str = "p", states: int = 4,
+                    on_saturation: str = "fail", cap=None, gamma_shape=None):
+    """A scan along the alignment `seq`: `range_networks` on `window_ranges(L, width, step)`.  Returns (starts, ends, orders, W,
+    stats)."""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    if seq.ndim != 2:
+        raise ValueError("seq must have shape (n, L)")
+    starts, ends = window_ranges(seq.shape[1], width, step)
+    orders, W, stats = range_networks(seq, starts, ends, weights=weights, device=device, model=model, states=states, on_saturation=on_saturation,
+                                      cap=cap, gamma_shape=gamma_shape)
+    return starts, ends, orders, W, stats
+
+
 # ---- split support: the distinct splits of many problems, tallied (DESIGN.md section 15)
 
 def split_support(orders, W, threshold: float = 1e-6, lead: int = 0, device: int = 0):

@@ -30,6 +30,10 @@
 //
 // Gamma-distributed rates: a shape in DistModel / DistPairs, read by the two model epilogues and filled by
 // the host side from a fnn_dist_model_rates; 0.0 is equal rates.  What a lane does with it is fnn_dist_model.h (dist_rate_log).
+//
+// Site ranges (k_dist_ranges, k_dist_ranges_pairs): problem b is the sites [start_b, end_b), the B operand
+// is made in registers from the two bounds and the walk covers the ranges' span only; the per-lane steps are fnn_dist_ranges.h,
+// the host side is the one below.
 #ifndef FNN_DIST_H
 #define FNN_DIST_H
 
@@ -240,6 +244,7 @@ FNN_HD void dist_lane_store_model(const DistArgs& a, const DistModel& dm, const 
 }  // namespace fnn
 #include "fnn_draw.h"  // the per-lane steps of k_draw: the planes of a bootstrap made where they are read
 #include "fnn_dist_pairs.h"  // the per-lane steps of k_dist_pairs: the 4 x 4 table of state pairs and its models
+#include "fnn_dist_ranges.h"  // the per-lane steps of the range kernels: the B operand from a range's bounds
 namespace fnn {
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -331,9 +336,18 @@ struct dist_runs_draw : std::false_type {};
 template <class B>
 struct dist_runs_draw<B, std::void_t<decltype(&B::run_draw)>> : std::true_type {};
 
+// A backend that has the range kernels (and the models and tables: the ranges take every model) adds
+// run_ranges(model, missing, args, ranges, model args, tile groups, problems of the chunk, &t_kernel_s) and
+// run_ranges_pairs(model or DIST_PAIR_COUNTS, args, ranges, pair args, ...): one window tile of 16 problems per wave.
+template <class B, class = void>
+struct dist_runs_ranges : std::false_type {};
+template <class B>
+struct dist_runs_ranges<B, std::void_t<decltype(&B::run_ranges), decltype(&B::run_ranges_pairs)>> : std::true_type {};
+
 // Where the site multiplicities of a call come from: the caller's array, or a bootstrap of `seed` - problems 0 ... lead - 1
 // the original data (every site once), problem b >= lead replicate b - lead of fnn_bootstrap_counts(L, batch - lead, seed) -
-// drawn on the host into such an array or on the device straight into the planes.
+// drawn on the host into such an array or on the device straight into the planes, or `batch` site
+// ranges, whose 0/1 multiplicities exist nowhere.
 struct DistSource {
     const uint16_t* counts = nullptr;
     int64_t ldc = 0;
@@ -342,6 +356,10 @@ struct DistSource {
     uint64_t seed = 0;
     int64_t lead = 0;
     bool pair_counts = false;            // the call wants the 4 x 4 tables (16 int64_t per pair in place of one double), no distance
+    bool ranges = false;                 // problem b is the sites starts[b] <= s < ends[b]
+    const int64_t* starts = nullptr;
+    const int64_t* ends = nullptr;
+    fnn_range_stats* range_stats = nullptr;  // of a call on ranges: receives n_site_blocks, n_site_blocks_dense
 };
 
 template <class B>
@@ -384,9 +402,17 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
         return fail(FNN_EINVAL, W + "the cap of saturated pairs must be finite and > 0");
     if (L > (((int64_t)1 << 31) - 1) / 127) return fail(FNN_EINVAL, W + "too many sites: 127 L must stay below 2^31 (the int32 digit accumulators)");
     if (batch == 0) { if (stats) *stats = bst; return FNN_OK; }
-    if (!seq || (!src.bootstrap && !src.counts) || !D_out) return fail(FNN_EINVAL, W + "NULL argument");
-    if (lds < L || (!src.bootstrap && src.ldc < L)) return fail(FNN_EINVAL, W + "needs lds >= L and ldc >= L");
+    if (!seq || (!src.bootstrap && !src.ranges && !src.counts) || (src.ranges && (!src.starts || !src.ends)) || !D_out)
+        return fail(FNN_EINVAL, W + "NULL argument");
+    if (lds < L || (!src.bootstrap && !src.ranges && src.ldc < L)) return fail(FNN_EINVAL, W + (src.ranges ? "needs lds >= L" : "needs lds >= L and ldc >= L"));
     if (ld < n || stride < (int64_t)n * ld * cell) return fail(FNN_EINVAL, W + (tables ? "needs ld >= n and stride >= 16 * n * ld" : "needs ld >= n and stride >= n * ld"));
+    if (src.ranges) {
+        if (!dist_runs_ranges<B>::value) return fail(FNN_EINVAL, W + "this backend has no range kernels");
+        for (int64_t b = 0; b < batch; b++)
+            if (src.starts[b] < 0 || src.starts[b] > src.ends[b] || src.ends[b] > L)
+                return fail(FNN_EINVAL, W + "range " + std::to_string(b) + ": needs 0 <= start <= end <= L, got [" + std::to_string(src.starts[b]) + ", " +
+                                            std::to_string(src.ends[b]) + ")");
+    }
     if (draw && !dist_runs_draw<B>::value) return fail(FNN_EINVAL, W + "this backend has no draw kernel");
     if (draw && L > DRAW_MAX_SITES)
         return fail(FNN_EINVAL, W + "the draw kernel takes at most " + std::to_string(DRAW_MAX_SITES) + " sites (FNN_DRAW_ROUTE=device)");
@@ -436,14 +462,19 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
     // (drawn on the device: every row's total is L > 0, and the largest count is the kernel's to report)
     std::vector<int64_t> total(draw ? 0 : (size_t)batch, 0);
     uint32_t cmax = 0;
-    for (int64_t b = 0; b < batch && !draw; b++) {
+    for (int64_t b = 0; b < batch && !draw && !src.ranges; b++) {
         const uint16_t* c = counts + b * ldc;
         int64_t t = 0;
         for (int64_t s = 0; s < L; s++) { t += c[s]; cmax = c[s] > cmax ? c[s] : cmax; }
         total[(size_t)b] = t;
     }
+    // (ranges: the row's total is the range's length, every count is 0 or 1 and there is one digit, whatever the switch says)
+    for (int64_t b = 0; b < batch && src.ranges; b++) {
+        total[(size_t)b] = src.ends[b] - src.starts[b];
+        if (total[(size_t)b] > 0) cmax = 1;
+    }
     int32_t P = dist_digits_of(cmax);
-    if (dist_force_digits() > P) P = dist_force_digits();
+    if (dist_force_digits() > P && !src.ranges) P = dist_force_digits();
     // valid is the total: an empty replicate has valid == 0 for every pair, (0, 1) the lowest (with missing bytes the
     // kernel flags it, so that a lower replicate with one empty pair is named first; so it does when a saturated pair fails
     // the call, for the same reason)
@@ -457,17 +488,21 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
     const double tu0 = now_s();
     const int64_t lpad = round_up(L, (int64_t)DIST_K), nn = (int64_t)n * n;
     const std::vector<DistTile> tiles = dist_tiles(n);
-    const int64_t chunk = batch_chunk(batch, 8 * nn * cell + (int64_t)P * lpad, false), cpad = round_up(chunk, (int64_t)DIST_REPS);
+    const int64_t chunk = batch_chunk(batch, 8 * nn * cell + (src.ranges ? 0 : (int64_t)P * lpad), false), cpad = round_up(chunk, (int64_t)DIST_REPS);
     const size_t seq_bytes = (size_t)(n + DIST_PAD_ROWS) * (size_t)lpad, plane_bytes = (size_t)cpad * (size_t)lpad;
     uint8_t* d_seq = (uint8_t*)be.alloc(seq_bytes);
     DistTile* d_tiles = (DistTile*)be.alloc(sizeof(DistTile) * tiles.size());
-    int8_t* d_planes = (int8_t*)be.alloc(plane_bytes * (size_t)P);
+    int8_t* d_planes = src.ranges ? nullptr : (int8_t*)be.alloc(plane_bytes * (size_t)P);
+    int64_t* d_starts = src.ranges ? (int64_t*)be.alloc(sizeof(int64_t) * (size_t)cpad) : nullptr;
+    int64_t* d_ends = src.ranges ? (int64_t*)be.alloc(sizeof(int64_t) * (size_t)cpad) : nullptr;
+    DistSpan* d_spans = src.ranges ? (DistSpan*)be.alloc(sizeof(DistSpan) * (size_t)(cpad / DIST_TILE)) : nullptr;
     int64_t* d_total = (int64_t*)be.alloc(sizeof(int64_t) * (size_t)cpad);
     int32_t* d_bad = (int32_t*)be.alloc(sizeof(int32_t) * (size_t)cpad);
     int32_t* d_sat = model != FNN_DIST_P ? (int32_t*)be.alloc(sizeof(int32_t) * (size_t)cpad) : nullptr;
     double* d_out = on_device ? nullptr : (double*)be.alloc(sizeof(double) * (size_t)(nn * cell) * (size_t)chunk);
     uint32_t* d_max = draw ? (uint32_t*)be.alloc(sizeof(uint32_t)) : nullptr;
-    if (!d_seq || !d_tiles || !d_planes || !d_total || !d_bad || (model != FNN_DIST_P && !d_sat) || (!on_device && !d_out) || (draw && !d_max))
+    if (!d_seq || !d_tiles || (!src.ranges && !d_planes) || (src.ranges && (!d_starts || !d_ends || !d_spans)) || !d_total || !d_bad ||
+        (model != FNN_DIST_P && !d_sat) || (!on_device && !d_out) || (draw && !d_max))
         return fail(FNN_ENOMEM, W + "device allocation failed");
     {
         std::vector<uint8_t> img(seq_bytes, (uint8_t)FNN_SITE_MISSING);
@@ -483,7 +518,10 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
             return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
     }
     st.t_upload_s += now_s() - tu0;
-    std::vector<int8_t> planes(draw ? 0 : plane_bytes * (size_t)P);
+    std::vector<int8_t> planes(draw || src.ranges ? 0 : plane_bytes * (size_t)P);
+    std::vector<int64_t> r_starts, r_ends;
+    std::vector<DistSpan> r_spans;
+    int64_t site_blocks = 0;
     std::vector<int64_t> tot(draw ? 0 : (size_t)cpad);
     std::vector<int32_t> bad((size_t)cpad), sat(model != FNN_DIST_P ? (size_t)cpad : 0);
     std::vector<double> stage(on_device ? 0 : (size_t)(nn * cell) * (size_t)batch), one;
@@ -511,6 +549,18 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
                     if (!d_planes) return fail(FNN_ENOMEM, W + "device allocation failed");
                 }
             }
+        } else if (src.ranges) {  // the bounds and the tiles' spans in place of planes
+            const double tu = now_s();
+            site_blocks += dist_range_chunk(src.starts + b0, src.ends + b0, cnt, cpad, r_starts, r_ends, r_spans);
+            std::fill(tot.begin(), tot.end(), (int64_t)0);
+            std::fill(bad.begin(), bad.end(), 0);
+            for (int64_t b = 0; b < cnt; b++) tot[(size_t)b] = total[(size_t)(b0 + b)];
+            if (be.h2d(d_starts, r_starts.data(), sizeof(int64_t) * (size_t)cpad) != FNN_OK || be.h2d(d_ends, r_ends.data(), sizeof(int64_t) * (size_t)cpad) != FNN_OK ||
+                be.h2d(d_spans, r_spans.data(), sizeof(DistSpan) * r_spans.size()) != FNN_OK ||
+                be.h2d(d_total, tot.data(), sizeof(int64_t) * (size_t)cpad) != FNN_OK || be.h2d(d_bad, bad.data(), sizeof(int32_t) * (size_t)cpad) != FNN_OK ||
+                (d_sat && be.h2d(d_sat, bad.data(), sizeof(int32_t) * (size_t)cpad) != FNN_OK))  // (zeros)
+                return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
+            st.t_upload_s += now_s() - tu;
         } else {
             const double tu = now_s();
             std::memset(planes.data(), 0, planes.size());  // (padding: zero counts)
@@ -537,8 +587,31 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
         else { a.out = d_out; a.ld = n; a.stride = nn * cell; }
         double tk = 0.0;
         int32_t rk = FNN_OK;
+        bool ran = false;
+        if constexpr (dist_runs_ranges<B>::value) {
+            if (src.ranges) {  // (the model and pair arguments as below)
+                DistRanges dr{};
+                dr.starts = d_starts; dr.ends = d_ends; dr.spans = d_spans;
+                if (pairs) {
+                    DistPairs dp{};
+                    dp.sat_value = cap ? mp->cap : __builtin_huge_val();
+                    dp.deg_value = cap ? mp->cap : -__builtin_huge_val();
+                    dp.sat = d_sat;
+                    dp.shape = shape;
+                    rk = be.run_ranges_pairs(model, a, dr, dp, (int64_t)(tiles.size() / DIST_WAVES), cnt, &tk);
+                } else {
+                    DistModel dm{};
+                    dm.states = mp->states;
+                    dm.sat_value = cap ? mp->cap : __builtin_huge_val();
+                    dm.sat = d_sat;
+                    dm.shape = shape;
+                    rk = be.run_ranges(model, missing, a, dr, dm, (int64_t)(tiles.size() / DIST_WAVES), cnt, &tk);
+                }
+                ran = true;
+            }
+        }
         if constexpr (dist_runs_pairs<B>::value) {
-            if (pairs) {  // a degenerate pair is told from a saturated one by the sign of the infinity it leaves
+            if (pairs && !ran) {  // a degenerate pair is told from a saturated one by the sign of the infinity it leaves
                 DistPairs dp{};
                 dp.sat_value = cap ? mp->cap : __builtin_huge_val();
                 dp.deg_value = cap ? mp->cap : -__builtin_huge_val();
@@ -548,7 +621,7 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
             }
         }
         if constexpr (dist_runs_models<B>::value) {
-            if (!pairs) {
+            if (!pairs && !ran) {
                 DistModel dm{};
                 dm.states = mp->states;
                 dm.sat_value = cap ? mp->cap : __builtin_huge_val();
@@ -557,7 +630,7 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
                 rk = model != FNN_DIST_P ? be.run_model(model, P, missing, a, dm, (int64_t)(tiles.size() / DIST_WAVES), cnt, &tk)
                                          : be.run(P, missing, a, (int64_t)(tiles.size() / DIST_WAVES), round_up(cnt, (int64_t)DIST_REPS) / DIST_REPS, &tk);
             }
-        } else if (!pairs)
+        } else if (!pairs && !ran)
             rk = be.run(P, missing, a, (int64_t)(tiles.size() / DIST_WAVES), round_up(cnt, (int64_t)DIST_REPS) / DIST_REPS, &tk);
         if (rk != FNN_OK) return fail(FNN_EHIP, W + "kernel failed (" + be.err() + ")");
         st.t_kernel_s += tk;
@@ -591,6 +664,10 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
                             sizeof(double) * (size_t)(n * cell));
     st.digit_passes = P;
     bst.max_count = (int32_t)cmax;
+    if (src.range_stats) {
+        src.range_stats->n_site_blocks = site_blocks;
+        src.range_stats->n_site_blocks_dense = (batch + DIST_TILE - 1) / DIST_TILE * (lpad / DIST_K);
+    }
     st.t_total_s = now_s() - t0;
     if (stats) *stats = bst;
     return FNN_OK;
@@ -644,6 +721,26 @@ int32_t dist_batch_pair_counts(B& be, const char* who, const uint8_t* seq, int32
     fnn_boot_stats bst{};
     const int32_t rc = dist_batch_source(be, who, seq, n, L, lds, src, batch, &pm, device, reinterpret_cast<double*>(F_out), on_device, ld, stride, &bst);
     if (rc == FNN_OK && stats) *stats = bst.model;
+    return rc;
+}
+
+// fnn_alignment_distances_ranges[_device]_f64 and, with m == nullptr and tables, fnn_alignment_pair_counts_ranges[_device]_i64
+template <class B>
+int32_t dist_batch_ranges(B& be, const char* who, const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts, const int64_t* ends,
+                          int64_t batch, const fnn_dist_model* mp, bool tables, int32_t device, double* D_out, bool on_device, int64_t ld, int64_t stride,
+                          fnn_range_stats* stats) {
+    fnn_range_stats rst{};
+    DistSource src;
+    src.ranges = true;
+    src.starts = starts;
+    src.ends = ends;
+    src.pair_counts = tables;
+    src.range_stats = &rst;
+    fnn_dist_model pm{};
+    fnn_boot_stats bst{};
+    const int32_t rc = dist_batch_source(be, who, seq, n, L, lds, src, batch, tables ? &pm : mp, device, D_out, on_device, ld, stride, &bst);
+    rst.model = bst.model;
+    if (rc == FNN_OK && stats) *stats = rst;
     return rc;
 }
 

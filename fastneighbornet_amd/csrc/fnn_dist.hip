@@ -7,6 +7,9 @@
 // 4 x P (x 2 with MISSING) v_mfma_i32_16x16x64_i8.  No LDS, no atomics, no hand-over; vector stores and plain C++ only.
 //
 // k_draw (fnn_draw.h) makes the digit planes of a bootstrap on the device, one workgroup per row.
+//
+// k_dist_ranges, k_dist_ranges_pairs (fnn_dist_ranges.h): the same pair tiles against problems that are site
+// ranges.  The B operand is made in registers from a range's two bounds and the walk covers the span of the wave's window tile.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -121,6 +124,60 @@ __global__ __launch_bounds__(DIST_THREADS) void k_dist_pairs(const DistArgs a, c
     for (int rt = 0; rt < RT; rt++) dist_lane_store_pairs<MODEL, P>(a, dp, t, b0 + DIST_TILE * rt, lane, acc[rt]);
 }
 
+// k_dist_ranges<MODEL, MISSING, GAMMA>: k_dist (MODEL = FNN_DIST_P) and k_dist_model for problems that are site ranges
+// (the steps are fnn_dist_ranges.h).  A wave takes one pair tile and one window tile of 16 ranges (the
+// grid's slow index is the window tile); a lane reads the bounds of its column once.  The walk covers the tile's span from the
+// host's table, wave-uniform; per 64 sites a lane makes the A operands as the kernels above do and the 0/1 B operand from the
+// bounds: no plane is loaded, one digit.  The epilogues are the ones above with P = 1.
+template <int MODEL, bool MISSING, bool GAMMA>
+__global__ __launch_bounds__(DIST_THREADS) void k_dist_ranges(const DistArgs a, const DistRanges dr, const DistModel dm_in, const uint32_t tile_groups) {
+    constexpr bool K2P = MODEL == FNN_DIST_K2P;
+    DistModel dm = dm_in;
+    if (!GAMMA) dm.shape = 0.0;
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    const uint32_t wt = blockIdx.x / tile_groups, tg = blockIdx.x - wt * tile_groups;
+    const DistTile t = a.tiles[(size_t)tg * DIST_WAVES + (size_t)wave];
+    const int64_t b0 = (int64_t)wt * DIST_TILE;
+    const DistSpan sp = dr.spans[wt];
+    const DistRangeLane rl = dist_lane_range(dr, b0, lane);
+    DistAcc am[1] = {DistAcc{{0, 0, 0, 0}}}, av[1] = {DistAcc{{0, 0, 0, 0}}}, at[1] = {DistAcc{{0, 0, 0, 0}}};
+    for (int32_t s = sp.lo; s < sp.hi; s += DIST_K) {
+        DistFrag fm, fv, ft;
+        if (K2P) dist_lane_a_ts<MISSING>(a, t, lane, s, fm, fv, ft);
+        else dist_lane_a<MISSING>(a, t, lane, s, fm, fv);
+        const DistFrag fb = dist_lane_b_range(rl, lane, s);
+        am[0] = dist_mma(fm, fb, am[0]);
+        if (MISSING) av[0] = dist_mma(fv, fb, av[0]);
+        if (K2P) at[0] = dist_mma(ft, fb, at[0]);
+    }
+    if constexpr (MODEL == FNN_DIST_P) dist_lane_store<1, MISSING>(a, t, b0, lane, am, av);
+    else dist_lane_store_model<MODEL, 1, MISSING>(a, dm, t, b0, lane, am, av, at);
+}
+
+// k_dist_ranges_pairs<MODEL, GAMMA>: k_dist_pairs for problems that are site ranges, in the same way.
+template <int MODEL, bool GAMMA>
+__global__ __launch_bounds__(DIST_THREADS) void k_dist_ranges_pairs(const DistArgs a, const DistRanges dr, const DistPairs dp_in, const uint32_t tile_groups) {
+    DistPairs dp = dp_in;
+    if (!GAMMA) dp.shape = 0.0;
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    const uint32_t wt = blockIdx.x / tile_groups, tg = blockIdx.x - wt * tile_groups;
+    const DistTile t = a.tiles[(size_t)tg * DIST_WAVES + (size_t)wave];
+    const int64_t b0 = (int64_t)wt * DIST_TILE;
+    const DistSpan sp = dr.spans[wt];
+    const DistRangeLane rl = dist_lane_range(dr, b0, lane);
+    DistAcc acc[DIST_PAIR_CELLS][1];
+#pragma unroll
+    for (int c = 0; c < DIST_PAIR_CELLS; c++) acc[c][0] = DistAcc{{0, 0, 0, 0}};
+    for (int32_t s = sp.lo; s < sp.hi; s += DIST_K) {
+        DistFrag f[DIST_PAIR_CELLS];
+        dist_lane_a_pairs(a, t, lane, s, f);
+        const DistFrag fb = dist_lane_b_range(rl, lane, s);
+#pragma unroll
+        for (int c = 0; c < DIST_PAIR_CELLS; c++) acc[c][0] = dist_mma(f[c], fb, acc[c][0]);
+    }
+    dist_lane_store_pairs<MODEL, 1>(a, dp, t, b0, lane, acc);
+}
+
 // k_draw: one workgroup makes one row of the digit planes of a bootstrap (the steps are fnn_draw.h).
 // Dynamic LDS: the row's histogram, 2 * lpad bytes <= DRAW_LDS_BYTES.  grid: the chunk's padded rows.
 __global__ __launch_bounds__(DRAW_THREADS) void k_draw(const DrawArgs a) {
@@ -220,6 +277,61 @@ struct DistHipBackend : HipBatchBase {
             case FNN_DIST_TN93: return run_pairs_of<FNN_DIST_TN93>(P, a, dp, tile_groups, cnt, t_kernel_s);
             case FNN_DIST_LOGDET: return run_pairs_of<FNN_DIST_LOGDET>(P, a, dp, tile_groups, cnt, t_kernel_s);
             case DIST_PAIR_COUNTS: return run_pairs_of<DIST_PAIR_COUNTS>(P, a, dp, tile_groups, cnt, t_kernel_s);
+        }
+        last = "no kernel for model " + std::to_string(model);
+        return FNN_EHIP;
+    }
+    // ---- site ranges: window tiles of 16 problems in place of replicate groups
+    template <int MODEL, bool MISSING, bool GAMMA>
+    int32_t launch_ranges(const DistArgs& a, const DistRanges& dr, const DistModel& dm, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+        const int64_t win_tiles = round_up(cnt, (int64_t)DIST_TILE) / DIST_TILE;
+        if (tile_groups * win_tiles >= ((int64_t)1 << 31)) { last = "too many workgroups for one launch"; return FNN_EHIP; }
+        return timed_launch(reinterpret_cast<const void*>(&k_dist_ranges<MODEL, MISSING, GAMMA>), "k_dist_ranges", 0, [&] {
+            hipLaunchKernelGGL((k_dist_ranges<MODEL, MISSING, GAMMA>), dim3((unsigned)(tile_groups * win_tiles)), dim3(DIST_THREADS), 0, stream, a, dr, dm,
+                               (uint32_t)tile_groups);
+        }, t_kernel_s);
+    }
+    template <int MODEL>
+    int32_t run_ranges_of(bool missing, const DistArgs& a, const DistRanges& dr, const DistModel& dm, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+        if constexpr (MODEL != FNN_DIST_P) {  // (the models with a gamma form)
+            if (dm.shape != 0.0)
+                return missing ? launch_ranges<MODEL, true, true>(a, dr, dm, tile_groups, cnt, t_kernel_s)
+                               : launch_ranges<MODEL, false, true>(a, dr, dm, tile_groups, cnt, t_kernel_s);
+        }
+        return missing ? launch_ranges<MODEL, true, false>(a, dr, dm, tile_groups, cnt, t_kernel_s)
+                       : launch_ranges<MODEL, false, false>(a, dr, dm, tile_groups, cnt, t_kernel_s);
+    }
+    int32_t run_ranges(int32_t model, bool missing, const DistArgs& a, const DistRanges& dr, const DistModel& dm, int64_t tile_groups, int64_t cnt,
+                       double* t_kernel_s) {
+        if (model == FNN_DIST_P) return run_ranges_of<FNN_DIST_P>(missing, a, dr, dm, tile_groups, cnt, t_kernel_s);
+        if (model == FNN_DIST_JC69) return run_ranges_of<FNN_DIST_JC69>(missing, a, dr, dm, tile_groups, cnt, t_kernel_s);
+        if (model == FNN_DIST_K2P) return run_ranges_of<FNN_DIST_K2P>(missing, a, dr, dm, tile_groups, cnt, t_kernel_s);
+        last = "no kernel for model " + std::to_string(model);
+        return FNN_EHIP;
+    }
+    template <int MODEL, bool GAMMA>
+    int32_t launch_ranges_pairs(const DistArgs& a, const DistRanges& dr, const DistPairs& dp, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+        const int64_t win_tiles = round_up(cnt, (int64_t)DIST_TILE) / DIST_TILE;
+        if (tile_groups * win_tiles >= ((int64_t)1 << 31)) { last = "too many workgroups for one launch"; return FNN_EHIP; }
+        return timed_launch(reinterpret_cast<const void*>(&k_dist_ranges_pairs<MODEL, GAMMA>), "k_dist_ranges_pairs", 0, [&] {
+            hipLaunchKernelGGL((k_dist_ranges_pairs<MODEL, GAMMA>), dim3((unsigned)(tile_groups * win_tiles)), dim3(DIST_THREADS), 0, stream, a, dr, dp,
+                               (uint32_t)tile_groups);
+        }, t_kernel_s);
+    }
+    template <int MODEL>
+    int32_t run_ranges_pairs_of(const DistArgs& a, const DistRanges& dr, const DistPairs& dp, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+        if constexpr (MODEL == FNN_DIST_F81 || MODEL == FNN_DIST_F84 || MODEL == FNN_DIST_TN93) {  // (the models with a gamma form)
+            if (dp.shape != 0.0) return launch_ranges_pairs<MODEL, true>(a, dr, dp, tile_groups, cnt, t_kernel_s);
+        }
+        return launch_ranges_pairs<MODEL, false>(a, dr, dp, tile_groups, cnt, t_kernel_s);
+    }
+    int32_t run_ranges_pairs(int32_t model, const DistArgs& a, const DistRanges& dr, const DistPairs& dp, int64_t tile_groups, int64_t cnt, double* t_kernel_s) {
+        switch (model) {
+            case FNN_DIST_F81: return run_ranges_pairs_of<FNN_DIST_F81>(a, dr, dp, tile_groups, cnt, t_kernel_s);
+            case FNN_DIST_F84: return run_ranges_pairs_of<FNN_DIST_F84>(a, dr, dp, tile_groups, cnt, t_kernel_s);
+            case FNN_DIST_TN93: return run_ranges_pairs_of<FNN_DIST_TN93>(a, dr, dp, tile_groups, cnt, t_kernel_s);
+            case FNN_DIST_LOGDET: return run_ranges_pairs_of<FNN_DIST_LOGDET>(a, dr, dp, tile_groups, cnt, t_kernel_s);
+            case DIST_PAIR_COUNTS: return run_ranges_pairs_of<DIST_PAIR_COUNTS>(a, dr, dp, tile_groups, cnt, t_kernel_s);
         }
         last = "no kernel for model " + std::to_string(model);
         return FNN_EHIP;
@@ -327,5 +439,42 @@ int32_t fnn_bootstrap_distances_batch_device_f64(const uint8_t* seq, int32_t n, 
 }
 
 int32_t fnn_bootstrap_draw_max_sites(void) { return fnn::DRAW_MAX_SITES; }
+
+int32_t fnn_alignment_distances_ranges_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts, const int64_t* ends, int64_t batch,
+                                           const fnn_dist_model* m, int32_t device, double* D_out, int64_t ld, int64_t stride, fnn_range_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch_ranges(be, "fnn_alignment_distances_ranges_f64", seq, n, L, lds, starts, ends, batch, m, false, device, D_out, false, ld, stride,
+                                      stats);
+    )
+}
+
+int32_t fnn_alignment_distances_ranges_device_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts, const int64_t* ends,
+                                                  int64_t batch, const fnn_dist_model* m, int32_t device, double* d_D_out, int64_t ld, int64_t stride,
+                                                  fnn_range_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch_ranges(be, "fnn_alignment_distances_ranges_device_f64", seq, n, L, lds, starts, ends, batch, m, false, device, d_D_out, true, ld,
+                                      stride, stats);
+    )
+}
+
+int32_t fnn_alignment_pair_counts_ranges_i64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts, const int64_t* ends, int64_t batch,
+                                             int32_t device, int64_t* F_out, int64_t ld, int64_t stride, fnn_range_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch_ranges(be, "fnn_alignment_pair_counts_ranges_i64", seq, n, L, lds, starts, ends, batch, nullptr, true, device,
+                                      reinterpret_cast<double*>(F_out), false, ld, stride, stats);
+    )
+}
+
+int32_t fnn_alignment_pair_counts_ranges_device_i64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts, const int64_t* ends,
+                                                    int64_t batch, int32_t device, int64_t* d_F_out, int64_t ld, int64_t stride, fnn_range_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch_ranges(be, "fnn_alignment_pair_counts_ranges_device_i64", seq, n, L, lds, starts, ends, batch, nullptr, true, device,
+                                      reinterpret_cast<double*>(d_F_out), true, ld, stride, stats);
+    )
+}
 
 }  // extern "C"

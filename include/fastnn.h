@@ -667,6 +667,44 @@ int32_t fnn_bootstrap_distances_batch_device_f64(const uint8_t* seq, int32_t n, 
                                                  int64_t lead, const fnn_dist_model* m, int32_t device,
                                                  double* d_D_out, int64_t ld, int64_t stride, fnn_boot_stats* stats);
 int32_t fnn_bootstrap_draw_max_sites(void);
+/* ---- site ranges: per-gene matrices and sliding windows without a counts matrix -----------------
+ * The model and the table entries above for problems that are contiguous runs of sites: problem b is the alignment restricted
+ * to the sites starts[b] <= s < ends[b] (half-open; HOST arrays of `batch` int64_t in both variants) - a gene of a
+ * concatenated alignment, one window of a scan along a genome.  Each entry writes the same bytes as its counts entry
+ * (fnn_alignment_distances_model_batch[_device]_f64, fnn_alignment_pair_counts_batch[_device]_i64) writes on
+ *     counts[b][s] = [starts[b] <= s < ends[b]]
+ * for every model, both saturation policies and gamma rates, and everything said there holds: layout, chunks and
+ * FNN_BATCH_CHUNK, host output written only on success, the device variant's in-place output and synchronised stream, K2P's
+ * recoding with n_recoded and has_missing, FNN_DIST_FORCE_MISSING, n == 1, batch == 0, 127 L < 2^31, all argument checks
+ * before any device use; a failing call fails with the same status and fnn_last_error() names the same lowest (b, i, j) and
+ * the same kind (empty, degenerate, saturated).  No counts exist anywhere: the kernel makes its 0/1 operand from the two
+ * bounds, the uploads per chunk are the bounds and one span per 16 ranges, and the kernel walks, for each TILE of 16
+ * consecutive ranges in the caller's order, only the 64-site blocks from floor64(the lowest start) to ceil64(the highest end)
+ * of the tile's non-empty ranges.  Ranges may overlap, nest, repeat and come in any order: the order changes the cost (ranges
+ * that lie close together belong next to each other), never a byte.
+ * FNN_EINVAL beyond the lists above, before any device use: a NULL starts or ends; a range outside 0 <= start <= end <= L,
+ * and fnn_last_error() names the lowest such b.  An empty range (start == end) is no argument error: it is the all-zero row
+ * of the counts and behaves as that row does - every pair of it is empty.
+ * stats: model = what the counts entry reports (digit_passes is 1); n_site_blocks = the 64-site blocks walked, summed over the
+ * call's tiles of 16 consecutive ranges (a chunk starts a new tile); n_site_blocks_dense = what the counts entries walk,
+ * ceil(batch / 16) * round_up(L, 64) / 64.  Their ratio tells what an unfortunate order of the ranges costs. */
+typedef struct fnn_range_stats {
+    fnn_dist_model_stats model;
+    int64_t n_site_blocks, n_site_blocks_dense;
+    int64_t reserved[4];
+} fnn_range_stats;
+int32_t fnn_alignment_distances_ranges_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts,
+                                           const int64_t* ends, int64_t batch, const fnn_dist_model* m, int32_t device,
+                                           double* D_out, int64_t ld, int64_t stride, fnn_range_stats* stats /* may be NULL */);
+int32_t fnn_alignment_distances_ranges_device_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts,
+                                                  const int64_t* ends, int64_t batch, const fnn_dist_model* m, int32_t device,
+                                                  double* d_D_out, int64_t ld, int64_t stride, fnn_range_stats* stats);
+int32_t fnn_alignment_pair_counts_ranges_i64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts,
+                                             const int64_t* ends, int64_t batch, int32_t device, int64_t* F_out, int64_t ld,
+                                             int64_t stride, fnn_range_stats* stats /* may be NULL */);
+int32_t fnn_alignment_pair_counts_ranges_device_i64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts,
+                                                    const int64_t* ends, int64_t batch, int32_t device, int64_t* d_F_out,
+                                                    int64_t ld, int64_t stride, fnn_range_stats* stats);
 
 /* ---- split support: how often each split occurs among many problems ---------
  * The last stage of a bootstrap run: the orderings and split weights of `batch` problems over ONE taxon set go in, one
