@@ -68,6 +68,7 @@ def api() -> _capi.Api:
         _capi.bind_pair_counts(a)  # fnn_alignment_pair_counts_batch[_device]_i64
         _capi.bind_boot(a)  # fnn_bootstrap_distances_batch[_device]_f64, fnn_bootstrap_draw_max_sites
         _capi.bind_ranges(a)  # fnn_alignment_distances_ranges[_device]_f64, fnn_alignment_pair_counts_ranges[_device]_i64
+        _capi.bind_scan(a)  # fnn_bootscan_counts, fnn_bootscan_distances[_device]_f64, fnn_bootscan_pair_counts[_device]_i64
         _capi.bind_support(a)  # fnn_split_support[_device]_f64, fnn_split_keys, fnn_split_support_max_n / _min_work
         _api = a
     return _api
@@ -77,4 +78,5 @@ from .canonical import (NeighborNetCanonical, NeighborNetLocal, canonical_order,
                         split_weights, split_weights_batch, split_weights_ragged, split_weights_sparse,
                         encode_alignment, bootstrap_counts, alignment_distances_batch, pair_counts_batch, bootstrap_distances, bootstrap,
                         split_support, split_keys, key_taxa, bootstrap_support,
-                        window_ranges, range_distances, pair_counts_ranges, range_networks, sliding_windows)
+                        window_ranges, range_distances, pair_counts_ranges, range_networks, sliding_windows,
+                        bootscan_counts, bootscan_distances, bootscan_pair_counts, bootscan_networks, bootscan)

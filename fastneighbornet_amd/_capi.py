@@ -421,6 +421,56 @@ def run_pair_counts_ranges(a: Api, seq, n: int, L: int, lds: int, starts, ends, 
     return st
 
 
+class FnnScanStats(C.Structure):
+    _fields_ = [("boot", FnnBootStats), ("n_windows", C.c_int64), ("n_site_blocks", C.c_int64), ("n_site_blocks_dense", C.c_int64),
+                ("n_host_chunks", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+    def as_dict(self):
+        return dict(self.boot.as_dict(), n_windows=self.n_windows, n_site_blocks=self.n_site_blocks, n_site_blocks_dense=self.n_site_blocks_dense,
+                    n_host_chunks=self.n_host_chunks)
+
+
+_SCAN_ARGS = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.POINTER(FnnDistModel),
+              C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(FnnScanStats)]
+
+
+def bind_scan(a: Api) -> Api:
+    """The bootscan entry points of include/fastnn.h (bootstrap replicates inside every site range) on `a`."""
+    a._fn("bootscan_counts", C.c_int32, [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p])
+    a._fn("bootscan_distances_f64", C.c_int32, _SCAN_ARGS)
+    a._fn("bootscan_distances_device_f64", C.c_int32, _SCAN_ARGS)
+    a._fn("bootscan_pair_counts_i64", C.c_int32, _SCAN_ARGS)
+    a._fn("bootscan_pair_counts_device_i64", C.c_int32, _SCAN_ARGS)
+    return a
+
+
+def run_bootscan_counts(a: Api, L: int, starts, ends, replicates: int, seed: int, lead: int = 0, first: int = 0, count=None) -> np.ndarray:
+    """Rows first ... first + count - 1 (count=None: to the last) of the counts a bootscan stands for: uint16 (count, L)."""
+    starts, ends = np.ascontiguousarray(starts, dtype=np.int64), np.ascontiguousarray(ends, dtype=np.int64)
+    if starts.ndim != 1 or starts.shape != ends.shape:
+        raise ValueError("starts and ends must be one-dimensional and of the same length")
+    if count is None:
+        count = len(starts) * (replicates + lead) - first
+    counts = np.zeros((max(count, 0), max(L, 0)), dtype=np.uint16)
+    a.check(a.bootscan_counts(L, starts.ctypes.data, ends.ctypes.data, len(starts), replicates, lead, seed & 0xFFFFFFFFFFFFFFFF, first, count,
+                              counts.ctypes.data))
+    return counts
+
+
+def run_scan(a: Api, seq, n: int, L: int, lds: int, starts, ends, windows: int, replicates: int, seed: int, lead: int, out, ld: int, stride: int,
+             m: FnnDistModel, device: int = 0, on_device: bool = False, tables: bool = False):
+    """One bootscan call on raw addresses (seq, starts, ends: host memory, the bounds int64; out: host memory, or device memory
+    with on_device; tables: the pair-count entries, out int64, 16 per (i, j)); m=None passes NULL.  Returns the stats
+    (FnnScanStats)."""
+    st = FnnScanStats()
+    if tables:
+        fn = a.bootscan_pair_counts_device_i64 if on_device else a.bootscan_pair_counts_i64
+    else:
+        fn = a.bootscan_distances_device_f64 if on_device else a.bootscan_distances_f64
+    a.check(fn(seq, n, L, lds, starts, ends, windows, replicates, seed & 0xFFFFFFFFFFFFFFFF, lead, dist_model_ref(m), device, out, ld, stride, C.byref(st)))
+    return st
+
+
 class FnnSupportStats(C.Structure):
     _fields_ = [("n_problems", C.c_int64), ("n_records", C.c_int64), ("n_splits", C.c_int64),
                 ("words", C.c_int32), ("route", C.c_int32), ("hash_retries", C.c_int32), ("chunks", C.c_int32),

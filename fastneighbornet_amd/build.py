@@ -17,7 +17,7 @@ SRC_SUPPORT = os.path.join(HERE, "csrc", "fnn_support.hip")  # split support: th
 SOURCES = (SRC, SRC_SPLITS, SRC_BATCH, SRC_SPLITS_BATCH, SRC_DIST, SRC_SUPPORT)
 DEPS = [SRC, SRC_SPLITS, SRC_BATCH, SRC_SPLITS_BATCH, SRC_DIST, SRC_SUPPORT, os.path.join(HERE, "csrc", "fnn_core.h"), os.path.join(HERE, "csrc", "fnn_engine.h"),
         os.path.join(HERE, "csrc", "fnn_chain.h"), os.path.join(HERE, "csrc", "fnn_small.h"), os.path.join(HERE, "csrc", "fnn_small_global.h"),
-        os.path.join(HERE, "csrc", "fnn_small_splits.h"), os.path.join(HERE, "csrc", "fnn_ragged_hip.h"), os.path.join(HERE, "csrc", "fnn_dist.h"), os.path.join(HERE, "csrc", "fnn_dist_model.h"), os.path.join(HERE, "csrc", "fnn_dist_pairs.h"), os.path.join(HERE, "csrc", "fnn_dist_ranges.h"), os.path.join(HERE, "csrc", "fnn_draw.h"),
+        os.path.join(HERE, "csrc", "fnn_small_splits.h"), os.path.join(HERE, "csrc", "fnn_ragged_hip.h"), os.path.join(HERE, "csrc", "fnn_dist.h"), os.path.join(HERE, "csrc", "fnn_dist_model.h"), os.path.join(HERE, "csrc", "fnn_dist_pairs.h"), os.path.join(HERE, "csrc", "fnn_dist_ranges.h"), os.path.join(HERE, "csrc", "fnn_scan.h"), os.path.join(HERE, "csrc", "fnn_draw.h"),
         os.path.join(HERE, "csrc", "fnn_support.h"), os.path.join(HERE, "csrc", "fnn_splits_plan.h"), os.path.join(ROOT, "include", "fastnn.h")]
 
 # -ffp-contract=off: one rounding per fp64 operation on host and device (parity with Java doubles)
@@ -101,7 +101,7 @@ def build_host(force: bool = False) -> None:
 OBJ_DIR = os.path.join(HERE, "csrc", "build")  # objects are kept (git-ignored): a source is recompiled only when it or a header changed
 HEADERS = [os.path.join(HERE, "csrc", "fnn_core.h"), os.path.join(HERE, "csrc", "fnn_engine.h"), os.path.join(HERE, "csrc", "fnn_chain.h"),
            os.path.join(HERE, "csrc", "fnn_small.h"), os.path.join(HERE, "csrc", "fnn_small_global.h"), os.path.join(HERE, "csrc", "fnn_small_splits.h"),
-           os.path.join(HERE, "csrc", "fnn_ragged_hip.h"), os.path.join(HERE, "csrc", "fnn_dist.h"), os.path.join(HERE, "csrc", "fnn_dist_model.h"), os.path.join(HERE, "csrc", "fnn_dist_pairs.h"), os.path.join(HERE, "csrc", "fnn_dist_ranges.h"), os.path.join(HERE, "csrc", "fnn_draw.h"), os.path.join(HERE, "csrc", "fnn_support.h"),
+           os.path.join(HERE, "csrc", "fnn_ragged_hip.h"), os.path.join(HERE, "csrc", "fnn_dist.h"), os.path.join(HERE, "csrc", "fnn_dist_model.h"), os.path.join(HERE, "csrc", "fnn_dist_pairs.h"), os.path.join(HERE, "csrc", "fnn_dist_ranges.h"), os.path.join(HERE, "csrc", "fnn_scan.h"), os.path.join(HERE, "csrc", "fnn_draw.h"), os.path.join(HERE, "csrc", "fnn_support.h"),
            os.path.join(HERE, "csrc", "fnn_splits_plan.h"), os.path.join(ROOT, "include", "fastnn.h")]
 
 

@@ -608,6 +608,97 @@ def sliding_windows(seq, width: int, step: int = 1, weights: bool = True, device
     return starts, ends, orders, W, stats
 
 
+# ---- bootscan: bootstrap replicates inside every site range
+
+def bootscan_counts(L: int, starts, ends, R: int, seed: int, lead: int = 0, first: int = 0, count=None) -> np.ndarray:
+    """The counts a bootscan stands for (`fnn_bootscan_counts`, host only): rows first ... first + count - 1 (count=None: to the
+    last) of the len(starts) * (R + lead) problems, window-major - per window `lead` rows of its 0/1 indicator, then the R rows of
+    `bootstrap_counts(width, R, seed_w)` placed at the window's columns, seed_w the w-th SplitMix64 output of `seed`.  uint16
+    (count, L)."""
+    from . import api
+    return _capi.run_bootscan_counts(api(), int(L), starts, ends, int(R), int(seed), int(lead), int(first), None if count is None else int(count))
+
+
+def _bootscan_call(seq, starts, ends, R, seed, lead, device, out, m, tables):
+    from . import api
+    a = api()
+    seq, starts, ends = _range_inputs(seq, starts, ends)
+    if lead not in (0, 1) or R < 0:
+        raise ValueError("lead must be 0 or 1 and R >= 0")
+    (n, L), W, P = seq.shape, starts.shape[0], int(R) + int(lead)
+    cell = (4, 4) if tables else ()
+
+    def run(ptr, **kw):
+        return _capi.run_scan(a, seq.ctypes.data, n, L, L, starts.ctypes.data, ends.ctypes.data, W, int(R), int(seed), int(lead), ptr, max(n, 1),
+                              max((16 if tables else 1) * n * n, 1), m, device=device, tables=tables, **kw)
+    if out == "torch":
+        import torch
+        dev = torch.device("cuda", device)
+        D = torch.empty((W, P, n, n) + cell, dtype=torch.int64 if tables else torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        st = run(D.data_ptr() if W and P and n else None, on_device=True)
+    elif out == "numpy":
+        D = np.empty((W, P, n, n) + cell, dtype=np.int64 if tables else np.float64)
+        st = run(D.ctypes.data)
+    else:
+        raise ValueError('out must be "numpy" or "torch"')
+    return D, st.as_dict()
+
+
+def bootscan_distances(seq, starts, ends, R: int, seed: int, lead: int = 1, device: int = 0, out: str = "numpy", model: str = "p", states: int = 4,
+                       on_saturation: str = "fail", cap=None, gamma_shape=None):
+    """Distance matrices of R bootstrap replicates inside every site range [starts[w], ends[w]) of the alignment `seq` (uint8
+    (n, L)) over `fnn_bootscan_distances_f64`, lead=1 (the default) with the window's original data in front of them: for
+    window w bit for bit what `bootstrap_distances(seq[:, starts[w]:ends[w]], R, seed_w, lead)` returns, seed_w the w-th
+    SplitMix64 output of `seed`, and bit for bit what `alignment_distances_batch` returns on `bootscan_counts` - in one call,
+    without those counts: a kernel draws every row of a plane that is only as long as its window, and the distance kernel
+    walks that window's sites only.  out, model, states, on_saturation, cap, gamma_shape as there.  Returns (matrices (W, R +
+    lead, n, n), stats dict); stats adds "n_windows", "n_site_blocks", "n_site_blocks_dense" and "n_host_chunks" (chunks that
+    needed a second digit and were computed from the host's counts) to what `bootstrap_distances` reports."""
+    m = _capi.dist_model(model, states, on_saturation, cap, gamma_shape)
+    return _bootscan_call(seq, starts, ends, R, seed, lead, device, out, m, False)
+
+
+def bootscan_pair_counts(seq, starts, ends, R: int, seed: int, lead: int = 1, device: int = 0, out: str = "numpy"):
+    """The 4 x 4 tables of state pairs of the same problems over `fnn_bootscan_pair_counts_i64`: what `pair_counts_batch` returns
+    on `bootscan_counts`.  Returns (tables (W, R + lead, n, n, 4, 4) int64, stats dict as `bootscan_distances` reports it)."""
+    return _bootscan_call(seq, starts, ends, R, seed, lead, device, out, None, True)
+
+
+def bootscan_networks(seq, starts, ends, R: int, seed: int, threshold: float = 1e-6, device: int = 0, model: str = "p", states: int = 4,
+                      on_saturation: str = "fail", cap=None, gamma_shape=None):
+    """A bootscan end to end: `bootscan_distances(..., lead=1)` as a tensor on the GPU, `canonical_order_batch` and
+    `split_weights_batch` of all W (R + 1) problems at once, then `split_support(..., lead=1)` of every window's R + 1 problems,
+    one call per window.  No matrix crosses to the host.  Returns (orders[W, n + 1], weights[W, n(n-1)/2], tables, stats): the
+    order and the weights of every window's original data, one support table per window - as `bootstrap_support` returns it for
+    the window's slice - and stats = {"distances", "splits", "support": one dict per window}."""
+    D, dst = bootscan_distances(seq, starts, ends, R, seed, lead=1, device=device, out="torch", model=model, states=states, on_saturation=on_saturation,
+                                cap=cap, gamma_shape=gamma_shape)
+    W, P, n = D.shape[0], D.shape[1], D.shape[2]
+    flat = D.reshape(W * P, n, n)
+    orders = canonical_order_batch(flat, device=device)
+    Wt, sst = split_weights_batch(flat, orders, device=device)
+    tables, ust = [], []
+    for w in range(W):
+        t, u = split_support(orders[w * P:(w + 1) * P], Wt[w * P:(w + 1) * P], threshold=threshold, lead=1, device=device)
+        tables.append(t)
+        ust.append(u)
+    return orders[::P].copy(), Wt[::P].copy(), tables, {"distances": dst, "splits": sst, "support": ust}
+
+
+def bootscan(seq, width: int, step: int, R: int, seed: int, threshold: float = 1e-6, device: int = 0, model: str = "p", states: int = 4,
+             on_saturation: str = "fail", cap=None, gamma_shape=None):
+    """A bootscan along the alignment `seq`: `bootscan_networks` on `window_ranges(L, width, step)`.  Returns (starts, ends,
+    orders, weights, tables, stats)."""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    if seq.ndim != 2:
+        raise ValueError("seq must have shape (n, L)")
+    starts, ends = window_ranges(seq.shape[1], width, step)
+    orders, Wt, tables, stats = bootscan_networks(seq, starts, ends, R, seed, threshold=threshold, device=device, model=model, states=states,
+                                                  on_saturation=on_saturation, cap=cap, gamma_shape=gamma_shape)
+    return starts, ends, orders, Wt, tables, stats
+
+
 # ---- split support: the distinct splits of many problems, tallied (DESIGN.md section 15)
 
 def split_support(orders, W, threshold: float = 1e-6, lead: int = 0, device: int = 0):

@@ -34,6 +34,10 @@
 // Site ranges (k_dist_ranges, k_dist_ranges_pairs): problem b is the sites [start_b, end_b), the B operand
 // is made in registers from the two bounds and the walk covers the ranges' span only; the per-lane steps are fnn_dist_ranges.h,
 // the host side is the one below.
+//
+// Bootscan (k_draw_ranges, k_dist_scan, k_dist_scan_pairs): P problems per site range, the range's original
+// data and bootstrap replicates of the range alone, drawn on the device into compact planes as long as the range's span; the
+// per-lane steps are fnn_scan.h, the host side is the one below.
 #ifndef FNN_DIST_H
 #define FNN_DIST_H
 
@@ -245,6 +249,7 @@ FNN_HD void dist_lane_store_model(const DistArgs& a, const DistModel& dm, const 
 #include "fnn_draw.h"  // the per-lane steps of k_draw: the planes of a bootstrap made where they are read
 #include "fnn_dist_pairs.h"  // the per-lane steps of k_dist_pairs: the 4 x 4 table of state pairs and its models
 #include "fnn_dist_ranges.h"  // the per-lane steps of the range kernels: the B operand from a range's bounds
+#include "fnn_scan.h"  // the per-lane steps of the bootscan kernels: compact planes of a bootstrap of every range
 namespace fnn {
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -269,6 +274,13 @@ inline int32_t dist_force_digits() {
     const char* e = std::getenv("FNN_DIST_FORCE_DIGITS");
     const int v = e ? std::atoi(e) : 0;
     return v == 2 || v == 3 ? v : 1;
+}
+// FNN_DRAW_ROUTE=device|host (tests): where a bootstrap is drawn; anything else leaves the choice to the call
+inline int32_t dist_draw_route_switch() {
+    const char* e = std::getenv("FNN_DRAW_ROUTE");
+    if (e && std::strcmp(e, "device") == 0) return FNN_DRAW_DEVICE;
+    if (e && std::strcmp(e, "host") == 0) return FNN_DRAW_HOST;
+    return -1;
 }
 inline int32_t dist_digits_of(uint32_t cmax) { return cmax <= 127 ? 1 : (cmax <= 16383 ? 2 : 3); }
 inline int32_t dist_fail_no_site(const std::string& W, int64_t b, int64_t i, int64_t j) {
@@ -344,10 +356,19 @@ struct dist_runs_ranges : std::false_type {};
 template <class B>
 struct dist_runs_ranges<B, std::void_t<decltype(&B::run_ranges), decltype(&B::run_ranges_pairs)>> : std::true_type {};
 
+// A backend that has the bootscan kernels (and the draw, the models and the tables) adds run_draw_ranges(scan args, rows, the widest
+// span, &t_draw_s): one workgroup per row; run_scan(model, missing, args, scan args, model args, tile groups, column groups,
+// &t_kernel_s) and run_scan_pairs(model or DIST_PAIR_COUNTS, args, scan args, pair args, ...): one column group per wave.
+template <class B, class = void>
+struct dist_runs_scan : std::false_type {};
+template <class B>
+struct dist_runs_scan<B, std::void_t<decltype(&B::run_draw_ranges), decltype(&B::run_scan), decltype(&B::run_scan_pairs)>> : std::true_type {};
+
 // Where the site multiplicities of a call come from: the caller's array, or a bootstrap of `seed` - problems 0 ... lead - 1
 // the original data (every site once), problem b >= lead replicate b - lead of fnn_bootstrap_counts(L, batch - lead, seed) -
 // drawn on the host into such an array or on the device straight into the planes, or `batch` site
-// ranges, whose 0/1 multiplicities exist nowhere.
+// ranges, whose 0/1 multiplicities exist nowhere, or a bootstrap of each of `windows` site ranges, per_window
+// problems each, whose compact planes are drawn on the device.
 struct DistSource {
     const uint16_t* counts = nullptr;
     int64_t ldc = 0;
@@ -360,6 +381,10 @@ struct DistSource {
     const int64_t* starts = nullptr;
     const int64_t* ends = nullptr;
     fnn_range_stats* range_stats = nullptr;  // of a call on ranges: receives n_site_blocks, n_site_blocks_dense
+    bool scan = false;                   // problem p is q = p % per_window of the window [starts[w], ends[w]), w = p / per_window; seed, lead
+    int64_t windows = 0, per_window = 0;
+    fnn_scan_stats* scan_stats = nullptr;    // of a bootscan: receives n_windows, n_site_blocks, n_site_blocks_dense, n_host_chunks
+    int64_t base = 0;                    // problem 0 of this call is problem `base` of the caller's: what a failure names
 };
 
 template <class B>
@@ -402,9 +427,10 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
         return fail(FNN_EINVAL, W + "the cap of saturated pairs must be finite and > 0");
     if (L > (((int64_t)1 << 31) - 1) / 127) return fail(FNN_EINVAL, W + "too many sites: 127 L must stay below 2^31 (the int32 digit accumulators)");
     if (batch == 0) { if (stats) *stats = bst; return FNN_OK; }
-    if (!seq || (!src.bootstrap && !src.ranges && !src.counts) || (src.ranges && (!src.starts || !src.ends)) || !D_out)
+    const bool bounds = src.ranges || src.scan;  // the call has starts and ends, and no counts
+    if (!seq || (!src.bootstrap && !bounds && !src.counts) || (bounds && (!src.starts || !src.ends)) || !D_out)
         return fail(FNN_EINVAL, W + "NULL argument");
-    if (lds < L || (!src.bootstrap && !src.ranges && src.ldc < L)) return fail(FNN_EINVAL, W + (src.ranges ? "needs lds >= L" : "needs lds >= L and ldc >= L"));
+    if (lds < L || (!src.bootstrap && !bounds && src.ldc < L)) return fail(FNN_EINVAL, W + (bounds ? "needs lds >= L" : "needs lds >= L and ldc >= L"));
     if (ld < n || stride < (int64_t)n * ld * cell) return fail(FNN_EINVAL, W + (tables ? "needs ld >= n and stride >= 16 * n * ld" : "needs ld >= n and stride >= n * ld"));
     if (src.ranges) {
         if (!dist_runs_ranges<B>::value) return fail(FNN_EINVAL, W + "this backend has no range kernels");
@@ -412,6 +438,22 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
             if (src.starts[b] < 0 || src.starts[b] > src.ends[b] || src.ends[b] > L)
                 return fail(FNN_EINVAL, W + "range " + std::to_string(b) + ": needs 0 <= start <= end <= L, got [" + std::to_string(src.starts[b]) + ", " +
                                             std::to_string(src.ends[b]) + ")");
+    }
+    int32_t scan_widest = 0;  // the widest padded span of a bootscan's windows
+    if (src.scan) {
+        if (!dist_runs_scan<B>::value) return fail(FNN_EINVAL, W + "this backend has no bootscan kernels");
+        for (int64_t w = 0; w < src.windows; w++) {
+            if (src.starts[w] < 0 || src.starts[w] > src.ends[w] || src.ends[w] > L)
+                return fail(FNN_EINVAL, W + "window " + std::to_string(w) + ": needs 0 <= start <= end <= L, got [" + std::to_string(src.starts[w]) + ", " +
+                                            std::to_string(src.ends[w]) + ")");
+            const int32_t span = scan_ceil64(src.ends[w]) - scan_floor64(src.starts[w]);
+            scan_widest = span > scan_widest ? span : scan_widest;
+        }
+        const int32_t sw = dist_draw_route_switch();
+        if (sw == FNN_DRAW_DEVICE && scan_widest > DRAW_MAX_SITES)
+            return fail(FNN_EINVAL, W + "the draw kernel takes windows of at most " + std::to_string(DRAW_MAX_SITES) + " padded sites (FNN_DRAW_ROUTE=device)");
+        src.draw_route = sw >= 0 ? sw : (scan_widest <= DRAW_MAX_SITES ? FNN_DRAW_DEVICE : FNN_DRAW_HOST);
+        bst.draw_route = src.draw_route;
     }
     if (draw && !dist_runs_draw<B>::value) return fail(FNN_EINVAL, W + "this backend has no draw kernel");
     if (draw && L > DRAW_MAX_SITES)
@@ -460,9 +502,10 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
     const uint16_t* counts = src.counts;
     const int64_t ldc = src.ldc;
     // (drawn on the device: every row's total is L > 0, and the largest count is the kernel's to report)
-    std::vector<int64_t> total(draw ? 0 : (size_t)batch, 0);
+    // (a bootscan: a row's total is its window's width, the device route has one digit and the kernel reports the largest count)
+    std::vector<int64_t> total(draw || src.scan ? 0 : (size_t)batch, 0);
     uint32_t cmax = 0;
-    for (int64_t b = 0; b < batch && !draw && !src.ranges; b++) {
+    for (int64_t b = 0; b < batch && !draw && !bounds; b++) {
         const uint16_t* c = counts + b * ldc;
         int64_t t = 0;
         for (int64_t s = 0; s < L; s++) { t += c[s]; cmax = c[s] > cmax ? c[s] : cmax; }
@@ -474,25 +517,114 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
         if (total[(size_t)b] > 0) cmax = 1;
     }
     int32_t P = dist_digits_of(cmax);
-    if (dist_force_digits() > P && !src.ranges) P = dist_force_digits();
+    if (dist_force_digits() > P && !bounds) P = dist_force_digits();
     // valid is the total: an empty replicate has valid == 0 for every pair, (0, 1) the lowest (with missing bytes the
     // kernel flags it, so that a lower replicate with one empty pair is named first; so it does when a saturated pair fails
     // the call, for the same reason)
     const bool sat_fails = model != FNN_DIST_P && !cap && !tables;
     if (n >= 2 && !missing && !sat_fails && !tables)
-        for (int64_t b = 0; b < batch && !draw; b++)
-            if (total[(size_t)b] == 0) return dist_fail_no_site(W, b, 0, 1);
+        for (int64_t b = 0; b < batch && !draw && !src.scan; b++)
+            if (total[(size_t)b] == 0) return dist_fail_no_site(W, src.base + b, 0, 1);
+    if (src.scan && n >= 2 && !missing && !sat_fails && !tables)  // (an empty window is P empty rows: its first problem is the lowest)
+        for (int64_t w = 0; w < src.windows; w++)
+            if (src.starts[w] == src.ends[w]) return dist_fail_no_site(W, src.base + w * src.per_window, 0, 1);
+    const int64_t lpad = round_up(L, (int64_t)DIST_K), nn = (int64_t)n * n;
+    int64_t site_blocks = 0, host_chunks = 0;
+    // what ends every successful call: the host variant's output, the stats
+    auto finish = [&](const std::vector<double>& staged) {
+        if (!on_device)
+            for (int64_t b = 0; b < batch; b++)
+                for (int32_t r = 0; r < n; r++)
+                    std::memcpy(D_out + b * stride + (int64_t)r * ld * cell, &staged[(size_t)b * (size_t)(nn * cell) + (size_t)r * (size_t)(n * cell)],
+                                sizeof(double) * (size_t)(n * cell));
+        st.digit_passes = P;
+        bst.max_count = (int32_t)cmax;
+        const int64_t dense = (batch + DIST_TILE - 1) / DIST_TILE * (lpad / DIST_K);
+        if (src.range_stats) {
+            src.range_stats->n_site_blocks = site_blocks;
+            src.range_stats->n_site_blocks_dense = dense;
+        }
+        if (src.scan_stats) {
+            src.scan_stats->n_windows = src.windows;
+            src.scan_stats->n_site_blocks = site_blocks;
+            src.scan_stats->n_site_blocks_dense = dense;
+            src.scan_stats->n_host_chunks = host_chunks;
+        }
+        st.t_total_s = now_s() - t0;
+        if (stats) *stats = bst;
+        return FNN_OK;
+    };
+    // A bootscan's host route is the definition itself: slices of fnn_bootscan_counts through the counts source above, on a backend
+    // of their own, at most SCAN_COUNTS_BYTES of counts at a time.  It serves a whole call (a window wider than the draw kernel
+    // takes, FNN_DRAW_ROUTE=host) or single chunks of the device route (a chunk that needs more than one digit).  Such rows walk
+    // the whole alignment: they count as dense in n_site_blocks.
+    auto scan_host_rows = [&](int64_t first, int64_t count, double* dst, bool dst_on_device, int64_t dld, int64_t dstride) -> int32_t {
+        const int64_t most = SCAN_COUNTS_BYTES / (2 * L) > 1 ? SCAN_COUNTS_BYTES / (2 * L) : 1;
+        std::vector<uint16_t> rows;
+        for (int64_t f = first; f < first + count; f += most) {
+            const int64_t c = first + count - f < most ? first + count - f : most;
+            rows.resize((size_t)c * (size_t)L);
+            int32_t r = dist_bootscan_counts(who, L, src.starts, src.ends, src.windows, src.per_window - src.lead, src.lead, src.seed, f, c, rows.data());
+            if (r != FNN_OK) return r;
+            DistSource cs;
+            cs.counts = rows.data();
+            cs.ldc = L;
+            cs.pair_counts = src.pair_counts;
+            cs.base = src.base + f;
+            fnn_boot_stats sub{};
+            B side;
+            r = dist_batch_source(side, who, seq, n, L, lds, cs, c, mp, device, dst + (f - first) * dstride, dst_on_device, dld, dstride, &sub);
+            if (r != FNN_OK) return r;
+            st.t_upload_s += sub.model.base.t_upload_s;
+            st.t_kernel_s += sub.model.base.t_kernel_s;
+            mst.n_saturated_problems += sub.model.n_saturated_problems;
+            cmax = (uint32_t)sub.max_count > cmax ? (uint32_t)sub.max_count : cmax;
+            P = sub.model.base.digit_passes > P ? sub.model.base.digit_passes : P;
+            site_blocks += (c + DIST_TILE - 1) / DIST_TILE * (lpad / DIST_K);
+        }
+        return FNN_OK;
+    };
+    if (src.scan && src.draw_route == FNN_DRAW_HOST) {
+        std::vector<double> staged(on_device ? 0 : (size_t)(nn * cell) * (size_t)batch);
+        const int64_t chunk = batch_chunk(batch, 8 * nn * cell + 2 * L, false);
+        for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+            const int64_t cnt = batch - b0 < chunk ? batch - b0 : chunk;
+            st.chunks++;
+            const int32_t rh = on_device ? scan_host_rows(b0, cnt, D_out + b0 * stride, true, ld, stride)
+                                         : scan_host_rows(b0, cnt, &staged[(size_t)b0 * (size_t)(nn * cell)], false, n, nn * cell);
+            if (rh != FNN_OK) return rh;
+        }
+        return finish(staged);
+    }
 
     int32_t rc = be.open(device);
     if (rc != FNN_OK) return fail(rc, W + be.err());
     const double tu0 = now_s();
-    const int64_t lpad = round_up(L, (int64_t)DIST_K), nn = (int64_t)n * n;
     const std::vector<DistTile> tiles = dist_tiles(n);
-    const int64_t chunk = batch_chunk(batch, 8 * nn * cell + (src.ranges ? 0 : (int64_t)P * lpad), false), cpad = round_up(chunk, (int64_t)DIST_REPS);
-    const size_t seq_bytes = (size_t)(n + DIST_PAD_ROWS) * (size_t)lpad, plane_bytes = (size_t)cpad * (size_t)lpad;
+    const int64_t chunk = batch_chunk(batch, 8 * nn * cell + (src.ranges ? 0 : src.scan ? (int64_t)scan_widest : (int64_t)P * lpad), false),
+                  cpad = round_up(chunk, (int64_t)DIST_REPS);
+    const size_t seq_bytes = (size_t)(n + DIST_PAD_ROWS) * (size_t)lpad;
+    // a bootscan's planes are compact: the bytes of the chunk that needs most; its draw reports one largest count per chunk
+    const int32_t scan_group = DIST_TILE * scan_rt(pairs);
+    const int64_t n_chunks = (batch + chunk - 1) / chunk;
+    std::vector<ScanWindow> s_wins;
+    std::vector<ScanGroup> s_groups;
+    size_t scan_bytes = 0, scan_wins = 0, scan_groups = 0;
+    for (int64_t b0 = 0; b0 < batch && src.scan; b0 += chunk) {
+        int32_t span = 0;
+        int64_t blocks = 0;
+        const size_t bytes = (size_t)scan_chunk(src.starts, src.ends, src.per_window, src.seed, b0, batch - b0 < chunk ? batch - b0 : chunk, scan_group, s_wins,
+                                                s_groups, &span, &blocks);
+        scan_bytes = bytes > scan_bytes ? bytes : scan_bytes;
+        scan_wins = s_wins.size() > scan_wins ? s_wins.size() : scan_wins;
+        scan_groups = s_groups.size() > scan_groups ? s_groups.size() : scan_groups;
+    }
+    const size_t plane_bytes = src.scan ? scan_bytes : (size_t)cpad * (size_t)lpad;
     uint8_t* d_seq = (uint8_t*)be.alloc(seq_bytes);
     DistTile* d_tiles = (DistTile*)be.alloc(sizeof(DistTile) * tiles.size());
     int8_t* d_planes = src.ranges ? nullptr : (int8_t*)be.alloc(plane_bytes * (size_t)P);
+    ScanWindow* d_wins = src.scan ? (ScanWindow*)be.alloc(sizeof(ScanWindow) * scan_wins) : nullptr;
+    ScanGroup* d_groups = src.scan ? (ScanGroup*)be.alloc(sizeof(ScanGroup) * scan_groups) : nullptr;
     int64_t* d_starts = src.ranges ? (int64_t*)be.alloc(sizeof(int64_t) * (size_t)cpad) : nullptr;
     int64_t* d_ends = src.ranges ? (int64_t*)be.alloc(sizeof(int64_t) * (size_t)cpad) : nullptr;
     DistSpan* d_spans = src.ranges ? (DistSpan*)be.alloc(sizeof(DistSpan) * (size_t)(cpad / DIST_TILE)) : nullptr;
@@ -500,9 +632,9 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
     int32_t* d_bad = (int32_t*)be.alloc(sizeof(int32_t) * (size_t)cpad);
     int32_t* d_sat = model != FNN_DIST_P ? (int32_t*)be.alloc(sizeof(int32_t) * (size_t)cpad) : nullptr;
     double* d_out = on_device ? nullptr : (double*)be.alloc(sizeof(double) * (size_t)(nn * cell) * (size_t)chunk);
-    uint32_t* d_max = draw ? (uint32_t*)be.alloc(sizeof(uint32_t)) : nullptr;
+    uint32_t* d_max = draw ? (uint32_t*)be.alloc(sizeof(uint32_t)) : src.scan ? (uint32_t*)be.alloc(sizeof(uint32_t) * (size_t)n_chunks) : nullptr;
     if (!d_seq || !d_tiles || (!src.ranges && !d_planes) || (src.ranges && (!d_starts || !d_ends || !d_spans)) || !d_total || !d_bad ||
-        (model != FNN_DIST_P && !d_sat) || (!on_device && !d_out) || (draw && !d_max))
+        (model != FNN_DIST_P && !d_sat) || (!on_device && !d_out) || ((draw || src.scan) && !d_max) || (src.scan && (!d_wins || !d_groups)))
         return fail(FNN_ENOMEM, W + "device allocation failed");
     {
         std::vector<uint8_t> img(seq_bytes, (uint8_t)FNN_SITE_MISSING);
@@ -513,23 +645,58 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
                 for (int64_t s = 0; s < L; s++) row[s] = lut[row[s]];
         }
         const uint32_t zero = 0;
+        const std::vector<uint32_t> zeros(src.scan ? (size_t)n_chunks : 0, 0u);
         if (be.h2d(d_seq, img.data(), seq_bytes) != FNN_OK || be.h2d(d_tiles, tiles.data(), sizeof(DistTile) * tiles.size()) != FNN_OK ||
-            (draw && be.h2d(d_max, &zero, sizeof(zero)) != FNN_OK))
+            (draw && be.h2d(d_max, &zero, sizeof(zero)) != FNN_OK) || (src.scan && be.h2d(d_max, zeros.data(), sizeof(uint32_t) * zeros.size()) != FNN_OK))
             return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
     }
     st.t_upload_s += now_s() - tu0;
-    std::vector<int8_t> planes(draw || src.ranges ? 0 : plane_bytes * (size_t)P);
+    std::vector<int8_t> planes(draw || bounds ? 0 : plane_bytes * (size_t)P);
     std::vector<int64_t> r_starts, r_ends;
     std::vector<DistSpan> r_spans;
-    int64_t site_blocks = 0;
     std::vector<int64_t> tot(draw ? 0 : (size_t)cpad);
     std::vector<int32_t> bad((size_t)cpad), sat(model != FNN_DIST_P ? (size_t)cpad : 0);
     std::vector<double> stage(on_device ? 0 : (size_t)(nn * cell) * (size_t)batch), one;
     for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
         const int64_t cnt = batch - b0 < chunk ? batch - b0 : chunk;
         st.chunks++;
+        ScanArgs sa{};
         // the planes of this chunk, the rows' totals and their zeroed flags
-        if (draw) {
+        if (src.scan) {
+            if constexpr (dist_runs_scan<B>::value) {
+                // The tables of the chunk's windows and column groups are the uploads; the kernel writes one compact plane and
+                // reports the chunk's largest count in a word of its own.  A chunk that needs a second digit (no honest bootstrap
+                // has one: a digit holds 127) is the host route's, and so is every chunk under FNN_DIST_FORCE_DIGITS.
+                bool host_chunk = dist_force_digits() > 1;
+                if (!host_chunk) {
+                    const double tu = now_s();
+                    int32_t span = 0;
+                    int64_t blocks = 0;
+                    scan_chunk(src.starts, src.ends, src.per_window, src.seed, b0, cnt, scan_group, s_wins, s_groups, &span, &blocks);
+                    if (be.h2d(d_wins, s_wins.data(), sizeof(ScanWindow) * s_wins.size()) != FNN_OK ||
+                        be.h2d(d_groups, s_groups.data(), sizeof(ScanGroup) * s_groups.size()) != FNN_OK)
+                        return fail(FNN_EHIP, W + "upload failed (" + be.err() + ")");
+                    st.t_upload_s += now_s() - tu;
+                    sa.planes = d_planes; sa.windows = d_wins; sa.groups = d_groups; sa.first = b0; sa.per_window = src.per_window; sa.lead = src.lead;
+                    sa.cnt = cnt; sa.total = d_total; sa.bad = d_bad; sa.sat = d_sat; sa.max_count = d_max + b0 / chunk;
+                    double td = 0.0;
+                    uint32_t most = 0;
+                    if (be.run_draw_ranges(sa, cnt, span, &td) != FNN_OK) return fail(FNN_EHIP, W + "kernel failed (" + be.err() + ")");
+                    bst.t_draw_s += td;
+                    if (be.d2h(&most, sa.max_count, sizeof(most)) != FNN_OK) return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
+                    cmax = most > cmax ? most : cmax;
+                    host_chunk = dist_digits_of(most) > 1;
+                    if (!host_chunk) site_blocks += blocks;
+                }
+                if (host_chunk) {
+                    host_chunks++;
+                    const int32_t rh = on_device ? scan_host_rows(b0, cnt, D_out + b0 * stride, true, ld, stride)
+                                                 : scan_host_rows(b0, cnt, &stage[(size_t)b0 * (size_t)(nn * cell)], false, n, nn * cell);
+                    if (rh != FNN_OK) return rh;
+                    continue;
+                }
+            }
+        } else if (draw) {
             if constexpr (dist_runs_draw<B>::value) {
                 // The kernel writes P planes and reports the largest count of the call so far in one word, the only one of the
                 // counts that crosses the bus.  A count that needs more planes than were written (no honest bootstrap has
@@ -588,6 +755,26 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
         double tk = 0.0;
         int32_t rk = FNN_OK;
         bool ran = false;
+        if constexpr (dist_runs_scan<B>::value) {
+            if (src.scan) {  // (the model and pair arguments as below)
+                if (pairs) {
+                    DistPairs dp{};
+                    dp.sat_value = cap ? mp->cap : __builtin_huge_val();
+                    dp.deg_value = cap ? mp->cap : -__builtin_huge_val();
+                    dp.sat = d_sat;
+                    dp.shape = shape;
+                    rk = be.run_scan_pairs(model, a, sa, dp, (int64_t)(tiles.size() / DIST_WAVES), (int64_t)s_groups.size(), &tk);
+                } else {
+                    DistModel dm{};
+                    dm.states = mp->states;
+                    dm.sat_value = cap ? mp->cap : __builtin_huge_val();
+                    dm.sat = d_sat;
+                    dm.shape = shape;
+                    rk = be.run_scan(model, missing, a, sa, dm, (int64_t)(tiles.size() / DIST_WAVES), (int64_t)s_groups.size(), &tk);
+                }
+                ran = true;
+            }
+        }
         if constexpr (dist_runs_ranges<B>::value) {
             if (src.ranges) {  // (the model and pair arguments as below)
                 DistRanges dr{};
@@ -648,29 +835,16 @@ int32_t dist_batch_source(B& be, const char* who, const uint8_t* seq, int32_t n,
             for (int32_t i = 0; i < n; i++)
                 for (int32_t j = i + 1; j < n; j++) {
                     const double x = one[(size_t)dist_store_index(i, j, a.ld)];
-                    if (x != x) return dist_fail_no_site(W, b0 + b, i, j);
-                    if (sat_fails && x == __builtin_huge_val()) return dist_fail_saturated(W, b0 + b, i, j);
-                    if (sat_fails && x == -__builtin_huge_val()) return dist_fail_degenerate(W, b0 + b, i, j);
+                    if (x != x) return dist_fail_no_site(W, src.base + b0 + b, i, j);
+                    if (sat_fails && x == __builtin_huge_val()) return dist_fail_saturated(W, src.base + b0 + b, i, j);
+                    if (sat_fails && x == -__builtin_huge_val()) return dist_fail_degenerate(W, src.base + b0 + b, i, j);
                 }
-            return fail(FNN_EHIP, W + "replicate " + std::to_string(b0 + b) + ": flagged without an empty pair");
+            return fail(FNN_EHIP, W + "replicate " + std::to_string(src.base + b0 + b) + ": flagged without an empty pair");
         }
         if (!on_device && be.d2h(&stage[(size_t)b0 * (size_t)(nn * cell)], d_out, sizeof(double) * (size_t)(nn * cell) * (size_t)cnt) != FNN_OK)
             return fail(FNN_EHIP, W + "download failed (" + be.err() + ")");
     }
-    if (!on_device)
-        for (int64_t b = 0; b < batch; b++)
-            for (int32_t r = 0; r < n; r++)
-                std::memcpy(D_out + b * stride + (int64_t)r * ld * cell, &stage[(size_t)b * (size_t)(nn * cell) + (size_t)r * (size_t)(n * cell)],
-                            sizeof(double) * (size_t)(n * cell));
-    st.digit_passes = P;
-    bst.max_count = (int32_t)cmax;
-    if (src.range_stats) {
-        src.range_stats->n_site_blocks = site_blocks;
-        src.range_stats->n_site_blocks_dense = (batch + DIST_TILE - 1) / DIST_TILE * (lpad / DIST_K);
-    }
-    st.t_total_s = now_s() - t0;
-    if (stats) *stats = bst;
-    return FNN_OK;
+    return finish(stage);
 }
 
 // the counts entries: the caller's array
@@ -687,13 +861,6 @@ int32_t dist_batch_model(B& be, const char* who, const uint8_t* seq, int32_t n, 
     return rc;
 }
 
-// FNN_DRAW_ROUTE=device|host (tests): where a bootstrap is drawn; anything else leaves the choice to the call
-inline int32_t dist_draw_route_switch() {
-    const char* e = std::getenv("FNN_DRAW_ROUTE");
-    if (e && std::strcmp(e, "device") == 0) return FNN_DRAW_DEVICE;
-    if (e && std::strcmp(e, "host") == 0) return FNN_DRAW_HOST;
-    return -1;
-}
 // fnn_bootstrap_distances_batch[_device]_f64: up to DRAW_MAX_SITES sites the replicates are drawn on the device, above that
 // on the host; the bytes are the same
 template <class B>
@@ -721,6 +888,35 @@ int32_t dist_batch_pair_counts(B& be, const char* who, const uint8_t* seq, int32
     fnn_boot_stats bst{};
     const int32_t rc = dist_batch_source(be, who, seq, n, L, lds, src, batch, &pm, device, reinterpret_cast<double*>(F_out), on_device, ld, stride, &bst);
     if (rc == FNN_OK && stats) *stats = bst.model;
+    return rc;
+}
+
+// fnn_bootscan_distances[_device]_f64 and, with m == nullptr and tables, fnn_bootscan_pair_counts[_device]_i64: on the device while
+// every window's padded span fits the draw kernel, else through fnn_bootscan_counts on the host; the bytes are the same
+template <class B>
+int32_t dist_batch_scan(B& be, const char* who, const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts, const int64_t* ends,
+                        int64_t windows, int64_t replicates, uint64_t seed, int64_t lead, const fnn_dist_model* mp, bool tables, int32_t device, double* D_out,
+                        bool on_device, int64_t ld, int64_t stride, fnn_scan_stats* stats) {
+    const std::string W = std::string(who) + ": ";
+    if (windows < 0 || replicates < 0) return fail(FNN_EINVAL, W + "needs windows >= 0 and replicates >= 0");
+    if (lead < 0 || lead > 1) return fail(FNN_EINVAL, W + "needs 0 <= lead <= 1");
+    const int64_t P = replicates + lead;
+    if (P > 0 && windows > (((int64_t)1 << 62) / P)) return fail(FNN_EINVAL, W + "too many problems");
+    fnn_scan_stats sst{};
+    DistSource src;
+    src.scan = true;
+    src.starts = starts;
+    src.ends = ends;
+    src.windows = windows;
+    src.per_window = P;
+    src.seed = seed;
+    src.lead = lead;
+    src.pair_counts = tables;
+    src.scan_stats = &sst;
+    fnn_dist_model pm{};
+    const int32_t rc = dist_batch_source(be, who, seq, n, L, lds, src, windows * P, tables ? &pm : mp, device, D_out, on_device, ld, stride, &sst.boot);
+    sst.n_windows = windows;
+    if (rc == FNN_OK && stats) *stats = sst;
     return rc;
 }
 

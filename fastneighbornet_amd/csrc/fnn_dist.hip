@@ -10,6 +10,10 @@
 //
 // k_dist_ranges, k_dist_ranges_pairs (fnn_dist_ranges.h): the same pair tiles against problems that are site
 // ranges.  The B operand is made in registers from a range's two bounds and the walk covers the span of the wave's window tile.
+//
+// k_draw_ranges, k_dist_scan, k_dist_scan_pairs (fnn_scan.h): bootstrap replicates of every site range.  The
+// draw writes one compact plane row per problem, as long as its window's span; a wave walks one window's span against one group of
+// that window's rows.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -201,6 +205,105 @@ __global__ __launch_bounds__(DRAW_THREADS) void k_draw(const DrawArgs a) {
     if ((tid & 63) == 0 && most > 0) atomicMax(a.max_count, most);
 }
 
+// k_draw_ranges: one workgroup makes one compact row of a bootscan's plane (the steps are fnn_scan.h): k_draw
+// over the span [lo, hi) of the row's window.  Dynamic LDS: the histogram of the chunk's widest span, 2 bytes per site
+// <= DRAW_LDS_BYTES.  grid: the chunk's rows, all of them problems.
+__global__ __launch_bounds__(DRAW_THREADS) void k_draw_ranges(const ScanArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t scan_hist[];
+    const int tid = (int)threadIdx.x;
+    const int64_t row = (int64_t)blockIdx.x;
+    const ScanWindow w = scan_row_window(a, row);
+    draw_lane_zero(scan_hist, w.hi - w.lo, tid, DRAW_THREADS);
+    __syncthreads();
+    scan_lane_count(a, w, scan_hist, row, tid, DRAW_THREADS);
+    __syncthreads();
+    uint32_t most = scan_lane_plane(a, w, scan_hist, row, tid, DRAW_THREADS);
+    scan_lane_row_words(a, w, row, tid);
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)most, off);
+        most = o > most ? o : most;
+    }
+    if ((tid & 63) == 0 && most > 0) atomicMax(a.max_count, most);
+}
+
+// k_dist_scan<MODEL, MISSING, GAMMA>: k_dist (MODEL = FNN_DIST_P) and k_dist_model for a bootscan (the steps
+// are fnn_scan.h).  A wave takes one pair tile and one column group - up to DIST_RT tiles of 16 rows of ONE window (the grid's slow
+// index is the group) - and walks that window's span, wave-uniform; per 64 sites a lane makes the A operands as the kernels above
+// do and loads 16 bytes of its column's compact row at s - lo for each tile the group has.  One digit; the epilogues are the ones
+// above with P = 1, bounded by the group's last row.
+template <int MODEL, bool MISSING, bool GAMMA>
+__global__ __launch_bounds__(DIST_THREADS) void k_dist_scan(const DistArgs a, const ScanArgs sa, const DistModel dm_in, const uint32_t tile_groups) {
+    constexpr bool K2P = MODEL == FNN_DIST_K2P;
+    DistModel dm = dm_in;
+    if (!GAMMA) dm.shape = 0.0;
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    const uint32_t cg = blockIdx.x / tile_groups, tg = blockIdx.x - cg * tile_groups;
+    const DistTile t = a.tiles[(size_t)tg * DIST_WAVES + (size_t)wave];
+    const ScanGroup g = sa.groups[cg];
+    const int8_t* rows[DIST_RT];
+    DistAcc am[DIST_RT][1], av[DIST_RT][1], at[DIST_RT][1];
+#pragma unroll
+    for (int rt = 0; rt < DIST_RT; rt++) {
+        rows[rt] = scan_lane_row(sa, g, rt, lane);
+        am[rt][0] = DistAcc{{0, 0, 0, 0}};
+        av[rt][0] = DistAcc{{0, 0, 0, 0}};
+        at[rt][0] = DistAcc{{0, 0, 0, 0}};
+    }
+    for (int32_t s = g.lo; s < g.hi; s += DIST_K) {
+        DistFrag fm, fv, ft;
+        if (K2P) dist_lane_a_ts<MISSING>(a, t, lane, s, fm, fv, ft);
+        else dist_lane_a<MISSING>(a, t, lane, s, fm, fv);
+#pragma unroll
+        for (int rt = 0; rt < DIST_RT; rt++) {
+            if (DIST_TILE * rt >= g.rows) continue;  // (uniform over the wave)
+            const DistFrag fb = scan_lane_b(rows[rt], g, s);
+            am[rt][0] = dist_mma(fm, fb, am[rt][0]);
+            if (MISSING) av[rt][0] = dist_mma(fv, fb, av[rt][0]);
+            if (K2P) at[rt][0] = dist_mma(ft, fb, at[rt][0]);
+        }
+    }
+    const DistArgs al = scan_group_args(a, g);
+#pragma unroll
+    for (int rt = 0; rt < DIST_RT; rt++) {
+        if constexpr (MODEL == FNN_DIST_P) dist_lane_store<1, MISSING>(al, t, (int64_t)g.row0 + DIST_TILE * rt, lane, am[rt], av[rt]);
+        else dist_lane_store_model<MODEL, 1, MISSING>(al, dm, t, (int64_t)g.row0 + DIST_TILE * rt, lane, am[rt], av[rt], at[rt]);
+    }
+}
+
+// k_dist_scan_pairs<MODEL, GAMMA>: k_dist_pairs for a bootscan, in the same way; a column group is dist_pairs_rt(1) tiles.
+template <int MODEL, bool GAMMA>
+__global__ __launch_bounds__(DIST_THREADS) void k_dist_scan_pairs(const DistArgs a, const ScanArgs sa, const DistPairs dp_in, const uint32_t tile_groups) {
+    constexpr int RT = dist_pairs_rt(1);
+    DistPairs dp = dp_in;
+    if (!GAMMA) dp.shape = 0.0;
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    const uint32_t cg = blockIdx.x / tile_groups, tg = blockIdx.x - cg * tile_groups;
+    const DistTile t = a.tiles[(size_t)tg * DIST_WAVES + (size_t)wave];
+    const ScanGroup g = sa.groups[cg];
+    const int8_t* rows[RT];
+    DistAcc acc[RT][DIST_PAIR_CELLS][1];
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++) {
+        rows[rt] = scan_lane_row(sa, g, rt, lane);
+#pragma unroll
+        for (int c = 0; c < DIST_PAIR_CELLS; c++) acc[rt][c][0] = DistAcc{{0, 0, 0, 0}};
+    }
+    for (int32_t s = g.lo; s < g.hi; s += DIST_K) {
+        DistFrag f[DIST_PAIR_CELLS];
+        dist_lane_a_pairs(a, t, lane, s, f);
+#pragma unroll
+        for (int rt = 0; rt < RT; rt++) {
+            if (DIST_TILE * rt >= g.rows) continue;  // (uniform over the wave)
+            const DistFrag fb = scan_lane_b(rows[rt], g, s);
+#pragma unroll
+            for (int c = 0; c < DIST_PAIR_CELLS; c++) acc[rt][c][0] = dist_mma(f[c], fb, acc[rt][c][0]);
+        }
+    }
+    const DistArgs al = scan_group_args(a, g);
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++) dist_lane_store_pairs<MODEL, 1>(al, dp, t, (int64_t)g.row0 + DIST_TILE * rt, lane, acc[rt]);
+}
+
 struct DistHipBackend : HipBatchBase {
     int32_t run_draw(const DrawArgs& a, int64_t rows, double* t_draw_s) {
         const int32_t lds_bytes = draw_lds_bytes(a.lpad);
@@ -332,6 +435,66 @@ struct DistHipBackend : HipBatchBase {
             case FNN_DIST_TN93: return run_ranges_pairs_of<FNN_DIST_TN93>(a, dr, dp, tile_groups, cnt, t_kernel_s);
             case FNN_DIST_LOGDET: return run_ranges_pairs_of<FNN_DIST_LOGDET>(a, dr, dp, tile_groups, cnt, t_kernel_s);
             case DIST_PAIR_COUNTS: return run_ranges_pairs_of<DIST_PAIR_COUNTS>(a, dr, dp, tile_groups, cnt, t_kernel_s);
+        }
+        last = "no kernel for model " + std::to_string(model);
+        return FNN_EHIP;
+    }
+    // ---- bootscan: column groups of one window's rows in place of replicate groups
+    int32_t run_draw_ranges(const ScanArgs& a, int64_t rows, int32_t span, double* t_draw_s) {
+        const int32_t lds_bytes = draw_lds_bytes(span);
+        if (lds_bytes > DRAW_LDS_BYTES || rows >= ((int64_t)1 << 31)) { last = "too many sites or rows for the draw kernel"; return FNN_EHIP; }
+        return timed_launch(reinterpret_cast<const void*>(&k_draw_ranges), "k_draw_ranges", lds_bytes, [&] {
+            hipLaunchKernelGGL(k_draw_ranges, dim3((unsigned)rows), dim3(DRAW_THREADS), (size_t)lds_bytes, stream, a);
+        }, t_draw_s);
+    }
+    template <int MODEL, bool MISSING, bool GAMMA>
+    int32_t launch_scan(const DistArgs& a, const ScanArgs& sa, const DistModel& dm, int64_t tile_groups, int64_t groups, double* t_kernel_s) {
+        if (tile_groups * groups >= ((int64_t)1 << 31)) { last = "too many workgroups for one launch"; return FNN_EHIP; }
+        return timed_launch(reinterpret_cast<const void*>(&k_dist_scan<MODEL, MISSING, GAMMA>), "k_dist_scan", 0, [&] {
+            hipLaunchKernelGGL((k_dist_scan<MODEL, MISSING, GAMMA>), dim3((unsigned)(tile_groups * groups)), dim3(DIST_THREADS), 0, stream, a, sa, dm,
+                               (uint32_t)tile_groups);
+        }, t_kernel_s);
+    }
+    template <int MODEL>
+    int32_t run_scan_of(bool missing, const DistArgs& a, const ScanArgs& sa, const DistModel& dm, int64_t tile_groups, int64_t groups, double* t_kernel_s) {
+        if constexpr (MODEL != FNN_DIST_P) {  // (the models with a gamma form)
+            if (dm.shape != 0.0)
+                return missing ? launch_scan<MODEL, true, true>(a, sa, dm, tile_groups, groups, t_kernel_s)
+                               : launch_scan<MODEL, false, true>(a, sa, dm, tile_groups, groups, t_kernel_s);
+        }
+        return missing ? launch_scan<MODEL, true, false>(a, sa, dm, tile_groups, groups, t_kernel_s)
+                       : launch_scan<MODEL, false, false>(a, sa, dm, tile_groups, groups, t_kernel_s);
+    }
+    int32_t run_scan(int32_t model, bool missing, const DistArgs& a, const ScanArgs& sa, const DistModel& dm, int64_t tile_groups, int64_t groups,
+                     double* t_kernel_s) {
+        if (model == FNN_DIST_P) return run_scan_of<FNN_DIST_P>(missing, a, sa, dm, tile_groups, groups, t_kernel_s);
+        if (model == FNN_DIST_JC69) return run_scan_of<FNN_DIST_JC69>(missing, a, sa, dm, tile_groups, groups, t_kernel_s);
+        if (model == FNN_DIST_K2P) return run_scan_of<FNN_DIST_K2P>(missing, a, sa, dm, tile_groups, groups, t_kernel_s);
+        last = "no kernel for model " + std::to_string(model);
+        return FNN_EHIP;
+    }
+    template <int MODEL, bool GAMMA>
+    int32_t launch_scan_pairs(const DistArgs& a, const ScanArgs& sa, const DistPairs& dp, int64_t tile_groups, int64_t groups, double* t_kernel_s) {
+        if (tile_groups * groups >= ((int64_t)1 << 31)) { last = "too many workgroups for one launch"; return FNN_EHIP; }
+        return timed_launch(reinterpret_cast<const void*>(&k_dist_scan_pairs<MODEL, GAMMA>), "k_dist_scan_pairs", 0, [&] {
+            hipLaunchKernelGGL((k_dist_scan_pairs<MODEL, GAMMA>), dim3((unsigned)(tile_groups * groups)), dim3(DIST_THREADS), 0, stream, a, sa, dp,
+                               (uint32_t)tile_groups);
+        }, t_kernel_s);
+    }
+    template <int MODEL>
+    int32_t run_scan_pairs_of(const DistArgs& a, const ScanArgs& sa, const DistPairs& dp, int64_t tile_groups, int64_t groups, double* t_kernel_s) {
+        if constexpr (MODEL == FNN_DIST_F81 || MODEL == FNN_DIST_F84 || MODEL == FNN_DIST_TN93) {  // (the models with a gamma form)
+            if (dp.shape != 0.0) return launch_scan_pairs<MODEL, true>(a, sa, dp, tile_groups, groups, t_kernel_s);
+        }
+        return launch_scan_pairs<MODEL, false>(a, sa, dp, tile_groups, groups, t_kernel_s);
+    }
+    int32_t run_scan_pairs(int32_t model, const DistArgs& a, const ScanArgs& sa, const DistPairs& dp, int64_t tile_groups, int64_t groups, double* t_kernel_s) {
+        switch (model) {
+            case FNN_DIST_F81: return run_scan_pairs_of<FNN_DIST_F81>(a, sa, dp, tile_groups, groups, t_kernel_s);
+            case FNN_DIST_F84: return run_scan_pairs_of<FNN_DIST_F84>(a, sa, dp, tile_groups, groups, t_kernel_s);
+            case FNN_DIST_TN93: return run_scan_pairs_of<FNN_DIST_TN93>(a, sa, dp, tile_groups, groups, t_kernel_s);
+            case FNN_DIST_LOGDET: return run_scan_pairs_of<FNN_DIST_LOGDET>(a, sa, dp, tile_groups, groups, t_kernel_s);
+            case DIST_PAIR_COUNTS: return run_scan_pairs_of<DIST_PAIR_COUNTS>(a, sa, dp, tile_groups, groups, t_kernel_s);
         }
         last = "no kernel for model " + std::to_string(model);
         return FNN_EHIP;
@@ -474,6 +637,51 @@ int32_t fnn_alignment_pair_counts_ranges_device_i64(const uint8_t* seq, int32_t 
         fnn::DistHipBackend be;
         return fnn::dist_batch_ranges(be, "fnn_alignment_pair_counts_ranges_device_i64", seq, n, L, lds, starts, ends, batch, nullptr, true, device,
                                       reinterpret_cast<double*>(d_F_out), true, ld, stride, stats);
+    )
+}
+
+int32_t fnn_bootscan_counts(int64_t L, const int64_t* starts, const int64_t* ends, int64_t windows, int64_t replicates, int64_t lead, uint64_t seed,
+                            int64_t first, int64_t count, uint16_t* counts_out) {
+    FNN_BATCH_TRY(return fnn::dist_bootscan_counts("fnn_bootscan_counts", L, starts, ends, windows, replicates, lead, seed, first, count, counts_out);)
+}
+
+int32_t fnn_bootscan_distances_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts, const int64_t* ends, int64_t windows,
+                                   int64_t replicates, uint64_t seed, int64_t lead, const fnn_dist_model* m, int32_t device, double* D_out, int64_t ld,
+                                   int64_t stride, fnn_scan_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch_scan(be, "fnn_bootscan_distances_f64", seq, n, L, lds, starts, ends, windows, replicates, seed, lead, m, false, device, D_out,
+                                    false, ld, stride, stats);
+    )
+}
+
+int32_t fnn_bootscan_distances_device_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts, const int64_t* ends, int64_t windows,
+                                          int64_t replicates, uint64_t seed, int64_t lead, const fnn_dist_model* m, int32_t device, double* d_D_out,
+                                          int64_t ld, int64_t stride, fnn_scan_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch_scan(be, "fnn_bootscan_distances_device_f64", seq, n, L, lds, starts, ends, windows, replicates, seed, lead, m, false, device,
+                                    d_D_out, true, ld, stride, stats);
+    )
+}
+
+int32_t fnn_bootscan_pair_counts_i64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts, const int64_t* ends, int64_t windows,
+                                     int64_t replicates, uint64_t seed, int64_t lead, const fnn_dist_model* m, int32_t device, int64_t* F_out, int64_t ld,
+                                     int64_t stride, fnn_scan_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch_scan(be, "fnn_bootscan_pair_counts_i64", seq, n, L, lds, starts, ends, windows, replicates, seed, lead, m, true, device,
+                                    reinterpret_cast<double*>(F_out), false, ld, stride, stats);
+    )
+}
+
+int32_t fnn_bootscan_pair_counts_device_i64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts, const int64_t* ends,
+                                            int64_t windows, int64_t replicates, uint64_t seed, int64_t lead, const fnn_dist_model* m, int32_t device,
+                                            int64_t* d_F_out, int64_t ld, int64_t stride, fnn_scan_stats* stats) {
+    FNN_BATCH_TRY(
+        fnn::DistHipBackend be;
+        return fnn::dist_batch_scan(be, "fnn_bootscan_pair_counts_device_i64", seq, n, L, lds, starts, ends, windows, replicates, seed, lead, m, true, device,
+                                    reinterpret_cast<double*>(d_F_out), true, ld, stride, stats);
     )
 }
 

@@ -705,6 +705,67 @@ int32_t fnn_alignment_pair_counts_ranges_i64(const uint8_t* seq, int32_t n, int6
 int32_t fnn_alignment_pair_counts_ranges_device_i64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts,
                                                     const int64_t* ends, int64_t batch, int32_t device, int64_t* d_F_out,
                                                     int64_t ld, int64_t stride, fnn_range_stats* stats);
+/* ---- bootscan: bootstrap replicates inside every site range ----------------------------------------
+ * The two families above at once: `windows` ranges [starts[w], ends[w]) with 0 <= start <= end <= L (HOST arrays of `windows`
+ * int64_t in every variant), `replicates` = R >= 0 bootstrap replicates of each range alone, and lead = 0 or 1 problems of
+ * original data in front of them.  With P = R + lead the call has windows * P problems, window-major: problem p belongs to
+ * window w = p / P and is number q = p % P of it.
+ *   q < lead:   the window's original data, counts[s] = [starts[w] <= s < ends[w]].
+ *   otherwise:  replicate r = q - lead of window w.  With width = ends[w] - starts[w] and seed_w = the w-th output of SplitMix64
+ *               for `seed` in fnn_bootstrap_counts' convention (z = seed + (w + 1) * 0x9E3779B97F4A7C15, then the two
+ *               multiply-xorshift rounds), draw k = 0 ... width - 1 is x = output r * width + k of SplitMix64 for seed_w and
+ *               increments site starts[w] + floor(x * width / 2^64): row r of fnn_bootstrap_counts(width, R, seed_w) placed at
+ *               columns starts[w] ..., zero elsewhere.
+ * The seed of a window depends on w and not on its bounds: repeated identical ranges get different replicates.  The problems of
+ * window w are, bit for bit, what fnn_bootstrap_distances_batch_f64 gives for the slice seq[:, starts[w]:ends[w]] with
+ * (R + lead, seed_w, lead).  An empty window is P all-zero rows: every pair of them is empty, as with the range entries.
+ * fnn_bootscan_counts (host only, no device) writes rows first ... first + count - 1 of those counts, count x L uint16_t, so
+ * that no caller needs the whole windows * P x L array.  FNN_EINVAL: L <= 0, windows or replicates < 0, a NULL array, a range
+ * outside 0 <= start <= end <= L (fnn_last_error() names the lowest such w), lead outside 0 ... 1, a slice outside
+ * 0 ... windows * P, a count above 65535.
+ * Each distance entry writes the same bytes as its counts entry (fnn_alignment_distances_model_batch[_device]_f64,
+ * fnn_alignment_pair_counts_batch[_device]_i64) writes on those counts, for every model, both saturation policies and gamma
+ * rates, and everything said there holds with p in this call's numbering: layout, chunks and FNN_BATCH_CHUNK (a chunk boundary
+ * may fall inside a window), host output written only on success, the device variant's in-place output and synchronised stream,
+ * K2P's recoding, FNN_DIST_FORCE_MISSING, n == 1, batch == 0 (no window, or P == 0), 127 L < 2^31, all argument checks before
+ * any device use - among them the checks of fnn_bootscan_counts -; a failing call fails with the same status and
+ * fnn_last_error() names the same lowest (b, i, j) and the same kind.
+ * Routes.  While every window's padded span ceil64(end) - floor64(start) is at most fnn_bootstrap_draw_max_sites(), a kernel
+ * draws every problem's row of ONE digit plane, only as long as that span, where the distance kernel reads it, and the distance
+ * kernel walks one window's span against up to 64 (tables: 32) of that window's rows: the uploads per chunk are one table entry
+ * per window and per such group of rows, and of the counts one word per chunk - the largest - comes back.  A chunk whose
+ * largest count exceeds 127 (or every chunk under FNN_DIST_FORCE_DIGITS=2|3) is computed from fnn_bootscan_counts on the host
+ * through the counts entries' own path instead (n_host_chunks); so is the whole call when a window is wider than the limit or
+ * under FNN_DRAW_ROUTE=host (boot.draw_route = FNN_DRAW_HOST; n_host_chunks stays 0), with at most 256 MiB of counts at a time.
+ * FNN_DRAW_ROUTE=device above the limit is FNN_EINVAL before any device use.  All routes give the same bytes.
+ * stats: boot = what the bootstrap entries report (max_count, t_draw_s; digit_passes is the largest of any chunk); n_windows;
+ * n_site_blocks = the 64-site blocks walked, summed over every 16 rows of every group (rows of the host route walk the whole
+ * alignment); n_site_blocks_dense = what the counts entries walk, ceil(problems / 16) * round_up(L, 64) / 64. */
+typedef struct fnn_scan_stats {
+    fnn_boot_stats boot;
+    int64_t n_windows;
+    int64_t n_site_blocks, n_site_blocks_dense;
+    int64_t n_host_chunks;
+    int64_t reserved[4];
+} fnn_scan_stats;
+int32_t fnn_bootscan_counts(int64_t L, const int64_t* starts, const int64_t* ends, int64_t windows, int64_t replicates,
+                            int64_t lead, uint64_t seed, int64_t first, int64_t count, uint16_t* counts_out /* count x L */);
+int32_t fnn_bootscan_distances_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts,
+                                   const int64_t* ends, int64_t windows, int64_t replicates, uint64_t seed, int64_t lead,
+                                   const fnn_dist_model* m, int32_t device, double* D_out, int64_t ld, int64_t stride,
+                                   fnn_scan_stats* stats /* may be NULL */);
+int32_t fnn_bootscan_distances_device_f64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts,
+                                          const int64_t* ends, int64_t windows, int64_t replicates, uint64_t seed, int64_t lead,
+                                          const fnn_dist_model* m, int32_t device, double* d_D_out, int64_t ld, int64_t stride,
+                                          fnn_scan_stats* stats);
+int32_t fnn_bootscan_pair_counts_i64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts,
+                                     const int64_t* ends, int64_t windows, int64_t replicates, uint64_t seed, int64_t lead,
+                                     const fnn_dist_model* m /* ignored; may be NULL */, int32_t device, int64_t* F_out,
+                                     int64_t ld, int64_t stride, fnn_scan_stats* stats /* may be NULL */);
+int32_t fnn_bootscan_pair_counts_device_i64(const uint8_t* seq, int32_t n, int64_t L, int64_t lds, const int64_t* starts,
+                                            const int64_t* ends, int64_t windows, int64_t replicates, uint64_t seed,
+                                            int64_t lead, const fnn_dist_model* m, int32_t device, int64_t* d_F_out,
+                                            int64_t ld, int64_t stride, fnn_scan_stats* stats);
 
 /* ---- split support: how often each split occurs among many problems ---------
  * The last stage of a bootstrap run: the orderings and split weights of `batch` problems over ONE taxon set go in, one
